@@ -15,6 +15,11 @@ region, so the timed region starts with all inputs resident in HBM.
 processes, before anything touches a GPU); under torchrun (RANK / WORLD_SIZE set) it is one of the ranks:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the result line.  `--full` adds what takes work of its own after
+the timed steps: the parity sample against the CPU restatement, the CPU baseline (`--no-cpu-baseline` leaves it out) and the
+secondary lines of the other BASELINE configs (`--no-secondary` leaves them out).  `--dump-outputs DIR` writes what the last
+timed step returned as DIR/<name>.npy (rank 0), so that two builds can be compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -125,6 +130,26 @@ def load_blob(name):
     from mfa_amd import image
     with open(os.path.join(GOLDEN, "images", name + ".dump")) as f:
         return image.blob_from_dump(f.read())
+
+
+DUMP_MAX_ELEMENTS = 2 << 20    # per array: 8 MB of float32 values (+ 16 MB of float64 indices when sampled), 64 MB in all at most
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor as out_dir/<name>.npy in float32.  An array longer than DUMP_MAX_ELEMENTS is written as a
+    seeded sample (the same positions for the same length, run after run) beside out_dir/<name>_index.npy, its positions in float64."""
+    import numpy as np
+    assert len(arrays) <= 2, "DUMP_MAX_ELEMENTS is sized for two arrays"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.Generator(np.random.Philox(0x5EED00D0)).choice(a.size, size=DUMP_MAX_ELEMENTS, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        elif os.path.exists(os.path.join(out_dir, name + "_index.npy")):
+            os.remove(os.path.join(out_dir, name + "_index.npy"))          # (left by a larger run: this array is whole)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 # ---- CPU baseline (rank 0, N = 1 only; bounded sample) ------------------------------------------------------------
@@ -610,14 +635,20 @@ def main():
                     help="weak: every rank generates --strings-per-example strings of each example (fixed work per GPU); strong: ONE batch of "
                          "10 x --strings-per-example strings is cut into --gpus ranges of about equal bytes (sharding.partition_by_bytes) and "
                          "every rank generates and matches its range only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps: parity sample, CPU baseline and secondary lines (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary lines")
     ap.add_argument("--engine", choices=["auto", "table", "jit"], default="auto",
                     help="walk kernels behind mfa_match_mixed: the table-driven walk (one launch per group of strings, any automaton per lane) or the "
                          "kernels generated per automaton (one launch per example); auto = the library's choice (MFA_WALK)")
     ap.add_argument("--cuts", default="", help="development: MFA_MIXED_CUTS, the fractions of the batch at which the region pre-pass is cut into groups")
     ap.add_argument("--order", default="", help="comma-separated order of the examples' segments in the batch (default: costliest walk first)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -708,12 +739,13 @@ def main():
             parts_b.append(d_bytes[:nbytes])
             parts_o.append(d_off[:-1] + pos_b)
             del d_bytes, d_off
-        # the parity sample of this example: a seeded 1 % of its strings, whatever their length
+        # the parity sample of this example: a seeded 1 % of its strings, whatever their length (host copies: --full only)
         n_par = max(1, int(round(count * PARITY_FRACTION))) if count else 0
         par_idx = np.sort(rng_par.choice(count, size=n_par, replace=False)) if n_par else np.zeros(0, dtype=np.int64)
+        host_copies = rank == 0 and args.full
         shards[ex] = {"img": img, "n": count, "nbytes": nbytes, "blob": blob, "first": pos_s, "par_idx": par_idx,
-                      "par_strings": corpus.host_strings(ex, sizes[par_idx], with_suffix[par_idx]) if rank == 0 else [],
-                      "sample": corpus.host_strings(ex, sizes[:BASELINE_N], with_suffix[:BASELINE_N]) if rank == 0 else []}
+                      "par_strings": corpus.host_strings(ex, sizes[par_idx], with_suffix[par_idx]) if host_copies else [],
+                      "sample": corpus.host_strings(ex, sizes[:BASELINE_N], with_suffix[:BASELINE_N]) if host_copies else []}
         pos_s += count
         pos_b += nbytes
     total_strings, total_bytes = pos_s, pos_b
@@ -846,7 +878,10 @@ def main():
                                                 "note": "runs beside the walk kernels of earlier groups"}},
             "order": layout, "per_example": per_ex,
         }
-        if world == 1 or args.scaling == "weak":
+        if args.dump_outputs:
+            # what the last timed step handed back: this rank's result codes and the step's bitmap (gathered results with N > 1)
+            dump_outputs(args.dump_outputs, {"results": results, ("gathered_results" if dist else "bitmap"): gathered})
+        if args.full and (world == 1 or args.scaling == "weak"):
             # parity at scale: a seeded 1 % of every example's strings, no length cap, against the CPU restatement
             jobs = []
             for ex in layout:
@@ -855,13 +890,13 @@ def main():
                     got = results[sh["first"] + torch.from_numpy(sh["par_idx"]).to(results.device)].cpu().numpy()
                     jobs.append((sh["blob"], sh["par_strings"], got))
             out["parity_sample"] = parity_sample(jobs)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             gpu_res = {ex: results[sh["first"]:sh["first"] + BASELINE_N].cpu().numpy() for ex, sh in shards.items()}
             out["cpu_baseline"] = cpu_baseline(corpus, shards, gpu_res)
             if out["cpu_baseline"] is not None and out.get("parity_sample"):
                 out["cpu_baseline"]["parity_restatement"] = {k: out["parity_sample"][k] for k in ("strings", "bytes", "max_len", "mismatches")}
                 out["cpu_baseline"]["parity"] = bool(out["cpu_baseline"]["parity"]) and out["parity_sample"]["mismatches"] == 0
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             mixed.close()
             del bytes_all, off_all
             torch.cuda.empty_cache()

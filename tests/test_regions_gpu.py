@@ -332,13 +332,13 @@ def test_shared_region_table_for_several_automata():
 
 
 def test_bench_line_smoke():
-    """bench.py end to end at a small size: one JSON line with the contract's fields, the roofline and the cpu_baseline objects"""
+    """bench.py --full end to end at a small size: one JSON line with the contract's fields, the roofline and the cpu_baseline objects"""
     import json
     import subprocess
     import sys
     root = oracle_lib.ROOT
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--strings-per-example", "3000", "--steps", "2", "--warmup", "1",
-                        "--no-secondary"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-secondary"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1
@@ -355,6 +355,36 @@ def test_bench_line_smoke():
     ps = d["parity_sample"]
     assert ps["strings"] >= 10 * 30 and ps["mismatches"] == 0 and ps["max_len"] > 20000
     assert c["parity_restatement"]["strings"] == ps["strings"]
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the headline line only (no parity sample, CPU baseline or secondary lines), and --dump-outputs writes
+    the last timed step's result codes and bitmap, which agree with each other, with the line and with a second run"""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from mfa_amd import sharding
+    root = oracle_lib.ROOT
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--strings-per-example", "3000", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert not {"parity_sample", "cpu_baseline", "secondary"} & set(d)
+        res, bm = np.load(out / "results.npy"), np.load(out / "bitmap.npy")
+        assert res.dtype == np.float32 and bm.dtype == np.float32
+        assert res.shape == (30000,) and set(np.unique(res)) <= {0.0, 1.0, 2.0}
+        assert int((res == 1).sum()) == sum(e["accepted"] for e in d["per_example"].values())
+        bits = sharding.unpack_bitmap(torch.from_numpy(bm.astype(np.uint8)), res.size).numpy()
+        assert np.array_equal(bits, (res == 1).astype(np.uint8))
+        runs.append(res)
+    assert np.array_equal(runs[0], runs[1])
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
@@ -399,7 +429,7 @@ def test_bench_single_rank_rccl():
     env.update({"MFA_BENCH_FORCE_DIST": "1", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1"})
     env.pop("MASTER_PORT", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--strings-per-example", "3000", "--steps", "2", "--warmup", "1",
-                        "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1

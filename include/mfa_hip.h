@@ -138,11 +138,7 @@ int  mfa_match_batch_regions(mfa_image_t* img, const uint8_t* d_bytes, const uin
  * as soon as its regions are known: the region launches go to `stream` itself, the walks to internal streams, so that
  * the walk of a group runs beside the region pass of the next (one region launch per group, the walks wait for the event
  * behind it).  Calls on one object are ordered one behind the other, also when they come on different streams (the object's
- * table and work areas are shared).  (MFA_MIXED_GATE=1, table-driven
- * walk only: the region pass is ONE launch over the whole batch; it counts every finished string for its group, a
- * one-wave kernel in front of a group's walk launches ends when the group is complete, and every word of a table row
- * carries the call's stamp, so that a walk never takes a row that has not arrived yet -- or a stale copy of an earlier
- * call's -- for this call's.  Measured: not faster; kept as an option.)  `stream` sees the call as a single operation: it waits for the internal streams before the call
+ * table and work areas are shared).  `stream` sees the call as a single operation: it waits for the internal streams before the call
  * returns, ALSO when the call returns an error (whatever was started is ordered before the caller's next
  * operation on `stream`). */
 typedef struct mfa_mixed mfa_mixed_t;
@@ -170,8 +166,8 @@ int  mfa_mixed_last_ms(mfa_mixed_t* mx, int device, float* region_ms, float* spa
 /* the same for the call `back` calls ago (0 = the last one; the events of the last 32 calls are kept, so a sequence of calls can be
  * timed without synchronising between them) */
 int  mfa_mixed_timing(mfa_mixed_t* mx, int device, uint32_t back, float* region_ms, float* span_ms);
-/* what the last call on `device` launched (any pointer may be NULL): region launches (1 when the walks are released by counters),
- * walk launches, groups of strings, and gated = 1 if the walks were released by counters, 0 if by events */
+/* what the last call on `device` launched (any pointer may be NULL): region launches, walk launches, groups of strings, and
+ * gated, always 0 (kept for compatibility) */
 int  mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launches, uint32_t* walk_launches, uint32_t* groups, uint32_t* gated);
 
 /* The result vector of a batch as a bitmap: bit k % 8 of byte k / 8 of d_bitmap ((n + 7) / 8 bytes, device memory) = string k was accepted

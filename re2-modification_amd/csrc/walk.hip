@@ -76,7 +76,7 @@ walk_kernel(WalkArgs a) {
     st.gsb = g; g += XI * W * 64u;
     st.gsa = g; g += XI * DW * 64u;
     st.gq = g;
-    Batch b{a.bytes, a.offsets, a.n, a.results, a.regions, a.accel, a.refill, a.n_seg, a.seg_first, a.seg_table, a.gate,
+    Batch b{a.bytes, a.offsets, a.n, a.results, a.regions, a.accel, a.refill, a.n_seg, a.seg_first, a.seg_table, 0u,
             a.lean_queue, reinterpret_cast<uint32_t*>(a.counter + 1)};
     TicketFeeder feed{a.counter, a.n, gwave * 64u};
 #if WALK_STATS

@@ -44,7 +44,7 @@ static size_t wave_words(uint32_t K, uint32_t C, bool ig, uint32_t nm_words = 0)
 // longest possible list if that leaves room for two workgroups per CU, else what does (longer lists spill to `d_spill`).
 int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                 uint8_t* d_results, const uint64_t* d_regions, uint32_t n_seg, const uint32_t* seg_first, const uint32_t* seg_table,
-                uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, uint32_t gate, LeanHint* lean, void* wait_event) {
+                uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, LeanHint* lean, void* wait_event) {
     if (n == 0) { if (wait_event) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)wait_event, 0)); return MFA_OK; }
     if (n_seg == 0 || n_seg > WALK_MAX_SEG || n > 0xffffffffull) return MFA_ERR_INVALID_ARG;
     WalkLaunch L;
@@ -52,7 +52,6 @@ int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, con
     std::memset(&a, 0, sizeof a);
     a.bytes = d_bytes; a.offsets = d_offsets; a.n = n; a.results = d_results; a.regions = d_regions; a.tables = d_tables;
     a.counter = d_counter;
-    a.gate = gate;
     a.table_words = p.table_words;
     a.shared_words = (p.table_words + 63u) & ~63u;
     // tables beyond a third of the LDS (or forced: development) stay in global memory
@@ -209,7 +208,6 @@ struct mfa_mixed {
     std::map<uint64_t, uint64_t> bytes_of;                     // string count of a batch -> its bytes (read back once, see mfa_match_mixed)
     struct Dev {
         uint32_t* d_tables = nullptr;
-        hipStream_t rs = nullptr;                              // region stream (the gate; MFA_MIXED_REGION_ON_CALLER=0)
         hipStream_t last_cs = nullptr;                         // the caller's stream of the last call
         hipStream_t ws[MIX_MAX_STREAMS] = {nullptr};           // walk streams
         hipEvent_t ev_g[MIX_MAX_GROUPS] = {nullptr};           // group g's regions are known (timed)
@@ -223,13 +221,7 @@ struct mfa_mixed {
         LeanHint lean[MIX_MAX_LAUNCHES];
         unsigned long long* d_counters = nullptr;
         int n_cus = 0;
-        // the gate: ONE region launch per call; in front of a group's walk launches, on their stream, one wave that ends when the region
-        // kernel has counted every string of the group (regions.hip: GATE)
-        int gate_state = 0;                                    // 0 not tried, 1 usable, -1 not
-        uint64_t* h_hdr = nullptr;                             // pinned: the gate headers of the last MIX_TIMINGS calls
-        hipEvent_t ev_clear = nullptr;
         uint32_t last_region_launches = 0, last_walk_launches = 0, last_groups = 0;
-        bool last_gated = false;
         bool timed = false, calibrated = false;
         std::vector<float> cost;                               // per segment: its walk alone, ms
         float ready[MIX_MAX_GROUPS] = {0};                     // per group: end of its region launch, ms from the start of the call
@@ -276,7 +268,6 @@ void mfa_mixed_destroy(mfa_mixed_t* mx) {
     for (auto& kv : mx->dev) {
         (void)hipSetDevice(kv.first);
         mfa_mixed::Dev& d = kv.second;
-        if (d.rs) (void)hipStreamSynchronize(d.rs);
         for (hipStream_t w : d.ws) if (w) (void)hipStreamSynchronize(w);
         if (d.calls > 0) (void)hipEventSynchronize(d.ev_end[(d.calls - 1) % MIX_TIMINGS]);      // (region launches on a caller's stream)
         if (d.d_tables) (void)hipFree(d.d_tables);
@@ -284,13 +275,10 @@ void mfa_mixed_destroy(mfa_mixed_t* mx) {
         for (uint32_t* p : d.d_spill) if (p) (void)hipFree(p);
         for (LeanHint& h : d.lean) lean_hint_free(h);
         if (d.d_counters) (void)hipFree(d.d_counters);
-        if (d.h_hdr) (void)hipHostFree(d.h_hdr);
-        if (d.ev_clear) (void)hipEventDestroy(d.ev_clear);
         for (hipEvent_t e : d.ev_g) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : d.ev_w) if (e) (void)hipEventDestroy(e);
         if (d.ev_in) (void)hipEventDestroy(d.ev_in);
         for (uint32_t k = 0; k < MIX_TIMINGS; k++) for (hipEvent_t e : {d.ev_r0[k], d.ev_r1[k], d.ev_end[k]}) if (e) (void)hipEventDestroy(e);
-        if (d.rs) (void)hipStreamDestroy(d.rs);
         for (hipStream_t w : d.ws) if (w) (void)hipStreamDestroy(w);
     }
     if (cur >= 0) (void)hipSetDevice(cur);
@@ -312,27 +300,16 @@ static int mixed_device(mfa_mixed* mx, int device, mfa_mixed::Dev** out) {
         HIP_TRY(hipMemcpy(d.d_tables, mx->words.data(), mx->words.size() * 4, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMalloc((void**)&d.d_counters, 64 * MIX_MAX_LAUNCHES * sizeof(unsigned long long)));
-    HIP_TRY(hipStreamCreateWithFlags(&d.rs, hipStreamNonBlocking));
-    // Streams are made when a call first needs them (walk_stream / region_stream2): every stream beyond the hardware queues of the process (four
+    // Streams are made when a call first needs them (the walk streams: match_mixed_impl): every stream beyond the hardware queues of the process (four
     // by default, the caller's included) shares a queue with another one, and work on streams that share a queue is serialised
     for (hipEvent_t& e : d.ev_g) HIP_TRY(hipEventCreate(&e));
     for (hipEvent_t& e : d.ev_w) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d.ev_in, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d.ev_clear, hipEventDisableTiming));
     for (uint32_t k = 0; k < MIX_TIMINGS; k++) { HIP_TRY(hipEventCreate(&d.ev_r0[k])); HIP_TRY(hipEventCreate(&d.ev_r1[k])); HIP_TRY(hipEventCreate(&d.ev_end[k])); }
     d.cost.assign(mx->images.size(), 0.0f);
     auto ins = mx->dev.emplace(device, d);
     *out = &ins.first->second;
     return MFA_OK;
-}
-
-// Is the gate usable on this device?  Decided once.
-static bool gate_ready(mfa_mixed::Dev& d) {
-    if (d.gate_state != 0) return d.gate_state > 0;
-    d.gate_state = -1;
-    if (hipHostMalloc((void**)&d.h_hdr, MIX_TIMINGS * MFA_GATE_FIXED_WORDS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) { d.h_hdr = nullptr; (void)hipGetLastError(); return false; }
-    d.gate_state = 1;
-    return true;
 }
 
 // What a call will launch, decided before anything is put on a stream (an error found here leaves the streams untouched).
@@ -412,13 +389,6 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     int NW = env_int("MFA_MIXED_WALK_STREAMS", table ? 2 : 3);
     if (NW < 1) NW = 1;
     if (NW > (int)MIX_MAX_STREAMS) NW = MIX_MAX_STREAMS;
-    // ONE region launch for the whole batch and the walks released group by group (the gate): table engine, more than one group.
-    // Built, checked (tests/test_regions_gpu.py::test_gated_walks_see_fresh_tables) and measured in round 4 -- and NOT the default: it saves
-    // seven region launches, and the step takes as long or longer (4.29 against 3.84-4.18 ms on one box; kernel traces in
-    // profiles/r04d_trace_*.txt).  What a launch's ramp and tail leave idle, the walk kernels beside it use: with one launch the walks take
-    // 5.3 ms of stream time instead of 4.2, the region pass 3.83 ms instead of 3.9 for its eight launches.  MFA_MIXED_GATE=1 turns it on.
-    const bool gate = table && with_regions && ng > 1 && ng <= MFA_GATE_MAX_GROUPS && env_int("MFA_MIXED_GATE", 0) != 0 && gate_ready(*d);
-    const uint32_t stamp = (uint32_t)(d->calls & 0xfffu);     // what every word of this call's table rows carries (the table buffer is rewritten by every call)
 
     // One automaton, one group: exactly the single-automaton call (mfa_match_batch: region pass, then the walk, on the caller's stream, with the
     // engine that call would choose) -- the hops to the internal streams and back cost such a batch 0.03-0.06 ms and buy it nothing.  (Cutting a
@@ -434,7 +404,7 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         HIP_TRY(hipEventRecord(d->ev_end[slot1], cs));
         if (rc != MFA_OK) return rc;
         d->timed = true; d->calls++; d->ng_last = 1;
-        d->last_region_launches = with_regions ? 1u : 0u; d->last_walk_launches = 1; d->last_groups = 1; d->last_gated = false;
+        d->last_region_launches = with_regions ? 1u : 0u; d->last_walk_launches = 1; d->last_groups = 1;
         return MFA_OK;
     }
 
@@ -466,10 +436,9 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     if (plan.size() > MIX_MAX_LAUNCHES) return MFA_ERR_UNSUPPORTED;      // (more runs of equal cell count than the object has launch slots: nothing was started)
     uint64_t* d_table = nullptr;
     if (with_regions) {
-        const size_t head = gate ? MFA_GATE_HEADER_WORDS : 0;
-        rc = ctx_reserve((void**)&d->d_regions, &d->region_bytes, ((size_t)n * MFA_REGION_WORDS + MFA_GATE_HEADER_WORDS) * sizeof(uint64_t));
+        rc = ctx_reserve((void**)&d->d_regions, &d->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
         if (rc != MFA_OK) return rc;
-        d_table = d->d_regions + head;
+        d_table = d->d_regions;
     }
     // which stream walks which segment (generated kernels): first call one after the other (timed), then by cost
     std::vector<int> where(ns, 0);
@@ -487,94 +456,58 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         }
     }
     for (int k = 0; k < NW; k++)
-        if (!d->ws[k]) {
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            if (env_int("MFA_MIXED_WALK_PRIORITY", 0) != 0) HIP_TRY(hipStreamCreateWithPriority(&d->ws[k], hipStreamNonBlocking, greatest));
-            else HIP_TRY(hipStreamCreateWithFlags(&d->ws[k], hipStreamNonBlocking));
-        }
+        if (!d->ws[k]) HIP_TRY(hipStreamCreateWithFlags(&d->ws[k], hipStreamNonBlocking));
     const uint32_t slot_t = (uint32_t)(d->calls % MIX_TIMINGS);
-    // The region launches go to the CALLER's stream (MFA_MIXED_REGION_ON_CALLER=0, or the gate: to a stream of the object's own): back-to-back calls
-    // then pass from the last walk of one to the first region launch of the next through ONE event (walk stream -> caller's stream) instead of
-    // three (walk stream -> region stream -> caller's stream -> region stream): 0.02 ms a call.
-    hipStream_t const rs = (!gate && env_int("MFA_MIXED_REGION_ON_CALLER", 1) != 0) ? cs : d->rs;
-
     // ---- from here on work goes to the internal streams.  Whatever happens, the caller's stream is made to wait for all of it before this
     // function returns: a caller that gets an error may free or reuse its buffers in stream order like one that gets MFA_OK.
     struct Join {
-        mfa_mixed::Dev* d; hipStream_t cs, rs; int NW; uint32_t slot_t; bool used[MIX_MAX_STREAMS] = {false}; bool started = false; int err = MFA_OK;
+        mfa_mixed::Dev* d; hipStream_t cs; int NW; uint32_t slot_t; bool used[MIX_MAX_STREAMS] = {false}; bool started = false; int err = MFA_OK;
         void run() {
             if (!started) return;
             started = false;
             for (int k = 0; k < NW; k++)
                 if (used[k]) {
-                    if (hipEventRecord(d->ev_w[k], d->ws[k]) != hipSuccess || hipStreamWaitEvent(rs, d->ev_w[k], 0) != hipSuccess) { err = MFA_ERR_HIP; (void)hipStreamSynchronize(d->ws[k]); }
+                    if (hipEventRecord(d->ev_w[k], d->ws[k]) != hipSuccess || hipStreamWaitEvent(cs, d->ev_w[k], 0) != hipSuccess) { err = MFA_ERR_HIP; (void)hipStreamSynchronize(d->ws[k]); }
                 }
-            if (hipEventRecord(d->ev_end[slot_t], rs) != hipSuccess || (rs != cs && hipStreamWaitEvent(cs, d->ev_end[slot_t], 0) != hipSuccess)) { err = MFA_ERR_HIP; (void)hipStreamSynchronize(rs); }
+            if (hipEventRecord(d->ev_end[slot_t], cs) != hipSuccess) { err = MFA_ERR_HIP; (void)hipStreamSynchronize(cs); }
         }
         ~Join() { run(); }
-    } join{d, cs, rs, NW, slot_t};
-    // (the object's buffers -- table, counters, spill areas -- are shared by its calls: with the region launches on an internal stream the calls
-    // follow each other there; on callers' streams a call starts behind the end of the one before it, whichever stream that one came on)
+    } join{d, cs, NW, slot_t};
+    // (the object's buffers -- table, counters, spill areas -- are shared by its calls: a call starts behind the end of the one before it,
+    // whichever stream that one came on)
     if (d->calls > 0 && d->last_cs != cs) HIP_TRY(hipStreamWaitEvent(cs, d->ev_end[(d->calls - 1) % MIX_TIMINGS], 0));      // (the walk streams start behind ev_in: below)
     d->last_cs = cs;
     HIP_TRY(hipEventRecord(d->ev_in, cs));
-    if (rs != cs) HIP_TRY(hipStreamWaitEvent(rs, d->ev_in, 0));
     join.started = true;
-    if (gate) {
-        // the gate header in front of the table (regions.hip: gate_signal), the counters back to zero; the walk streams start behind both
-        uint64_t* h = d->h_hdr + (size_t)slot_t * MFA_GATE_FIXED_WORDS;
-        for (uint32_t k = 0; k < MFA_GATE_FIXED_WORDS; k++) h[k] = 0ull;
-        for (uint32_t k = 0; k < MFA_GATE_MAX_GROUPS; k++) h[MFA_GATE_FIXED_WORDS - 1 - k] = k < ng ? cut[k + 1] : ~0ull;
-        h[MFA_GATE_FIXED_WORDS - 33] = (uint64_t)stamp << 52;
-        HIP_TRY(hipMemsetAsync(d->d_regions, 0, (MFA_GATE_HEADER_WORDS - MFA_GATE_FIXED_WORDS) * sizeof(uint64_t), rs));      // the counters
-        HIP_TRY(hipMemcpyAsync(d->d_regions + (MFA_GATE_HEADER_WORDS - MFA_GATE_FIXED_WORDS), h, MFA_GATE_FIXED_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, rs));
-        HIP_TRY(hipEventRecord(d->ev_clear, rs));
-    }
-    for (int k = 0; k < NW; k++) HIP_TRY(hipStreamWaitEvent(d->ws[k], gate ? d->ev_clear : d->ev_in, 0));
-    HIP_TRY(hipEventRecord(d->ev_r0[slot_t], rs));
+    for (int k = 0; k < NW; k++) HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_in, 0));
+    // The region launches go to the CALLER's stream: back-to-back calls pass from the last walk of one to the first region launch of the next
+    // through ONE event (walk stream -> caller's stream) instead of three through a region stream of the object's own: 0.02 ms a call.
+    HIP_TRY(hipEventRecord(d->ev_r0[slot_t], cs));
     uint32_t region_launches = 0;
-    const bool ext_events = table && !gate && env_int("MFA_MIXED_EXT_EVENTS", 1) != 0;      // a group's event = its region launch's completion signal
-    if (gate) {
-        rc = launch_region_scan(d->n_cus, d_bytes, d_offsets, n, d_table, rs, 128u, true);
-        if (rc != MFA_OK) return rc;
-        region_launches = 1;
-    }
     uint32_t slot = 0;
     for (uint32_t g = 0; g < ng; g++) {
         const uint64_t lo = cut[g], hi = cut[g + 1];
-        if (with_regions && !gate) {
-            rc = launch_region_scan(d->n_cus, d_bytes, d_offsets + lo, hi - lo, d_table + lo * MFA_REGION_WORDS, rs, table ? 128u : 256u, false, ext_events ? d->ev_g[g] : nullptr);
+        // a group's event: the table engine's is its region launch's completion signal (no packet of its own between region launches)
+        if (with_regions) {
+            rc = launch_region_scan(d->n_cus, d_bytes, d_offsets + lo, hi - lo, d_table + lo * MFA_REGION_WORDS, cs, table ? 128u : 256u, table ? d->ev_g[g] : nullptr);
             if (rc != MFA_OK) return rc;
             region_launches++;
         }
-        if (!gate && !(with_regions && ext_events)) HIP_TRY(hipEventRecord(d->ev_g[g], rs));
+        if (!(with_regions && table)) HIP_TRY(hipEventRecord(d->ev_g[g], cs));
+        // a stream's first launch of this group waits for the group's event
         bool waits[MIX_MAX_STREAMS] = {false};
-        // a stream's first launch of this group waits for the group's regions: for the event behind its region launch, or -- with the gate -- for
-        // one wave, launched in front of it, that ends when the region kernel has counted every string of the group
-        auto release = [&](int k) -> int {
-            if (waits[k]) return MFA_OK;
-            waits[k] = true;
-            if (gate) { join.used[k] = true; return launch_gate_wait(d_table, g, d->ws[k]); }
-            HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_g[g], 0));
-            return MFA_OK;
-        };
         if (table) {
             for (const MixLaunch& L : plan) {
                 if (L.g != g) continue;
-                void* wait_for = nullptr;                       // (without the gate the launch itself waits, behind its own preparations on the stream)
-                if (!gate && !waits[L.k]) { waits[L.k] = true; wait_for = d->ev_g[g]; }
-                else {
-                    rc = release(L.k);
-                    if (rc != MFA_OK) return rc;
-                }
+                void* wait_for = nullptr;                       // (the launch itself waits, behind its own preparations on the stream)
+                if (!waits[L.k]) { waits[L.k] = true; wait_for = d->ev_g[g]; }
                 uint32_t sf[WALK_MAX_SEG + 1], stb[WALK_MAX_SEG];
                 for (uint32_t j = 0; j <= L.s1 - L.s0; j++) sf[j] = (uint32_t)(std::min(std::max(seg_first[L.s0 + j], L.a), L.b) - L.a);
                 for (uint32_t j = 0; j < L.s1 - L.s0; j++) stb[j] = mx->block_at[L.s0 + j] - L.w0;
                 const WalkPlanInput pk{L.Kc, L.ml, mx->reversed, L.w1 - L.w0};
                 join.used[L.k] = true;
                 rc = launch_walk(pk, d->d_tables + L.w0, d->n_cus, d_bytes, d_offsets + L.a, L.b - L.a, d_results + L.a, d_table ? d_table + L.a * MFA_REGION_WORDS : nullptr,
-                                 L.s1 - L.s0, sf, stb, &d->d_spill[slot], &d->spill_bytes[slot], d->d_counters + 64 * slot, d->ws[L.k], gate ? (0x1000u | stamp) : 0u, &d->lean[slot], wait_for);
+                                 L.s1 - L.s0, sf, stb, &d->d_spill[slot], &d->spill_bytes[slot], d->d_counters + 64 * slot, d->ws[L.k], &d->lean[slot], wait_for);
                 if (rc != MFA_OK) return rc;
                 slot++;
             }
@@ -587,8 +520,7 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
                 const uint64_t a = std::max(seg_first[s], lo), b = std::min(seg_first[s + 1], hi);
                 if (b <= a) continue;
                 const int k = where[s];
-                rc = release(k);
-                if (rc != MFA_OK) return rc;
+                if (!waits[k]) { waits[k] = true; HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_g[g], 0)); }
                 join.used[k] = true;
                 rc = mfa_match_batch_regions(mx->images[s], d_bytes, d_offsets + a, b - a, d_results + a, d_table ? d_table + a * MFA_REGION_WORDS : nullptr, device, d->ws[k]);
                 if (rc != MFA_OK) return rc;
@@ -596,14 +528,14 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
             }
         }
     }
-    HIP_TRY(hipEventRecord(d->ev_r1[slot_t], rs));
-    // the caller's stream (and the call's end event, on the region stream) wait for every stream that was given work
+    HIP_TRY(hipEventRecord(d->ev_r1[slot_t], cs));
+    // the caller's stream (and with it the call's end event) waits for every stream that was given work
     join.run();
     if (join.err != MFA_OK) return join.err;
     d->timed = true;
     d->calls++;
     d->ng_last = ng;
-    d->last_region_launches = region_launches; d->last_walk_launches = slot; d->last_groups = ng; d->last_gated = gate;
+    d->last_region_launches = region_launches; d->last_walk_launches = slot; d->last_groups = ng;
     if (calibrating) {                                        // once per device: the walks' costs and the groups' region times
         HIP_TRY(hipEventSynchronize(d->ev_end[slot_t]));
         for (uint32_t s = 0; s < ns; s++) {
@@ -612,7 +544,7 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         }
         for (uint32_t g = 0; g < ng; g++) {
             // the calibration pass runs a group's walks before the next group's region launch is reached by nothing: region launches
-            // follow each other on their own stream, so the elapsed time between two group events is the later group's region time
+            // follow each other on the caller's stream, so the elapsed time between two group events is the later group's region time
             float ms = 0.0f;
             HIP_TRY(hipEventElapsedTime(&ms, d->ev_r0[slot_t], d->ev_g[g]));
             d->ready[g] = ms;
@@ -632,8 +564,8 @@ int mfa_match_mixed_sized(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint64_
     return match_mixed_impl(mx, d_bytes, d_offsets, n, seg_first, d_results, device, stream, total_bytes);
 }
 
-// what the last call on `device` launched (any pointer may be NULL): region launches (1 with the gate), walk launches, groups of strings, and
-// whether the walks were released by counters (1) or by events behind per-group region launches (0)
+// what the last call on `device` launched (any pointer may be NULL): region launches, walk launches, groups of strings, and `gated`, always 0
+// (kept for compatibility)
 int mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launches, uint32_t* walk_launches, uint32_t* groups, uint32_t* gated) {
     if (!mx) return MFA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(mx->mu);
@@ -642,7 +574,7 @@ int mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launch
     if (region_launches) *region_launches = it->second.last_region_launches;
     if (walk_launches) *walk_launches = it->second.last_walk_launches;
     if (groups) *groups = it->second.last_groups;
-    if (gated) *gated = it->second.last_gated ? 1u : 0u;
+    if (gated) *gated = 0u;
     return MFA_OK;
 }
 

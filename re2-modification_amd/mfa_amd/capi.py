@@ -205,7 +205,7 @@ class Mixed:
         return d_results[:n]
 
     def last_launches(self, device=0):
-        """what the last call launched: {"region_launches", "walk_launches", "groups", "gated"}"""
+        """what the last call launched: {"region_launches", "walk_launches", "groups", "gated"} ("gated" is always False, kept for compatibility)"""
         v = [ctypes.c_uint32() for _ in range(4)]
         _check(lib().mfa_mixed_last_launches(self._h, device, *[ctypes.byref(x) for x in v]), "mfa_mixed_last_launches")
         return {"region_launches": v[0].value, "walk_launches": v[1].value, "groups": v[2].value, "gated": bool(v[3].value)}

@@ -64,7 +64,7 @@ def test_no_cpu_fallback():
 def test_register_budget_of_the_built_kernels():
     """The region pass shares SIMDs with walk waves (512 VGPRs each): its streaming kernel must stay within 40 VGPRs (an allocation of 40,
     not 48) and the one-cell walk within 176 (2 x 176 + 4 x 40 = 512), or one region wave fewer fits beside two walk waves.  Read from the build's own resource
-    remarks (csrc/Makefile keeps them and fails the build on the first of the two)."""
+    remarks (csrc/Makefile keeps them and warns when the first of the two is over)."""
     import re
     csrc = os.path.join(os.path.dirname(capi.LIB_PATH))
     def vgprs(log, name_part):

@@ -440,12 +440,13 @@ def test_bench_single_rank_rccl():
     assert "shard needs about" in p.stderr                        # the HBM preflight of multi-rank runs
 
 
-def test_gated_walks_see_fresh_tables(monkeypatch):
-    """The gate of mfa_match_mixed (ONE region launch, the walks of a group released by a counter the region kernel raises; walk_launch.hip,
-    regions.hip: gate_signal): the walk kernels start while the region kernel is still running and read table rows that other CUs -- other
-    XCDs -- have just written.  Two batches of the SAME shape and DIFFERENT content go through one mixed object in turn (one table buffer,
-    rewritten by every call): a walk that read a stale row -- the other batch's regions -- would walk over bytes that do not repeat and
-    answer wrongly.  Every call is compared with the ungated schedule (events behind per-group region launches) and a sample with the oracle."""
+def test_mixed_calls_see_fresh_tables(monkeypatch):
+    """mfa_match_mixed puts a group's region launch on the caller's stream and starts the group's walks on internal streams behind its
+    completion event, so a walk reads table rows that other CUs -- other XCDs -- have just written.  Two batches of the SAME shape and
+    DIFFERENT content go through one mixed object in turn (one table buffer, rewritten by every call), without a synchronisation between
+    the calls, the second half of them alternating between two caller streams: a walk that read a stale row -- the other batch's regions --
+    would walk over bytes that do not repeat and answer wrongly.  Every call is compared with the single-automaton answers of its batch,
+    and those with a sample of the oracle."""
     import torch
     from mfa_amd import corpus
     dev = torch.device("cuda", 0)
@@ -472,30 +473,30 @@ def test_gated_walks_see_fresh_tables(monkeypatch):
     A, B = batch(0), batch(1)
     monkeypatch.setenv("MFA_WALK", "table")
     monkeypatch.setenv("MFA_MIXED_CUTS", "0.15,0.3,0.45,0.6,0.75,0.87,0.95")
-    mx = capi.Mixed(images)
     ref = {}
-    monkeypatch.setenv("MFA_MIXED_GATE", "0")
     for tag, (bts, off, seg, samples, total) in (("A", A), ("B", B)):
-        ref[tag] = mx.match_tensors(bts, off, seg).clone()
+        ref[tag] = torch.cat([images[k].match_tensors(bts, off[seg[k]:seg[k + 1] + 1]) for k in range(len(layout))])
         torch.cuda.synchronize()
-        assert not mx.last_launches()["gated"] and mx.last_launches()["region_launches"] == 8
         for k, (short, strings) in enumerate(samples):
             want = oracle_lib.OracleImage(blobs[k]).match(strings)
             assert np.array_equal(ref[tag][seg[k]:seg[k + 1]][short].cpu().numpy(), want), (tag, layout[k])
     assert not torch.equal(ref["A"], ref["B"])
-    monkeypatch.setenv("MFA_MIXED_GATE", "1")
-    res = torch.empty_like(ref["A"])
-    for r in range(40):
-        tag, (bts, off, seg, samples, total) = (("A", A), ("B", B))[r % 2]
-        res.fill_(7)
-        mx.match_tensors(bts, off, seg, res, total_bytes=total)
-        torch.cuda.synchronize()
+    mx = capi.Mixed(images)
+    calls = 40
+    res = [torch.full_like(ref["A"], 7) for _ in range(calls)]
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for r in range(calls):
+        bts, off, seg, samples, total = (A, B)[r % 2]
+        stream = None if r < calls // 2 else (s1, s2)[r % 2]
+        mx.match_tensors(bts, off, seg, res[r], stream=stream, total_bytes=total)
         la = mx.last_launches()
-        assert la["gated"] and la["region_launches"] == 1 and la["groups"] == 8
-        bad = torch.nonzero(res != ref[tag]).flatten()
-        assert bad.numel() == 0, "round %d (%s): %d answers differ from the ungated schedule, first at string %d" % (r, tag, bad.numel(), int(bad[0]))
-    # the tables themselves: the gated launch writes what per-group launches write
-    monkeypatch.setenv("MFA_MIXED_GATE", "0")
+        assert not la["gated"] and la["region_launches"] == 8 and la["groups"] == 8, (r, la)
+    torch.cuda.synchronize()
+    for r in range(calls):
+        tag = "AB"[r % 2]
+        bad = torch.nonzero(res[r] != ref[tag]).flatten()
+        assert bad.numel() == 0, "call %d (%s): %d answers differ from the single-automaton ones, first at string %d" % (r, tag, bad.numel(), int(bad[0]))
     mx.close()
 
 

@@ -8,7 +8,7 @@ timeout -k 10 300 rocprofv3 --output-format csv --kernel-trace -d $out/tr -o t -
 python3 - <<PY
 import csv, glob
 f = glob.glob("$out/tr/**/*kernel_trace.csv", recursive=True)[0]
-rows = [r for r in csv.DictReader(open(f)) if any(k in r["Kernel_Name"] for k in ("region_scan", "walk_kernel", "gate_wait"))]
+rows = [r for r in csv.DictReader(open(f)) if any(k in r["Kernel_Name"] for k in ("region_scan", "walk_kernel"))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last step = from the last-but-zero'th region launch group: find starts of steps as region launches that follow a walk
 regs = [i for i, r in enumerate(rows) if "region_scan" in r["Kernel_Name"]]

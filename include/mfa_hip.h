@@ -99,7 +99,23 @@ int  mfa_image_specialize(mfa_image_t* img);
  * larger buffer needs up to 15 bytes of slack behind it).  The bytes there are never interpreted.
  * Asynchronous: work is enqueued on `stream` (a hipStream_t, NULL = default
  * stream) and the call returns.  Replaces: the loop
- *     while (...) { match = automata->match(text); }      match.cpp:21-31 */
+ *     while (...) { match = automata->match(text); }      match.cpp:21-31
+ *
+ * Long strings of a memory-less automaton (MFA_KIND_NFA).  The table kernels walk one string per lane, so a call would take as long
+ * as its longest string.  A string of MFA_DFA_SPLIT_MIN bytes or more (default 65536) is therefore cut into chunks that are walked
+ * side by side for every start state, and the chunks' state maps are composed in scan order: the time of a call follows the bytes
+ * in the batch.  The answers are the same.  All of it runs inside this call on `stream`, with no read-back and no wait, so the call
+ * stays asynchronous and legal inside a stream capture (once a first call has allocated the workspace).
+ * Limits: automata whose table lives in LDS, that is up to 127 state sets, both scan directions; larger tables (kept in L2) and
+ * memory automata are matched as before whatever the lengths.  At most 16384 long strings per call are cut, the others are walked
+ * whole.  The chunk size is chosen on the device: max(MFA_DFA_CHUNK (default 4096), round_up(bytes of the long strings / 131072, 16)),
+ * so the maps fit a fixed arena (about 1.1 to 22 MB per overlapping launch, by the number of state sets) whatever the batch holds.
+ * A launch workspace (one per stream in use) whose last four calls met no long string leaves the extra launches out; the first batch
+ * with long strings after that is walked whole, and from then on that workspace keeps the extra launches for good: the hint can cost one
+ * slow batch per workspace, not one per batch, whatever the traffic looks like.  A stream capture records whichever form the call has at
+ * capture time and every replay repeats it: capture after a call that had long strings, or with MFA_DFA_SPLIT=2, which always launches
+ * the split kernels.  MFA_DFA_SPLIT=0 turns the path off (A/B runs).  A batch of 2^31 strings or more is not cut (the queue counts in 32 bits).
+ * mfa_last_dfa_split tells what the last call did. */
 int  mfa_match_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                      uint8_t* d_results, int device, void* stream);
 
@@ -183,8 +199,15 @@ int  mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t
 
 /* Device-side time of the last match kernel launched through this image on
  * `device`, in milliseconds, measured with HIP events recorded on the launch stream
- * around the kernel alone.  Synchronises on the stop event. */
+ * around the kernel alone (for a memory-less image: the table kernel and the plan, chunk and fold kernels of the split path
+ * behind it).  Synchronises on the stop event. */
 int  mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms);
+/* What the split path of the last match call on this image and device did (any pointer may be NULL):
+ * strings it took, chunks it cut them into, the chunk size in bytes the device chose.
+ * All 0 when the path did not run (no long string, a memory automaton, a table in L2, MFA_DFA_SPLIT=0, or a call
+ * that left the split launches out because its workspace had met no long string lately).
+ * Synchronises on that call's last event and reads the figures back with a blocking copy, holding the image's lock: for tests and tools. */
+int  mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes);
 /* Device-side time of the region pass of that launch (0 if it ran none). */
 int  mfa_last_region_ms(mfa_image_t* img, int device, float* ms);
 

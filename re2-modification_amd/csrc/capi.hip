@@ -13,17 +13,13 @@ namespace mfa {
 static thread_local int g_last_hip_error = 0;
 void set_last_hip_error(int e) { g_last_hip_error = e; }
 
-#define HIP_TRY(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) { set_last_hip_error((int)e_); return MFA_ERR_HIP; } \
-    } while (0)
-
 static void ctx_free(LaunchCtx& cx) {
     if (cx.d_counter) (void)hipFree(cx.d_counter);
     lean_hint_free(cx.lean);
     if (cx.d_scratch) (void)hipFree(cx.d_scratch);
     if (cx.d_regions) (void)hipFree(cx.d_regions);
+    if (cx.d_split) (void)hipFree(cx.d_split);
+    if (cx.split_seen) (void)hipHostFree(cx.split_seen);
     for (void* ev : {cx.ev_start, cx.ev_stop, cx.ev_r0, cx.ev_r1, cx.ev_done})
         if (ev) (void)hipEventDestroy((hipEvent_t)ev);
     cx = LaunchCtx{};
@@ -74,7 +70,7 @@ int ctx_acquire(DeviceState& ds, void* stream, LaunchCtx** out) {
         ds.ctxs.push_back(cx);
         pick = cx;
     }
-    pick->used = true; pick->stream = stream; pick->ran_regions = false;
+    pick->used = true; pick->stream = stream; pick->ran_regions = false; pick->split_ran = false;
     ds.last = pick;
     *out = pick;
     return MFA_OK;
@@ -352,6 +348,24 @@ int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {
     HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_stop));
     HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)cx.ev_start, (hipEvent_t)cx.ev_stop));
     jit_print_stats(cx, "last kernel");
+    return MFA_OK;
+}
+
+int mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes) {
+    if (!img) return MFA_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(img->mu);
+    auto it = img->dev.find(device);
+    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
+    LaunchCtx& cx = *it->second.last;
+    uint32_t h[SPLIT_H_WORDS] = {0};
+    if (cx.split_ran) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_done));
+        HIP_TRY(hipMemcpy(h, cx.d_split, sizeof h, hipMemcpyDeviceToHost));
+    }
+    if (strings) *strings = h[SPLIT_H_STRINGS];
+    if (chunks) *chunks = h[SPLIT_H_CHUNKS];
+    if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
     return MFA_OK;
 }
 

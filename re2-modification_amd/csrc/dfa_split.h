@@ -1,0 +1,53 @@
+// What the one-string-per-lane kernels (kernels.hip) and the split path (dfa_split.hip) share on the device: the plan header, the
+// queue of long strings, and the one place where a string is handed from the former to the latter.
+#ifndef MFA_DFA_SPLIT_H
+#define MFA_DFA_SPLIT_H
+
+#include "dfa_split_core.h"
+
+namespace mfa {
+
+// plan header, 32-bit words of device memory, zeroed in front of every launch that uses it
+enum : uint32_t {
+    SPLIT_H_SEEN = 0,        // strings with len >= split_min that asked for a queue slot (the main kernel counts them)
+    SPLIT_H_STRINGS = 1,     // strings queued = min(seen, queue capacity)           (the plan kernel writes this and the following)
+    SPLIT_H_CHUNKS = 2,      // chunks they are cut into
+    SPLIT_H_CHUNK = 3,       // chunk size in bytes
+    SPLIT_H_WORDS = 8,
+};
+
+struct SplitEntry {
+    uint64_t sid;            // string number
+    uint32_t first, nc;      // its first map in the arena, its chunk count; maps are stored in scan order
+    uint32_t dead_at, pad;   // lowest scan index of a chunk whose map is all 0 (0xffffffff: none known): later chunks need no walk
+};
+
+// argument of the main kernels.  split_min == 0: the split path is off, the kernel behaves as it always has.
+struct SplitArgs {
+    uint64_t    split_min;
+    uint32_t*   hdr;         // NULL: no split kernels follow this launch -- every string is walked here, a long one is reported to *seen
+    SplitEntry* queue;
+    uint32_t    qcap;
+    uint32_t*   seen;        // pinned host word (may be NULL): a launch with the split kernels behind it writes 1 (met no long string) or 2, one without writes 3 when it meets one
+};
+
+// A lane of a main kernel that holds a string with len >= split_min calls this.  true: the string is on the queue, the lane treats it
+// as empty and leaves its result byte alone (dfa_fold_kernel writes it, later on the same stream).  false: the lane walks it.
+// NO STRING IS LOST: the lane that skips a string is the lane that was given the queue slot for it, in this very call -- there is no
+// second place that decides what "long" means.  A full queue, or a launch without split kernels behind it, answers false.
+#ifdef __HIPCC__
+__device__ __forceinline__ bool split_take(const SplitArgs& sp, uint64_t sid) {
+    if (sp.hdr == nullptr) {
+        if (sp.seen != nullptr) *sp.seen = 3u;
+        return false;
+    }
+    const uint32_t slot = atomicAdd(&sp.hdr[SPLIT_H_SEEN], 1u);
+    if (slot >= sp.qcap) return false;
+    sp.queue[slot].sid = sid;
+    return true;
+}
+#endif
+
+}  // namespace mfa
+
+#endif

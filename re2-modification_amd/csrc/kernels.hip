@@ -14,26 +14,21 @@
 
 namespace mfa {
 
-#define HIP_TRY(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) { set_last_hip_error((int)e_); return MFA_ERR_HIP; } \
-    } while (0)
-
 // ---- table walk for memory-less automata -------------------------------------------------------
 // One string per lane.  LDS holds one fused table: next[state][byte] (16-bit entries, the state
 // pre-multiplied by the row stride), so a step is: extract byte, OR it into the state word, one
 // ds_read_u16.  Rows are padded by one dword so that equal bytes in different states fall into
 // different banks.  State 0 is the empty set: absorbing and rejecting, the reference's early
 // `break` (automata.cpp:186-188,196-198).  Input is read 16 bytes per lane per load.
-static constexpr uint32_t kDfaRow = 258;     // 16-bit entries per state row (256 + 2 pad)
+// (kDfaRow, the row stride: 16-bit entries per state row, 256 + 2 pad -- dfa_split_core.h)
+// sp: strings of sp.split_min bytes and more go to the split path (dfa_split.h: split_take); sp.split_min == 0: none does.
 
 template <bool REV>
 __global__ void __launch_bounds__(256)
 dfa_walk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__ accept_tab,
                 const uint8_t* __restrict__ byte_class, uint32_t n_states, uint32_t n_classes,
                 const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-                uint8_t* __restrict__ results) {
+                uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     uint16_t* s_next = reinterpret_cast<uint16_t*>(lds);             // [n_states][kDfaRow], entry = next_state * kDfaRow
     for (uint32_t k = threadIdx.x; k < n_states * 256u; k += blockDim.x) {
@@ -44,6 +39,7 @@ dfa_walk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__ 
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
         const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        if (sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // queued: dfa_fold_kernel writes results[sid]
         uint32_t st = kDfaRow;                                        // state 1 = {start}
         if (!REV) {
             uint64_t p = b;
@@ -117,7 +113,7 @@ __global__ void __launch_bounds__(256)
 dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t* __restrict__ accept_tab,
                  const uint8_t* __restrict__ byte_class, uint32_t n_states, uint32_t n_classes,
                  const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-                 uint8_t* __restrict__ results) {
+                 uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint8_t* tile = reinterpret_cast<uint8_t*>(lds) + wave * (64u * kTileRow);
@@ -139,7 +135,11 @@ dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t
     for (uint64_t w0 = ((uint64_t)blockIdx.x * 4u + wave) * 64u; w0 < n; w0 += n_waves * 64u) {
         const uint64_t sid = w0 + lane;
         const bool have = sid < n;
-        const uint64_t b = have ? offsets[sid] : 0, e = have ? offsets[sid + 1] : 0;
+        const uint64_t b = have ? offsets[sid] : 0;
+        uint64_t e = have ? offsets[sid + 1] : 0;
+        bool taken = false;                       // queued for the split path: empty here, and its result byte is dfa_fold_kernel's
+        if (sp.split_min != 0u && e - b >= sp.split_min) taken = split_take(sp, sid);
+        if (taken) e = b;
         uint64_t p = REV ? e : b;                 // forward: next byte to consume; reverse: one past it
         uint32_t st = PACKED ? 1u : kDfaRow;      // state 1 = {start}
         bool active = have && (REV ? p > b : p < e);
@@ -217,7 +217,7 @@ dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t
             line = (REV ? p - 1u : p) & ~(uint64_t)(kLine - 1u);
         }
         }
-        if (have) results[sid] = PACKED ? (uint8_t)((pk.accept_mask >> st) & 1u) : accept_tab[st / kDfaRow];
+        if (have && !taken) results[sid] = PACKED ? (uint8_t)((pk.accept_mask >> st) & 1u) : accept_tab[st / kDfaRow];
     }
 }
 
@@ -274,6 +274,9 @@ static bool make_packed(const HostImage& img, DfaPacked& pk) {
 template <bool REV, bool PACKED, int NLIT>
 static int launch_dfa_tiled(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const DfaPacked& pk, const uint8_t* d_bytes,
                             const uint64_t* d_offsets, uint64_t n, uint8_t* d_results, hipStream_t s) {
+    SplitLaunch sl;
+    int rc = split_begin(img, cx, n, s, &sl);
+    if (rc != MFA_OK) return rc;
     size_t lds = 4 * 64 * kTileRow + (PACKED ? 0 : (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t));
     uint64_t per_cu = (160u * 1024u) / lds;                 // resident blocks a CU's LDS allows (at most 8: 32 waves)
     if (per_cu > 8) per_cu = 8;
@@ -285,8 +288,10 @@ static int launch_dfa_tiled(const HostImage& img, DeviceState& ds, LaunchCtx& cx
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, pk, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
-                       img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results);
+                       img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
     HIP_TRY(hipGetLastError());
+    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
+    if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }
@@ -347,17 +352,22 @@ int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const 
     uint64_t cap = (uint64_t)ds.n_cus * 8;
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
+    SplitLaunch sl;
+    int rc = split_begin(img, cx, n, s, &sl);
+    if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
     if (img.h.is_reversed) {
         HIP_TRY(hipFuncSetAttribute((const void*)dfa_walk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(dfa_walk_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,
-                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results);
+                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
     } else {
         HIP_TRY(hipFuncSetAttribute((const void*)dfa_walk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(dfa_walk_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,
-                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results);
+                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
     }
     HIP_TRY(hipGetLastError());
+    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
+    if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }

@@ -12,6 +12,13 @@
 
 #include "../../include/mfa_hip.h"
 #include "walk_tables.h"
+#include "dfa_split.h"
+
+#define HIP_TRY(expr)                                                   \
+    do {                                                                \
+        hipError_t e_ = (expr);                                         \
+        if (e_ != hipSuccess) { set_last_hip_error((int)e_); return MFA_ERR_HIP; } \
+    } while (0)
 
 namespace mfa {
 
@@ -68,6 +75,13 @@ struct LaunchCtx {
     void*               stream = nullptr;      // stream of the launch it was last used for
     bool                used = false;
     bool                ran_regions = false;
+    // split path for long strings of memory-less automata (dfa_split.hip): plan header, queue and map arena of this launch
+    uint8_t*            d_split = nullptr;
+    size_t              split_bytes = 0;
+    uint32_t*           split_seen = nullptr;  // pinned, device-visible; dfa_split.hip: split_begin has the values
+    uint32_t            split_quiet = 0;       // calls in a row that found "no long string" there
+    bool                split_keep = false;    // a launch without the split kernels met a long string once: this workspace keeps them
+    bool                split_ran = false;     // this launch has the split kernels behind its main kernel
 };
 
 struct DeviceState {
@@ -108,6 +122,16 @@ namespace mfa {
 // launchers (kernels.hip); all asynchronous on `stream`
 int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
                     uint64_t n, uint8_t* d_results, void* stream);
+// dfa_split.hip: split_begin in front of the main kernel (its `args` go to that kernel), split_tail behind it
+struct SplitLaunch {
+    SplitArgs args{};
+    uint8_t*  maps = nullptr;
+    uint32_t  lanes_log2 = 0, chunk_min = 0, arena_chunks = 0, map_cap = 0;
+};
+bool split_applies(const HostImage& img);
+int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                uint8_t* d_results, void* stream);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

@@ -44,12 +44,6 @@
 
 namespace mfa {
 
-#define HIP_TRY(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) { set_last_hip_error((int)e_); return MFA_ERR_HIP; } \
-    } while (0)
-
 static constexpr int kCleanMin = 4;          // clean 16-byte blocks between two dirty ones that make a candidate
 static constexpr uint32_t kMaxLen = 0x00ffffffu;
 

@@ -15,12 +15,6 @@
 
 namespace mfa {
 
-#define HIP_TRY(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) { set_last_hip_error((int)e_); return MFA_ERR_HIP; } \
-    } while (0)
-
 static int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e && *e ? atoi(e) : dflt;

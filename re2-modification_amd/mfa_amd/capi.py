@@ -18,7 +18,7 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_match_batch_regions", "mfa_region_scan", "mfa_match_batch_host", "mfa_last_kernel_ms", "mfa_last_region_ms",
            "mfa_device_count", "mfa_last_hip_error", "mfa_strerror", "mfa_version",
            "mfa_mixed_create", "mfa_mixed_destroy", "mfa_match_mixed", "mfa_match_mixed_sized", "mfa_match_mixed_host", "mfa_mixed_last_ms", "mfa_mixed_timing",
-           "mfa_mixed_last_launches", "mfa_pack_result_bitmap"]
+           "mfa_mixed_last_launches", "mfa_pack_result_bitmap", "mfa_last_dfa_split"]
 
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
 
@@ -68,6 +68,8 @@ def lib():
         L.mfa_last_region_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
         L.mfa_match_batch_host.argtypes = [vp, vp, vp, u64, vp, i32]
         L.mfa_last_kernel_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(L, "mfa_last_dfa_split"):              # (a library of an older build given by MFA_LIB_PATH for an A/B run lacks it)
+            L.mfa_last_dfa_split.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32)]
         L.mfa_mixed_create.argtypes = [ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp)]
         L.mfa_mixed_destroy.argtypes = [vp]
         L.mfa_mixed_destroy.restype = None
@@ -164,6 +166,12 @@ class Image:
         ms = ctypes.c_float()
         _check(lib().mfa_last_kernel_ms(self._h, device, ctypes.byref(ms)), "mfa_last_kernel_ms")
         return ms.value
+
+    def last_dfa_split(self, device=0):
+        """(strings, chunks, chunk_bytes) of the split path for long strings in the last match call; (0, 0, 0) if it did not run"""
+        st, ch, cb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        _check(lib().mfa_last_dfa_split(self._h, device, ctypes.byref(st), ctypes.byref(ch), ctypes.byref(cb)), "mfa_last_dfa_split")
+        return st.value, ch.value, cb.value
 
     def close(self):
         if self._h:

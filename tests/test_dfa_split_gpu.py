@@ -1,0 +1,359 @@
+"""Long strings of memory-less automata on the GPU: the split path (csrc/dfa_split.hip) cuts a string of MFA_DFA_SPLIT_MIN bytes or
+more into chunks, walks the chunks side by side for every start state and composes their maps.  Answers against the CPU
+restatement and against the same call with MFA_DFA_SPLIT=0; what the path did through mfa_last_dfa_split."""
+import json
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle_lib
+from mfa_amd import capi, image
+
+pytestmark = pytest.mark.gpu
+
+with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
+    MANIFEST = json.load(f)
+NFA_NAMES = [a["name"] for a in MANIFEST["automata"] if a["name"].startswith("nfa_")]
+MAX_BYTES = 0x00ffffff
+SPLIT_MIN, CHUNK_MIN, ARENA = 65536, 4096, 131072           # the library's defaults (include/mfa_hip.h)
+DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
+
+
+def upload(strings):
+    import torch
+    data, off = oracle_lib.pack(strings)
+    d_bytes = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
+    d_bytes[:len(data)] = torch.from_numpy(data.copy())
+    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda(), off
+
+
+def gpu_match(img, strings):
+    import torch
+    d_bytes, d_off, off = upload(strings)
+    res = torch.full((max(len(strings), 1),), 7, dtype=torch.uint8, device="cuda")
+    img.match_tensors(d_bytes, d_off, res)
+    torch.cuda.synchronize()
+    return res[:len(strings)].cpu().numpy(), off
+
+
+def expected_split(off, split_min, chunk_min, arena=ARENA):
+    """what mfa_last_dfa_split must report for a batch with these offsets (the formulas of the header)"""
+    spans = [(int(b), int(e)) for b, e in zip(off[:-1], off[1:]) if int(e) - int(b) >= split_min]
+    if not spans:
+        return (0, 0, 0)
+    long_bytes = sum(e - b for b, e in spans)
+    chunk = max(chunk_min, (long_bytes // arena + 15) // 16 * 16)
+    return (len(spans), sum((e - (b & ~15) + chunk - 1) // chunk for b, e in spans), chunk)
+
+
+def rnd(alpha, n, rng):
+    return (np.frombuffer(alpha, dtype=np.uint8)[rng.integers(0, len(alpha), size=n)]).tobytes()
+
+
+def accepted_long(name, n, rng):
+    """a string of exactly n bytes (n >= 6000) that the fixture accepts -- all but the four nfa_dot_*, which die on every input tried"""
+    if name.startswith(("nfa_abb", "nfa_third")):
+        return rnd(b"ab", n - 3, rng) + b"abb"
+    if name.startswith("nfa_enum"):
+        return rnd(b"abc", n - 3, rng) + b"abc"
+    if name.startswith("nfa_star1"):
+        return rnd(b"ab", n - 2, rng) + b"ab"
+    if name.startswith("nfa_star2"):
+        return rnd(b"ab", n - 1, rng) + b"a"
+    if name.startswith("nfa_alt3"):
+        tail = 5000 + (n & 1)
+        words = np.array([[97, 98], [98, 97]], dtype=np.uint8)[rng.integers(0, 2, size=(n - 2 - tail) // 2)]
+        return b"ab" + words.tobytes() + b"c" * tail
+    if name.startswith("nfa_star4"):
+        words = [b"ab", b"c", b"cc", b"abab"]
+        idx = rng.integers(0, 4, size=n)
+        cum = np.cumsum(np.array([2, 1, 2, 4])[idx])
+        m = int(np.searchsorted(cum, n - 1, side="right"))
+        body = b"".join(words[i] for i in idx[:m].tolist())
+        return body + b"c" * (n - 1 - len(body)) + b"a"
+    return rnd(b"ab", n, rng)
+
+
+def scan_poke(s, k, is_rev):
+    """s with the k-th byte IN SCAN ORDER replaced by z (k < 0: from the end of the scan)"""
+    i = k if k >= 0 else len(s) + k
+    if is_rev:
+        i = len(s) - 1 - i
+    return s[:i] + b"z" + s[i + 1:]
+
+
+def short_strings(rng, count=300):
+    """the ragged batch of test_gpu_parity.py: test_table_walk_whole_lines"""
+    out = []
+    for k, ln in enumerate(int(x) for x in rng.integers(0, 700, size=count)):
+        t = bytes(rng.choice(list(b"ab" if k % 4 else b"abc."), size=ln).tolist())
+        if k % 3 == 0 and ln >= 3:
+            t = t[:-3] + b"abb"
+        out.append(t)
+    return out
+
+
+def fixture_blob(name, rev=None):
+    d = image.parse_dump(oracle_lib.load_dump(name))
+    if rev is not None:
+        d["reversed"] = rev
+    return image.to_blob(d)
+
+
+def front_end_blob(regex, tmp_path, flag):
+    p = subprocess.run([DIPLOMA, "-dump", flag], input=regex + "\n", capture_output=True, text=True, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr
+    return image.blob_from_dump(p.stdout)
+
+
+def check(got, want, strings, what):
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "%s: %d mismatches, first string %d (len %d) want %d got %d" % (what, bad.size, bad[0], len(strings[bad[0]]), want[bad[0]], got[bad[0]])
+
+
+@pytest.mark.parametrize("name", NFA_NAMES)
+def test_parity_at_real_size(name):
+    """default knobs; four strings of 1 MiB to 16 MiB - 1 (one exactly MFA_MAX_STRING_BYTES), 300 short ones between them, one empty"""
+    blob = fixture_blob(name)
+    rng = np.random.default_rng(len(name) * 104729)
+    strings = short_strings(rng)
+    longs = [accepted_long(name, n, rng) for n in (1 << 20, MAX_BYTES, (1 << 20) + 77777, 2 * (1 << 20) + 5)]
+    longs[2] = scan_poke(longs[2], -1, image.blob_info(blob)["reversed"])
+    for at, s in zip((17, 120, 121, 290), longs):
+        strings.insert(at, s)
+    strings.insert(200, b"")
+    want = oracle_lib.OracleImage(blob).match(strings)
+    img = capi.Image(blob)
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, name)
+    assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN) and img.last_dfa_split()[0] == 4
+    assert img.info()["last_kernel"] == capi.KERNEL_TABLE
+
+
+@pytest.mark.parametrize("chunk", [16, 48, 256])
+@pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
+@pytest.mark.parametrize("name", ["nfa_abb_thompson", "nfa_third_glushkov", "nfa_alt3_plain", "nfa_enum_glushkov"])
+def test_parity_at_every_border(name, rev, chunk, monkeypatch):
+    """MFA_DFA_SPLIT_MIN=256, tiny chunks: 2 000 strings of 0 to 5 000 bytes carved out of one buffer, starting at every alignment"""
+    monkeypatch.setenv("MFA_DFA_SPLIT_MIN", "256")
+    monkeypatch.setenv("MFA_DFA_CHUNK", str(chunk))
+    blob = fixture_blob(name, rev)
+    rng = np.random.default_rng(chunk * 31 + rev)
+    # 2 000 strings of 0 to 5 000 bytes; most of them short, so that the long ones stay under 2 MiB and the device keeps the 16-byte
+    # chunk it is asked for (at 131 072 chunks per batch it enlarges the chunk from 16 * 131 072 bytes on)
+    lens = [int(x) for x in rng.integers(0, 700, size=1600)] + [int(x) for x in rng.integers(0, 5001, size=390)] + [0, 255, 256, 257, 5000, 4999, 16, 4096, 272, 4112]
+    lens = [lens[i] for i in rng.permutation(len(lens))]
+    assert len(lens) == 2000 and sum(ln for ln in lens if ln >= 256) < (2 << 20)
+    buf = accepted_long(name, sum(lens) + 16, rng)
+    strings, at = [], 0
+    for k, ln in enumerate(lens):
+        s = buf[at:at + ln]
+        if k % 3 == 0 and ln >= 3 and name.startswith(("nfa_abb", "nfa_third")):
+            s = (b"bba" + s[3:]) if rev else (s[:-3] + b"abb")
+        strings.append(s)
+        at += ln
+    data, off = oracle_lib.pack(strings)
+    assert {int(o) % 16 for o, ln in zip(off[:-1], lens) if ln >= 256} == set(range(16))
+    want = oracle_lib.OracleImage(blob).match(strings)
+    img = capi.Image(blob)
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, "%s rev %d chunk %d" % (name, rev, chunk))
+    assert img.last_dfa_split() == expected_split(off, 256, chunk) and img.last_dfa_split()[2] == chunk
+    monkeypatch.setenv("MFA_DFA_SPLIT", "0")
+    plain, _ = gpu_match(img, strings)
+    assert img.last_dfa_split() == (0, 0, 0)
+    check(got, plain, strings, "against the same call without the split path")
+
+
+def test_largest_table_in_lds(tmp_path):
+    """127 state sets, the most the path takes: the chunk kernel's table is 65 532 bytes of LDS, 128 lanes per chunk"""
+    ab = "(a|b)"
+    regex = "(a|b)*(a" + ab * 5 + "|b" + ab * 4 + "a)" + "(c|d)" * 7 + "c*"
+    blob = front_end_blob(regex, tmp_path, "-thompson")
+    img = capi.Image(blob)
+    assert img.info()["dfa_states"] == 127
+    rng = np.random.default_rng(127)
+    body = rnd(b"ab", 1 << 20, rng)
+    tail = rnd(b"cd", 7, rng)
+    strings = [body + b"abbbbb" + tail + b"ccc", body + b"babbba" + tail, body + b"bbbbbb" + tail, body + b"abbbbb" + tail + b"d", b"", body[:500] + b"aaaaaa" + tail,
+               body[:70000] + b"aaaaaa" + tail + b"c" * 300000]
+    want = oracle_lib.OracleImage(blob).match(strings)
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, "127 state sets")
+    assert list(want[:4]) == [1, 1, 0, 0]
+    assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN) and img.last_dfa_split()[0] == 5
+
+
+@pytest.mark.parametrize("kernel", ["tiled", "simple"])
+def test_quiet_workspace_hands_long_strings_over(kernel, monkeypatch):
+    """ONE image.  After a few batches without a long string the call leaves the split kernels out; the first long strings it then meets are
+    walked whole by the main kernel (right answers, nothing cut), which tells the workspace, and from the next call on they are cut again --
+    for good: a later quiet spell does not drop the split kernels a second time.  Both main kernels."""
+    if kernel == "simple":
+        monkeypatch.setenv("MFA_DFA_KERNEL", "simple")
+    blob = fixture_blob("nfa_abb_thompson")
+    rng = np.random.default_rng(31)
+    ora = oracle_lib.OracleImage(blob)
+    short = short_strings(rng)
+    longs = short[:40] + [rnd(b"ab", 200000, rng) + b"abb", rnd(b"ab", 65536, rng), b"", rnd(b"ab", 300001, rng) + b"abb", rnd(b"ab", 65534, rng) + b"b"] + short[40:90]      # (65 535 bytes: the longest string that is not cut)
+    want_short, want_long = ora.match(short), ora.match(longs)
+    assert want_long[40] == 1 and want_long[41] == 0 and want_long[43] == 1
+    img = capi.Image(blob)
+    for call in range(8):                                      # quiet after four calls that reported no long string
+        got, _ = gpu_match(img, short)
+        check(got, want_short, short, "short batch, call %d" % call)
+        assert img.last_dfa_split() == (0, 0, 0)
+    got, off = gpu_match(img, longs)
+    check(got, want_long, longs, "long strings in a call without split kernels")
+    assert img.last_dfa_split() == (0, 0, 0)                   # walked whole, this once
+    cut = expected_split(off, SPLIT_MIN, CHUNK_MIN)
+    assert cut[0] == 3
+    for round_ in range(2):
+        got, _ = gpu_match(img, longs)
+        check(got, want_long, longs, "long strings again")
+        assert img.last_dfa_split() == cut
+        for call in range(8):
+            got, _ = gpu_match(img, short)
+            check(got, want_short, short, "short batch after long ones")
+            assert img.last_dfa_split() == (0, 0, 0)
+
+
+def test_more_state_sets_than_a_wave_and_the_limit(tmp_path):
+    """(a|b)*a(a|b)^k: 66 state sets at k = 5 (more than 64: a chunk's start states take two waves) are cut, a table beyond LDS (k = 8) is not"""
+    rng = np.random.default_rng(58)
+    for k, cut in ((5, True), (8, False)):
+        blob = front_end_blob("(a|b)*a" + "(a|b)" * k, tmp_path, "-thompson")
+        img = capi.Image(blob)
+        states = img.info()["dfa_states"]
+        assert (65 <= states <= 127) if cut else states > 127
+        body = rnd(b"ab", 2 << 20, rng)
+        strings = [body[:-(k + 1)] + b"a" + b"b" * k, body[:-(k + 1)] + b"b" + b"a" * k, b"", body[:1000], b"a" + b"b" * k]
+        want = oracle_lib.OracleImage(blob).match(strings)
+        got, off = gpu_match(img, strings)
+        check(got, want, strings, "k = %d" % k)
+        assert list(want[:2]) == [1, 0]
+        assert img.last_dfa_split() == (expected_split(off, SPLIT_MIN, CHUNK_MIN) if cut else (0, 0, 0))
+
+
+@pytest.mark.parametrize("name", NFA_NAMES)
+def test_death_and_survival(name):
+    """a long string that is accepted, one rejected only by the last byte scanned, one that dies in its first chunk: the all-dead
+    shortcut changes no answer.  Every fixture but the four nfa_dot_* (they die within a few bytes on every input) must have the
+    accept / late-reject pair."""
+    blob = fixture_blob(name)
+    is_rev = image.blob_info(blob)["reversed"]
+    rng = np.random.default_rng(len(name) * 15485863)
+    ok = accepted_long(name, (1 << 20) + 4321, rng)
+    strings = [ok, scan_poke(ok, -1, is_rev), scan_poke(ok, 5, is_rev), scan_poke(ok, 70000, is_rev), b"ab"]
+    want = oracle_lib.OracleImage(blob).match(strings)
+    img = capi.Image(blob)
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, name)
+    assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN)
+    if not name.startswith("nfa_dot"):
+        assert list(want[:4]) == [1, 0, 0, 0], "%s has no accept / late-reject pair of long strings" % name
+
+
+def test_one_image_two_streams_back_to_back():
+    """one image, two streams, no synchronisation between the calls; two batches of the same shape and different content alternate
+    for 20 calls, each call checked: a queue or an arena shared between launches would mix them up"""
+    import torch
+    blob = fixture_blob("nfa_abb_thompson")
+    rng = np.random.default_rng(77)
+    lens = [300000, 50, 70001, 0, 1 << 20, 999, 65536, 65535]
+    batches = []
+    for v in range(2):
+        strings = [rnd(b"ab", ln, rng) for ln in lens]
+        strings = [s[:-3] + b"abb" if (k + v) % 2 and len(s) >= 3 else s for k, s in enumerate(strings)]
+        d_bytes, d_off, off = upload(strings)
+        batches.append((d_bytes, d_off, oracle_lib.OracleImage(blob).match(strings), off))
+    assert not np.array_equal(batches[0][2], batches[1][2])
+    img = capi.Image(blob)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    outs = []
+    for call in range(20):
+        d_bytes, d_off, want, off = batches[call % 2]
+        res = torch.full((len(lens),), 7, dtype=torch.uint8, device="cuda")
+        img.match_tensors(d_bytes, d_off, res, stream=streams[(call // 2) % 2])
+        outs.append((res, want))
+    torch.cuda.synchronize()
+    for call, (res, want) in enumerate(outs):
+        assert np.array_equal(res.cpu().numpy(), want), "call %d" % call
+    assert img.last_dfa_split() == expected_split(batches[1][3], SPLIT_MIN, CHUNK_MIN)
+
+
+def test_arena_pressure(monkeypatch):
+    """a small arena (test-only knob MFA_DFA_ARENA) makes the device choose chunk > chunk_min: round_up(long bytes / arena chunks, 16)"""
+    monkeypatch.setenv("MFA_DFA_ARENA", "100")
+    blob = fixture_blob("nfa_third_thompson")
+    rng = np.random.default_rng(9)
+    strings = [rnd(b"ab", n, rng) for n in (1 << 20, 40, 3 << 20, 70000, 0, (1 << 20) + 13)]
+    want = oracle_lib.OracleImage(blob).match(strings)
+    img = capi.Image(blob)
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, "arena of 100 chunks")
+    n_long, chunks, chunk = img.last_dfa_split()
+    long_bytes = (1 << 20) + (3 << 20) + 70000 + (1 << 20) + 13
+    assert chunk == (long_bytes // 100 + 15) // 16 * 16 and chunk > CHUNK_MIN
+    assert (n_long, chunks, chunk) == expected_split(off, SPLIT_MIN, CHUNK_MIN, arena=100)
+    assert 0 < want.sum() < len(strings)
+
+
+def test_through_the_layers(tmp_path):
+    """`./diploma -match` with one 4 MiB token (a large file without blanks is one string), and mfa_match_batch_host on the same string"""
+    auto = next(a for a in MANIFEST["automata"] if a["name"] == "nfa_abb_plain")
+    rng = np.random.default_rng(4)
+    blob = fixture_blob("nfa_abb_plain")
+    for token in (rnd(b"ab", (4 << 20) - 3, rng) + b"abb", rnd(b"ab", (4 << 20) - 3, rng) + b"abz"):
+        want = oracle_lib.OracleImage(blob).match([token])
+        p = subprocess.run([DIPLOMA, "-match"], input=auto["regex"].encode() + b"\n" + token + b"\nexit\n", capture_output=True, cwd=tmp_path)
+        assert p.returncode == 0, p.stderr
+        assert p.stdout == auto["header"].encode() + b"%d\n" % want[0]
+        img = capi.Image(blob)
+        data, off = oracle_lib.pack([token])
+        assert list(img.match_host(data, off)) == list(want)
+        assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN)
+
+
+def test_memory_automata_untouched(monkeypatch):
+    """an ex1_plain batch with a 1 MiB string: the split path does not run, the answer is the one without it"""
+    blob = fixture_blob("ex1_plain")
+    strings = [b"aa", b"a" * (1 << 20), b"a" * (1 << 20) + b"b", b"", b"aaaaaab"]
+    img = capi.Image(blob)
+    got, _ = gpu_match(img, strings)
+    assert img.last_dfa_split() == (0, 0, 0)
+    assert list(got) == [1, 1, 0, 1, 0]          # the restatement's answers (it needs minutes for the long two; computed once)
+    monkeypatch.setenv("MFA_DFA_SPLIT", "0")
+    again, _ = gpu_match(capi.Image(blob), strings)
+    assert np.array_equal(got, again)
+
+
+def test_call_is_capturable():
+    """no read-back and no stream wait: the call is captured into a graph (one stream, no parallel branches) and replayed on a batch
+    with two long strings"""
+    import torch
+    blob = fixture_blob("nfa_abb_glushkov")
+    rng = np.random.default_rng(12)
+    strings = [rnd(b"ab", 500000, rng) + b"abb", b"ab", rnd(b"ab", 900001, rng), b"abb", b""]
+    want = oracle_lib.OracleImage(blob).match(strings)
+    d_bytes, d_off, off = upload(strings)
+    res = torch.full((len(strings),), 7, dtype=torch.uint8, device="cuda")
+    img = capi.Image(blob)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        img.match_tensors(d_bytes, d_off, res)                 # allocates the workspace
+    torch.cuda.synchronize()
+    assert np.array_equal(res.cpu().numpy(), want) and img.last_dfa_split()[0] == 2
+    res.fill_(7)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        img.match_tensors(d_bytes, d_off, res)
+    torch.cuda.synchronize()
+    res.fill_(7)
+    g.replay()
+    torch.cuda.synchronize()
+    assert np.array_equal(res.cpu().numpy(), want)

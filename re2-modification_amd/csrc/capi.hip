@@ -13,6 +13,13 @@ namespace mfa {
 static thread_local int g_last_hip_error = 0;
 void set_last_hip_error(int e) { g_last_hip_error = e; }
 
+int check_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
+    HIP_TRY(hipSetDevice(device));
+    return MFA_OK;
+}
+
 static void ctx_free(LaunchCtx& cx) {
     if (cx.d_counter) (void)hipFree(cx.d_counter);
     lean_hint_free(cx.lean);
@@ -93,11 +100,10 @@ void device_release(DeviceState& ds) {
 
 // caller holds img->mu
 int device_prepare(mfa_image* img, int device, DeviceState** out) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
+    int rc = check_device(device);
+    if (rc != MFA_OK) return rc;
     auto it = img->dev.find(device);
     if (it != img->dev.end()) { *out = &it->second; return MFA_OK; }
-    HIP_TRY(hipSetDevice(device));
     DeviceState ds;
     ds.device = device;
     hipDeviceProp_t prop;
@@ -109,7 +115,6 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
         if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
         return MFA_OK;
     };
-    int rc = MFA_OK;
     if (h.h.kind == MFA_KIND_MFA) {
         if (img->walk_ok) rc = up((void**)&ds.d_walk, img->walk.words.data(), img->walk.words.size() * 4);
     } else {
@@ -124,6 +129,40 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
     auto ins = img->dev.emplace(device, ds);
     *out = &ins.first->second;
     return MFA_OK;
+}
+
+// A batch given with HOST pointers: checks it, copies it to the device (offsets relative to the first string), runs `match` on the copies,
+// copies the results back and synchronises (throughput is then bounded by the host link).
+int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device,
+                      const std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes)>& match) {
+    if (!offsets || (!results && n)) return MFA_ERR_INVALID_ARG;
+    if (n == 0) return MFA_OK;
+    for (uint64_t k = 0; k < n; k++) {
+        if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
+        if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) return MFA_ERR_TOO_LONG;
+    }
+    int rc = check_device(device);
+    if (rc != MFA_OK) return rc;
+    const uint64_t total = offsets[n] - offsets[0];
+    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint8_t* d_res = nullptr;
+    std::vector<uint64_t> rel(n + 1);
+    for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
+    hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_res, n);
+    if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+    if (rc == MFA_OK) rc = match(d_bytes, d_off, d_res, total);
+    if (rc == MFA_OK) {
+        e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+    }
+    if (d_bytes) (void)hipFree(d_bytes);
+    if (d_off) (void)hipFree(d_off);
+    if (d_res) (void)hipFree(d_res);
+    return rc;
 }
 
 }  // namespace mfa
@@ -185,12 +224,6 @@ int mfa_image_specialize(mfa_image_t* img) {
     return MFA_OK;
 }
 
-static bool regions_enabled() {
-    const char* e = getenv("MFA_REGIONS");                      // MFA_REGIONS=0: no region pass and no table: every step is executed (A/B runs)
-    const char* a = getenv("MFA_ACCEL");
-    return !(e && e[0] == '0') && !(a && a[0] == '0');
-}
-
 // own_regions: run the region pass into the context's table; else use d_table (may be NULL)
 static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint8_t* d_results,
                       const uint64_t* d_table, bool own_regions, int device, void* stream) {
@@ -200,7 +233,6 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
     DeviceState* ds = nullptr;
     int rc = device_prepare(img, device, &ds);
     if (rc != MFA_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
     const bool is_mfa = img->host.h.kind == MFA_KIND_MFA;
     // Which walk: the table-driven kernel (walk.hip) works for every automaton at once; a kernel generated for this automaton
     // (jit_gen.cpp) steps faster on small automata but has to be compiled first.  Automatic: the generated kernel if its code object
@@ -232,18 +264,18 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
         LaunchCtx* cx; void* stream;
         ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
     } done_guard{cx, stream};
+    img->last_kernel = table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : MFA_KERNEL_TABLE;
+    if (is_mfa && own_regions && regions_enabled()) {
+        rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
+        if (rc != MFA_OK) return rc;
+        HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r0, (hipStream_t)stream));
+        rc = launch_region_scan(ds->n_cus, d_bytes, d_offsets, n, cx->d_regions, stream);
+        if (rc != MFA_OK) return rc;
+        HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r1, (hipStream_t)stream));
+        cx->ran_regions = true;
+        d_table = cx->d_regions;
+    }
     if (table_walk) {
-        img->last_kernel = MFA_KERNEL_WALK;
-        if (own_regions && regions_enabled()) {
-            rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
-            if (rc != MFA_OK) return rc;
-            HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r0, (hipStream_t)stream));
-            rc = launch_region_scan(ds->n_cus, d_bytes, d_offsets, n, cx->d_regions, stream);
-            if (rc != MFA_OK) return rc;
-            HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r1, (hipStream_t)stream));
-            cx->ran_regions = true;
-            d_table = cx->d_regions;
-        }
         const WalkPlanInput p{img->walk.K, img->walk.max_live, img->walk.reversed, (uint32_t)img->walk.words.size()};
         const uint32_t sf[2] = {0u, (uint32_t)n}, stb[1] = {0u};
         if (n > 0xffffffffull) return MFA_ERR_INVALID_ARG;
@@ -252,20 +284,8 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
                          cx->d_counter, stream, &cx->lean);
         HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_stop, (hipStream_t)stream));
     } else if (jit) {
-        img->last_kernel = MFA_KERNEL_SPECIALISED;
-        if (own_regions && regions_enabled()) {
-            rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
-            if (rc != MFA_OK) return rc;
-            HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r0, (hipStream_t)stream));
-            rc = launch_region_scan(ds->n_cus, d_bytes, d_offsets, n, cx->d_regions, stream);
-            if (rc != MFA_OK) return rc;
-            HIP_TRY(hipEventRecord((hipEvent_t)cx->ev_r1, (hipStream_t)stream));
-            cx->ran_regions = true;
-            d_table = cx->d_regions;
-        }
         rc = launch_mfa_jit(*ds, *cx, d_bytes, d_offsets, n, d_results, d_table, stream);
     } else {
-        img->last_kernel = MFA_KERNEL_TABLE;
         rc = launch_dfa_walk(img->host, *ds, *cx, d_bytes, d_offsets, n, d_results, stream);
     }
     return rc;
@@ -284,9 +304,8 @@ int mfa_match_batch_regions(mfa_image_t* img, const uint8_t* d_bytes, const uint
 int mfa_region_scan(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, int device, void* stream) {
     if (!d_offsets || (!d_table && n)) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
-    HIP_TRY(hipSetDevice(device));
+    const int rc = check_device(device);
+    if (rc != MFA_OK) return rc;
     static int cus[64] = {0};
     if (device < 64 && cus[device] == 0) {
         hipDeviceProp_t prop;
@@ -298,45 +317,9 @@ int mfa_region_scan(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t 
 
 int mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results,
                          int device) {
-    if (!img || !offsets || (!results && n)) return MFA_ERR_INVALID_ARG;
-    if (n == 0) return MFA_OK;
-    for (uint64_t k = 0; k < n; k++) {
-        if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
-        if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) return MFA_ERR_TOO_LONG;
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
-    HIP_TRY(hipSetDevice(device));
-    const uint64_t total = offsets[n] - offsets[0];
-    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint8_t* d_res = nullptr;
-    int rc = MFA_OK;
-    hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_res, n);
-    if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if (offsets[0] == 0) e = hipMemcpy(d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-        else {
-            uint64_t* tmp = new (std::nothrow) uint64_t[n + 1];
-            if (!tmp) rc = MFA_ERR_NOMEM;
-            else {
-                for (uint64_t k = 0; k <= n; k++) tmp[k] = offsets[k] - offsets[0];
-                e = hipMemcpy(d_off, tmp, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-                delete[] tmp;
-            }
-        }
-    }
-    if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    if (rc == MFA_OK) rc = mfa_match_batch(img, d_bytes, d_off, n, d_res, device, nullptr);
-    if (rc == MFA_OK) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    }
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_off) (void)hipFree(d_off);
-    if (d_res) (void)hipFree(d_res);
-    return rc;
+    if (!img) return MFA_ERR_INVALID_ARG;
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t) {
+        return mfa_match_batch(img, d_bytes, d_off, n, d_res, device, nullptr); });
 }
 
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {

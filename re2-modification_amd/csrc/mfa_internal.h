@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -13,6 +14,7 @@
 #include "../../include/mfa_hip.h"
 #include "walk_tables.h"
 #include "dfa_split.h"
+#include "walk_plan.h"      // LeanHint, WalkPlanInput, env_int, regions_enabled
 
 #define HIP_TRY(expr)                                                   \
     do {                                                                \
@@ -50,14 +52,6 @@ int tabulate_nfa(HostImage& img);                                    // fills th
 // pool of its (image, device); a context is reused by a later launch on the SAME stream (stream order makes
 // that safe) or once its `done` event has completed, so launches of one image that overlap on different
 // streams or from different host threads never share a counter, a scratch buffer or an event.
-// Whether the lean kernel behind a table walk (walk.hip: strings without periodic stretches) has had anything to do lately: the kernel
-// reports the length of its queue (+ 1) to a word of pinned host memory, and a launch whose slot last saw an empty queue leaves the lean
-// kernel and the queue out (an empty launch beside a region pass costs the stream 0.1-0.35 ms: its workgroups queue for room) -- except
-// every 32nd time, with a quarter of the grid, to notice when the input changes.
-struct LeanHint {
-    uint32_t* h_seen = nullptr;      // pinned, device-visible; 0 = nothing reported yet
-    uint32_t quiet = 0, launches = 0;
-};
 void lean_hint_free(LeanHint& h);
 
 struct LaunchCtx {
@@ -152,12 +146,13 @@ int         launch_mfa_jit(DeviceState& ds, LaunchCtx& cx, const uint8_t* d_byte
                            const uint64_t* d_regions, void* stream);
 void device_release(DeviceState& ds);
 // live-list walk (walk_launch.hip).  seg_first: n_seg + 1 string indices relative to the sub-batch; seg_table: word offsets into d_tables
-struct WalkPlanInput { uint32_t K, max_live; bool reversed; uint32_t table_words; };
 int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                 uint8_t* d_results, const uint64_t* d_regions, uint32_t n_seg, const uint32_t* seg_first, const uint32_t* seg_table,
                 uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, LeanHint* lean = nullptr, void* wait_event = nullptr);
-int  walk_mode();          // MFA_WALK: 0 auto (default), 1 table, 2 jit
 void set_last_hip_error(int e);
+int  match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device,      // capi.hip
+                       const std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes)>& match);
+int  check_device(int device);      // MFA_ERR_NO_DEVICE unless `device` exists; makes it the current one
 
 }  // namespace mfa
 

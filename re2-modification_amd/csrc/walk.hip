@@ -43,7 +43,7 @@ struct TicketFeeder {
     }
 };
 
-// LDS of a workgroup: [tables] then per wave [lv][ld][sb][sa][rt_cache]
+// LDS of a workgroup: [tables] then per wave a block laid out by walk.h's WalkLayout
 // TG: the tables stay in global memory (automata whose tables do not fit LDS beside the lists)
 template <int K, bool REV, bool STATS, bool TG, int NKEYS>
 __global__ void __launch_bounds__(256, WALK_MIN_WAVES)
@@ -54,28 +54,18 @@ walk_kernel(WalkArgs a) {
         for (uint32_t k = threadIdx.x; k < a.table_words; k += blockDim.x) smem[k] = a.tables[k];
         __syncthreads();
     }
-    constexpr uint32_t W = Lay<K>::W, DW = Lay<K>::DW;
-    const uint32_t CI = a.images_global ? 0u : a.C, XI = a.CX + a.C - CI;      // image entries in LDS / in global memory
-    const uint32_t nm_words = WALK_NODE_MAP ? a.nm_words : 0u;      // the lanes' node maps (long-list kernel)
-    const uint32_t per_wave = a.C * 64u * (2u * W + 2u * DW) + CI * 64u * (W + DW) + 2u * 64u * MFA_RT_CACHED + nm_words * 64u;
+    const WalkLayout lay{(uint32_t)K, a.C, a.CX, a.images_global != 0u, false, WALK_NODE_MAP ? a.nm_words : 0u};      // (nm: the lanes' node maps, long-list kernel)
     // the wave's number as a scalar: everything derived from it stays in scalar registers
     const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
-    WALK_LDS uint32_t* base = (WALK_LDS uint32_t*)smem + a.shared_words + wave_u * per_wave;
+    WALK_LDS uint32_t* const base = (WALK_LDS uint32_t*)smem + a.shared_words + wave_u * lay.lds_words();
     Store st;
-    st.C = a.C; st.CX = a.CX; st.CI = CI;
-    st.lv = base; base += 2u * a.C * W * 64u;
-    st.ld = base; base += 2u * a.C * DW * 64u;
-    st.sb = base; base += CI * W * 64u;
-    st.sa = base; base += CI * DW * 64u;
-    WALK_LDS uint64_t* const rtc = (WALK_LDS uint64_t*)base; base += 2u * 64u * MFA_RT_CACHED;
-    st.nm = (WALK_LDS uint8_t*)base; st.nm_words = nm_words;
+    st.C = a.C; st.CX = a.CX; st.CI = lay.CI();
+    st.lv = base + lay.lv(); st.ld = base + lay.ld(); st.sb = base + lay.sb(); st.sa = base + lay.sa();
+    WALK_LDS uint64_t* const rtc = (WALK_LDS uint64_t*)(base + lay.rtc());
+    st.nm = (WALK_LDS uint8_t*)(base + lay.nm()); st.nm_words = lay.nm_words;
     const uint64_t gwave = (uint64_t)blockIdx.x * 4u + wave_u;
-    uint32_t* g = a.spill + gwave * ((uint64_t)a.CX * 64u * (2u * W + 2u * DW) + (uint64_t)XI * 64u * (W + DW) + CMP_CACHE * 4u * 64u);
-    st.gv = g; g += 2u * a.CX * W * 64u;
-    st.gd = g; g += 2u * a.CX * DW * 64u;
-    st.gsb = g; g += XI * W * 64u;
-    st.gsa = g; g += XI * DW * 64u;
-    st.gq = g;
+    uint32_t* const g = a.spill + gwave * lay.spill_words();
+    st.gv = g + lay.gv(); st.gd = g + lay.gd(); st.gsb = g + lay.gsb(); st.gsa = g + lay.gsa(); st.gq = g + lay.gq();
     Batch b{a.bytes, a.offsets, a.n, a.results, a.regions, a.accel, a.refill, a.n_seg, a.seg_first, a.seg_table, 0u,
             a.lean_queue, reinterpret_cast<uint32_t*>(a.counter + 1)};
     TicketFeeder feed{a.counter, a.n, gwave * 64u};
@@ -128,19 +118,19 @@ walk_lean_kernel(WalkArgs a) {
         for (uint32_t k = threadIdx.x; k < a.table_words; k += blockDim.x) smem[k] = a.tables[k];
         __syncthreads();
     }
-    constexpr uint32_t W = Lay<K>::W;
+    const WalkLayout lay{(uint32_t)K, a.C, a.CX, false, true, WALK_NODE_MAP ? a.nm_words : 0u};
     const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    WALK_LDS uint32_t* const base = (WALK_LDS uint32_t*)smem + a.shared_words + wave_u * lay.lds_words();
     Store st;
     st.C = a.C; st.CX = a.CX; st.CI = 0u;
-    const uint32_t nm_words = WALK_NODE_MAP ? a.nm_words : 0u;
-    st.lv = (WALK_LDS uint32_t*)smem + a.shared_words + wave_u * (2u * a.C * W * 64u + nm_words * 64u);
-    st.nm = (WALK_LDS uint8_t*)(st.lv + 2u * a.C * W * 64u); st.nm_words = nm_words;
+    st.lv = base + lay.lv();
+    st.nm = (WALK_LDS uint8_t*)(base + lay.nm()); st.nm_words = lay.nm_words;
     st.ld = nullptr; st.sb = nullptr; st.sa = nullptr;
     const uint64_t gwave = (uint64_t)blockIdx.x * 4u + wave_u;
-    uint32_t* g = a.spill + gwave * ((uint64_t)a.CX * 64u * 2u * W + CMP_CACHE * 4u * 64u);
-    st.gv = g; g += 2u * a.CX * W * 64u;
+    uint32_t* const g = a.spill + gwave * lay.spill_words();
+    st.gv = g + lay.gv();
     st.gd = nullptr; st.gsb = nullptr; st.gsa = nullptr;
-    st.gq = g;
+    st.gq = g + lay.gq();
     Batch b{a.bytes, a.offsets, a.n, a.results, nullptr, 0u, a.refill, a.n_seg, a.seg_first, a.seg_table, 0u, nullptr, nullptr};
     QueueFeeder feed{a.lean_queue, count, a.counter + 2};
     if (TG) walk_wave_lean<K, REV, QueueFeeder, TablePtrG>(b, a.tables, st, feed);
@@ -150,11 +140,6 @@ walk_lean_kernel(WalkArgs a) {
 #define WALK_CAT2(a, b) a##b
 #define WALK_CAT(a, b) WALK_CAT2(a, b)
 
-// words of LDS one wave needs at capacity C
-static size_t wave_words(uint32_t C, bool images_global, uint32_t nm_words = 0) {
-    return (size_t)C * 64u * ((images_global ? 2u : 3u) * (Lay<WALK_K>::W + Lay<WALK_K>::DW)) + 2u * 64u * MFA_RT_CACHED + (WALK_NODE_MAP ? (size_t)nm_words * 64u : 0u);
-}
-
 #if WALK_STATS
 int launch_walk_stats(const WalkLaunch& L, void* stream) {
 #elif defined(WALK_LONG_LISTS)
@@ -162,10 +147,9 @@ int WALK_CAT(launch_walk_long_k, WALK_K)(const WalkLaunch& L, void* stream) {
 #else
 int WALK_CAT(launch_walk_k, WALK_K)(const WalkLaunch& L, void* stream) {
 #endif
-    WalkArgs a = L.args;
+    const WalkArgs& a = L.args;
     hipStream_t s = (hipStream_t)stream;
-    const size_t lds = ((size_t)a.shared_words + 4u * wave_words(a.C, a.images_global != 0u, a.nm_words)) * 4u;
-    if (lds > 160u * 1024u) return MFA_ERR_UNSUPPORTED;
+    const size_t lds = L.lds_bytes;
     hipError_t e = hipSuccess;
 #define WALK_GO(REVV, TGV)                                                                                                                   \
     do {                                                                                                                                     \
@@ -180,9 +164,8 @@ int WALK_CAT(launch_walk_k, WALK_K)(const WalkLaunch& L, void* stream) {
     if (e == hipSuccess && L.lean_grid != 0u && a.lean_queue != nullptr) {
         // behind it, on the same stream: the strings it has handed on (the kernel ends at once when there are none)
         WalkArgs al = a;
-        al.C = L.lean_C;
-        al.CX = a.CX + a.C > al.C ? a.CX + a.C - al.C : 1u;
-        const size_t lds_l = ((size_t)a.shared_words + 4u * ((size_t)al.C * 64u * 2u * Lay<WALK_K>::W + (WALK_NODE_MAP ? (size_t)a.nm_words * 64u : 0u))) * 4u;
+        al.C = L.lean_C; al.CX = L.lean_CX;
+        const size_t lds_l = L.lean_lds_bytes;
 #define WALK_GO_LEAN(REVV, TGV)                                                                                                              \
     do {                                                                                                                                     \
         e = hipFuncSetAttribute((const void*)walk_lean_kernel<WALK_K, REVV, TGV, WALK_KEYS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l); \
@@ -197,9 +180,5 @@ int WALK_CAT(launch_walk_k, WALK_K)(const WalkLaunch& L, void* stream) {
     if (e != hipSuccess) { set_last_hip_error((int)e); return MFA_ERR_HIP; }
     return MFA_OK;
 }
-
-#if !WALK_STATS && !defined(WALK_LONG_LISTS)
-size_t WALK_CAT(walk_wave_words_k, WALK_K)(uint32_t C, bool images_global) { return wave_words(C, images_global); }
-#endif
 
 }  // namespace mfa

@@ -37,6 +37,7 @@
 #define MFA_SCAN_DEPTH 1
 #define MFA_RUN_DEPTH 1
 #include "device_common.h"
+#include "walk.h"
 
 #ifndef WALK_WV
 #define WALK_WV 64u          /* lanes per wave = stride of the per-lane arrays */
@@ -343,10 +344,10 @@ template <class TP> WALK_DEV void aut_load(Aut& a, TP T, uint32_t at) {
 template <class TP> WALK_DEV uint32_t aut_start(TP T, const Aut& a) { return T[a.at + 4]; }
 
 // ---- list storage -----------------------------------------------------------------------------------------------------------------
-constexpr uint32_t CMP_CACHE = 4;      // answered comparisons a lane can hold for one step (beyond them it compares by itself)
+using mfa::CMP_CACHE;                  // (walk.h, with the layout of a wave's memory)
 template <int K> struct Lay {
-    static constexpr uint32_t W = 2 + 2 * K;            // value words per entry
-    static constexpr uint32_t DW = (1 + 2 * K + 1) / 2;  // direction words per entry: int16 each (pos, then S, L per cell)
+    static constexpr uint32_t W = mfa::walk_W(K);        // value words per entry
+    static constexpr uint32_t DW = mfa::walk_DW(K);      // direction words per entry
     static constexpr uint32_t EEW = K <= 6 ? 2 : 3;      // words per effective edge
 };
 

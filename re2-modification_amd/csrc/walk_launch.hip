@@ -15,152 +15,48 @@
 
 namespace mfa {
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e && *e ? atoi(e) : dflt;
-}
-
-int walk_mode() {
-    const char* e = getenv("MFA_WALK");
-    return !e ? 0 : e[0] == 't' ? 1 : e[0] == 'j' ? 2 : 0;     // "table" / "jit"; anything else: automatic
-}
-
-static size_t wave_words(uint32_t K, uint32_t C, bool ig, uint32_t nm_words = 0) {
-    if (nm_words != 0u && K == 1u) return walk_wave_words_k1(C, ig) + (size_t)nm_words * 64u;      // the long-list kernel's node maps
-    switch (K) {
-        case 1: return walk_wave_words_k1(C, ig); case 2: return walk_wave_words_k2(C, ig); case 3: return walk_wave_words_k3(C, ig);
-        case 4: return walk_wave_words_k4(C, ig); case 5: return walk_wave_words_k5(C, ig); case 6: return walk_wave_words_k6(C, ig);
-        case 7: return walk_wave_words_k7(C, ig); case 8: return walk_wave_words_k8(C, ig); default: return walk_wave_words_k9(C, ig);
-    }
-}
-
-// One launch over the sub-batch [d_offsets[0], d_offsets[n]).  The LDS capacity C of the lists: enough for the automata's
-// longest possible list if that leaves room for two workgroups per CU, else what does (longer lists spill to `d_spill`).
+// One launch over the sub-batch [d_offsets[0], d_offsets[n]): what is launched is plan_walk's decision (walk_plan.h); here are the
+// environment, the lean hint's pinned word, the spill buffer and the stream.
 int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                 uint8_t* d_results, const uint64_t* d_regions, uint32_t n_seg, const uint32_t* seg_first, const uint32_t* seg_table,
                 uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, LeanHint* lean, void* wait_event) {
     if (n == 0) { if (wait_event) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)wait_event, 0)); return MFA_OK; }
-    if (n_seg == 0 || n_seg > WALK_MAX_SEG || n > 0xffffffffull) return MFA_ERR_INVALID_ARG;
+    const WalkKnobs kn = walk_knobs();
+    Lean decision = d_regions != nullptr && kn.accel && kn.lean != 0 ? Lean::on : Lean::off;
+    LeanHint next;
+    const bool hinted = decision == Lean::on && lean != nullptr;
+    if (hinted && lean->h_seen == nullptr) {
+        if (hipHostMalloc((void**)&lean->h_seen, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) *lean->h_seen = 0u; else (void)hipGetLastError();
+    }
+    const uint32_t seen = hinted && lean->h_seen ? *(volatile uint32_t*)lean->h_seen : 0u;
+    if (hinted && lean->h_seen) { next = *lean; decision = lean_decide(seen, next, kn); }
     WalkLaunch L;
+    int rc = plan_walk(p, kn, n, n_cus, n_seg, decision, L);
+    if (rc != MFA_OK) return rc;
     WalkArgs& a = L.args;
-    std::memset(&a, 0, sizeof a);
-    a.bytes = d_bytes; a.offsets = d_offsets; a.n = n; a.results = d_results; a.regions = d_regions; a.tables = d_tables;
-    a.counter = d_counter;
-    a.table_words = p.table_words;
-    a.shared_words = (p.table_words + 63u) & ~63u;
-    // tables beyond a third of the LDS (or forced: development) stay in global memory
-    L.tables_global = a.shared_words > 160u * 1024u / 4u / 3u || getenv("MFA_WALK_TABLES_GLOBAL") != nullptr;
-    if (L.tables_global) a.shared_words = 0;
-    a.n_seg = n_seg;
+    if (hinted && lean->h_seen) {                              // (a launch that cannot be planned leaves the hint as it was)
+        if (getenv("MFA_VERBOSE")) fprintf(stderr, "mfa_hip: table walk of %llu strings: last lean queue seen %d, launch %u: lean kernel %s\n",
+                                           (unsigned long long)n, (int)seen - 1, lean->launches, decision == Lean::off ? "left out" : decision == Lean::probe ? "on (a look)" : "on");
+        *lean = next;
+        a.lean_seen = lean->h_seen;
+    }
+    rc = ctx_reserve((void**)d_spill, spill_bytes, L.spill_bytes);
+    if (rc != MFA_OK) return rc;
+    a.bytes = d_bytes; a.offsets = d_offsets; a.results = d_results; a.regions = d_regions; a.tables = d_tables; a.counter = d_counter;
     for (uint32_t k = 0; k <= n_seg; k++) a.seg_first[k] = seg_first[k];
     for (uint32_t k = 0; k < n_seg; k++) a.seg_table[k] = seg_table[k];
-    const char* ae = getenv("MFA_ACCEL");
-    a.accel = (ae && ae[0] == '0') ? 0u : 1u;
-    a.refill = (uint32_t)std::max(1, std::min(64, env_int("MFA_WALK_REFILL", 1)));
-    // capacity
-    const bool ig = env_int("MFA_WALK_IMAGES_GLOBAL", 0) != 0;
-    a.images_global = ig ? 1u : 0u;
-    const size_t lds_max = 160u * 1024u / 4u;                 // words
-    const int want_c = env_int("MFA_WALK_C", 0);
-    const uint32_t c_cap = want_c > 0 ? (uint32_t)want_c : 8u;
-    uint32_t C = std::min(p.max_live, c_cap);
-    if (C < 1) C = 1;
-    // two workgroups per CU when the batch fills the device; a batch that does not even give every CU one workgroup leaves the LDS to that
-    // one: longer lists stay in LDS (the 77-node automata: lists of 10, three entries of them in LDS at two workgroups per CU)
-    const uint64_t cus_ = (uint64_t)(n_cus > 0 ? n_cus : 256);
-    const uint32_t wgs_goal = (uint32_t)env_int("MFA_WALK_WGS", (n + 255) / 256 <= cus_ ? 1 : 2);
-    // one-cell automata with long lists (the 77-node ex. 8 -bnf / -reverse) have a kernel of their own, which finds a node's entry through a
-    // per-lane map in LDS: one byte per node and lane (automata of up to 128 nodes; beyond them the general kernel's key search)
-    const bool long_lists = p.K == 1 && p.max_live > 16u && p.max_live < 128u && env_int("MFA_WALK_LONG", 1) != 0 && getenv("MFA_WALK_STATS") == nullptr;
-    a.nm_words = long_lists ? (p.max_live + 1u + 3u) / 4u : 0u;
-    while (C > 1 && want_c <= 0 && a.shared_words + 4u * wave_words(p.K, C, ig, a.nm_words) > lds_max / wgs_goal) C--;
-    while (C > 1 && a.shared_words + 4u * wave_words(p.K, C, ig, a.nm_words) > lds_max) C--;
-    if (a.shared_words + 4u * wave_words(p.K, C, ig, a.nm_words) > lds_max) return MFA_ERR_UNSUPPORTED;      // the tables alone fill the LDS
-    a.C = C;
-    a.CX = p.max_live > C ? p.max_live - C : 1u;
-    const size_t lds_words = a.shared_words + 4u * wave_words(p.K, C, ig, a.nm_words);
-    uint64_t per_cu = lds_max / lds_words;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const int cap_waves = env_int("MFA_WALK_WAVES_PER_CU", 0);      // development knob (multiples of 4)
-    if (cap_waves > 0 && (uint64_t)(cap_waves + 3) / 4 < per_cu) per_cu = (uint64_t)(cap_waves + 3) / 4;
-    uint64_t grid = (uint64_t)(n_cus > 0 ? n_cus : 256) * per_cu, want = (n + 255) / 256;
-    {   // development: a fraction of the workgroups the device holds (fewer walk waves beside the region pass, each taking more tickets)
-        const int pct = env_int("MFA_WALK_GRID_PCT", 100);
-        if (pct > 0 && pct < 100) grid = std::max<uint64_t>(1, grid * (uint64_t)pct / 100u);
-    }
-    if (grid > want) grid = want;
-    // What a wave may spill (list entries and probe images beyond the LDS capacity) is sized for the worst case -- every node of the launch's
-    // largest automaton alive at once -- per wave of the grid: 4.7 MB per wave for 1024 nodes and one cell.  The grid shrinks (the waves are
-    // persistent: fewer of them take more tickets each) until that fits a budget, 2 GiB by default; what does not fit with ONE workgroup is MFA_ERR_NOMEM.
-    const uint32_t W = 2 + 2 * p.K, DW = (1 + 2 * p.K + 1) / 2;
-    const size_t per_wave = ((size_t)(a.CX + a.C) * 64u * (3u * W + 3u * DW) + 4u * 4u * 64u) * sizeof(uint32_t);      // + the comparison answers (walk_core.h: CMP_CACHE)
-    const size_t budget = (size_t)std::max(1, env_int("MFA_WALK_SPILL_MB", 2048)) << 20;
-    while (grid > 1 && grid * 4u * per_wave > budget) grid = (grid + 1) / 2;
-    if (grid * 4u * per_wave > budget) return MFA_ERR_NOMEM;
-    L.grid = (unsigned)grid;
-    L.reversed = p.reversed;
-    // the lean kernel behind it (strings without periodic stretches: walk.hip): the plain step only, lists of the same capacity, four
-    // workgroups per CU where the LDS allows; its waves' spill areas and the queue of string numbers share the buffer with this launch's
-    L.lean_grid = 0; L.lean_C = a.C;
-    size_t lean_bytes = 0, queue_at = 0;
-    // (An EMPTY lean launch is not free beside a region pass: its workgroups -- 128 VGPRs, LDS for the tables and the lists -- queue for room like any
-    // other; 0.1-0.35 ms of the walk stream's time were measured for launches that had nothing to do.  So a launch whose slot last reported an empty
-    // queue leaves the lean kernel and the queue out, and looks again every 32nd time only, with a quarter of the grid.)
-    bool want_lean = d_regions != nullptr && a.accel != 0u && env_int("MFA_WALK_LEAN", 1) != 0;
-    bool lean_probe = false;
-    if (want_lean && lean != nullptr) {
-        if (lean->h_seen == nullptr && hipHostMalloc((void**)&lean->h_seen, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) *lean->h_seen = 0u;
-        if (lean->h_seen == nullptr) (void)hipGetLastError();
-        else {
-            const uint32_t seen = *(volatile uint32_t*)lean->h_seen;      // what the last lean kernel of this slot that has ended found (+ 1; 0: none has reported yet)
-            lean->quiet = seen == 1u ? lean->quiet + 1u : 0u;
-            if (lean->quiet >= 1u && env_int("MFA_WALK_LEAN", 1) != 2) {      // (MFA_WALK_LEAN=2: always)
-                if ((lean->launches & 31u) != 0u) want_lean = false; else lean_probe = true;
-            }
-            if (getenv("MFA_VERBOSE")) fprintf(stderr, "mfa_hip: table walk of %llu strings: last lean queue seen %d, launch %u: lean kernel %s\n",
-                                               (unsigned long long)n, (int)seen - 1, lean->launches, want_lean ? (lean_probe ? "on (a look)" : "on") : "left out");
-            lean->launches++;
-            a.lean_seen = lean->h_seen;
-        }
-    }
-    if (want_lean) {
-        const size_t lean_wave_words = (size_t)a.C * 64u * 2u * W + (size_t)a.nm_words * 64u;
-        uint64_t lean_per_cu = lds_max / (a.shared_words + 4u * lean_wave_words);
-        if (lean_per_cu > 4) lean_per_cu = 4;
-        if (lean_per_cu >= 1) {
-            uint64_t lg = (uint64_t)(n_cus > 0 ? n_cus : 256) * lean_per_cu;
-            if (lean_probe) lg = std::max<uint64_t>(1, lg / 4u);
-            if (lg > want) lg = want;
-            const size_t lean_per_wave = ((size_t)(a.CX + a.C) * 64u * 2u * W + 4u * 4u * 64u) * sizeof(uint32_t);
-            while (lg > 1 && lg * 4u * lean_per_wave > budget) lg = (lg + 1) / 2;
-            L.lean_grid = (unsigned)lg;
-            lean_bytes = (size_t)lg * 4u * lean_per_wave;
-        }
-    }
-    const size_t need = std::max((size_t)grid * 4u * per_wave, lean_bytes);
-    queue_at = (need + 255u) & ~(size_t)255u;
-    int rc = ctx_reserve((void**)d_spill, spill_bytes, queue_at + (L.lean_grid ? (size_t)n * sizeof(uint32_t) : 0));
-    if (rc != MFA_OK) return rc;
     a.spill = *d_spill;
-    a.lean_queue = L.lean_grid ? reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(*d_spill) + queue_at) : nullptr;
-    const bool stats = getenv("MFA_WALK_STATS") != nullptr && p.K == 1;
-    if (stats) { a.lean_queue = nullptr; L.lean_grid = 0; }
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned long long) * (stats ? 32 : 3), (hipStream_t)stream));      // ticket counter, queue length, the lean kernel's tickets
+    a.lean_queue = L.lean_grid ? reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(*d_spill) + L.queue_at) : nullptr;
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned long long) * L.counter_words, (hipStream_t)stream));
     // (what the launch waits for -- its group's regions -- comes AFTER its own preparations on the stream: they are done when the event arrives)
     if (wait_event) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)wait_event, 0));
-    if (stats) {
-        rc = launch_walk_stats(L, stream);
-        if (rc == MFA_OK) { (void)hipStreamSynchronize((hipStream_t)stream); walk_print_stats(d_counter, "walk"); }
-        return rc;
-    }
-    if (long_lists) return launch_walk_long_k1(L, stream);
-    switch (p.K) {
-        case 1: return launch_walk_k1(L, stream); case 2: return launch_walk_k2(L, stream); case 3: return launch_walk_k3(L, stream);
-        case 4: return launch_walk_k4(L, stream); case 5: return launch_walk_k5(L, stream); case 6: return launch_walk_k6(L, stream);
-        case 7: return launch_walk_k7(L, stream); case 8: return launch_walk_k8(L, stream); case 9: return launch_walk_k9(L, stream);
-    }
-    return MFA_ERR_UNSUPPORTED;
+    typedef int (*Launcher)(const WalkLaunch&, void*);
+    static const Launcher by_cells[WALK_MAX_K + 1] = {nullptr, launch_walk_k1, launch_walk_k2, launch_walk_k3, launch_walk_k4, launch_walk_k5,
+                                                     launch_walk_k6, launch_walk_k7, launch_walk_k8, launch_walk_k9};
+    if (!walk_has_kernel(L)) return MFA_ERR_UNSUPPORTED;
+    rc = (L.kernel == WalkKernel::stats ? launch_walk_stats : L.kernel == WalkKernel::long_k1 ? launch_walk_long_k1 : by_cells[L.K])(L, stream);
+    if (L.kernel == WalkKernel::stats && rc == MFA_OK) { (void)hipStreamSynchronize((hipStream_t)stream); walk_print_stats(d_counter, "walk"); }
+    return rc;
 }
 
 void lean_hint_free(LeanHint& h) {
@@ -190,7 +86,7 @@ using namespace mfa;
 //   * generated kernels (default while they are the faster walk on small automata): one launch per segment, spread over a few walk
 //     streams by measured cost -- the first call on a device runs the walks one after the other and times them, later calls give
 //     each walk to the stream that can start it first (list scheduling with the groups' region times as release times).
-constexpr uint32_t MIX_MAX_GROUPS = 12, MIX_MAX_STREAMS = 4, MIX_MAX_LAUNCHES = 24, MIX_TIMINGS = 32;
+constexpr uint32_t MIX_TIMINGS = 32;      // (MIX_MAX_GROUPS, MIX_MAX_STREAMS, MIX_MAX_LAUNCHES: walk_plan.h)
 
 struct mfa_mixed {
     std::vector<mfa_image*> images;
@@ -280,9 +176,8 @@ void mfa_mixed_destroy(mfa_mixed_t* mx) {
 }
 
 static int mixed_device(mfa_mixed* mx, int device, mfa_mixed::Dev** out) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
-    HIP_TRY(hipSetDevice(device));
+    const int rc = check_device(device);
+    if (rc != MFA_OK) return rc;
     auto it = mx->dev.find(device);
     if (it != mx->dev.end()) { *out = &it->second; return MFA_OK; }
     mfa_mixed::Dev d;
@@ -306,9 +201,6 @@ static int mixed_device(mfa_mixed* mx, int device, mfa_mixed::Dev** out) {
     return MFA_OK;
 }
 
-// What a call will launch, decided before anything is put on a stream (an error found here leaves the streams untouched).
-struct MixLaunch { uint32_t g, s0, s1, ml, Kc, w0, w1; uint64_t a, b; int k; };
-
 // seg_first: HOST array of n_images + 1 string indices, seg_first[0] = 0, seg_first[n_images] = n: strings seg_first[s] ..
 // seg_first[s+1]-1 are matched against images[s] (the order of mfa_mixed_create).  `stream` sees the call as one operation.
 // total_bytes: offsets[n] - offsets[0] if the caller knows it, else 0 (then it is read back once per string count: see the header).
@@ -326,63 +218,28 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     if (rc != MFA_OK) return rc;
     hipStream_t cs = (hipStream_t)stream;
     const bool table = walk_mode() != 2 && mx->table_ok;      // the table engine unless the generated kernels are asked for
-    // groups: ranges of strings, cut at fractions of the batch (a segment may straddle a cut).  Decreasing sizes: the walk of the
-    // last group is what the call ends with.
-    std::vector<uint64_t> cut{0};
-    {
-        // How many groups pays depends on the batch's BYTES: a group's region launch should take about as long as a walk launch needs anyway
-        // (a walk is latency-bound: ~0.3-0.5 ms for 20 000 strings as for 200 000): 1.3 GB per group, eight groups at most (measured: 10.7 GB of
-        // 64 KiB strings 2.02 ms in eight groups, 2.28 ms in four; the 19.4 GB headline batch eight).  Cut finer, a small batch pays the walks'
-        // latency once per group (a 1.9 GB batch of one automaton: 1.26 ms in eight groups against 0.52 ms in one; 34 ms against 9.8 ms
-        // for the 77-node automaton).  The bytes of a batch are device data (offsets[n] - offsets[0]): a caller that knows them says so
-        // (mfa_match_mixed_sized); otherwise they are read back ONCE per string count this object meets -- that call waits for the
-        // caller's stream -- and remembered (a later batch with the same count and other bytes gets the same grouping: a matter of speed only).
-        const char* spec = getenv("MFA_MIXED_CUTS");
-        std::string made;
-        if (!spec) {
-            uint64_t bytes = total_bytes;
-            auto known = mx->bytes_of.find(n);
-            if (bytes != 0) { /* the caller's word */ }
-            else if (known != mx->bytes_of.end()) bytes = known->second;
-            else if (n >= 65536) {
-                uint64_t ends[2] = {0, 0};
-                HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
-                HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
-                HIP_TRY(hipStreamSynchronize(cs));
-                bytes = ends[1] - ends[0];
-                if (mx->bytes_of.size() >= 64) mx->bytes_of.clear();
-                mx->bytes_of[n] = bytes;
-            }
-            const double per_group = table ? 1.3e9 : 2.0e9;
-            const uint32_t most = table ? 8u : 5u;
-            uint32_t want = (uint32_t)std::min<double>(most, std::max(1.0, std::floor((double)bytes / per_group + 0.5)));
-            if (n < 65536) want = 1;
-            // sizes: equal, the last three groups 0.8 / 0.53 / 0.33 of that (two groups: 1, 0.6; three: 1, 0.8, 0.4) -- the walk of the last
-            // group is what the call ends with
-            std::vector<double> w(want, 1.0);
-            if (want == 2) w[1] = 0.6;
-            else if (want == 3) { w[1] = 0.8; w[2] = 0.4; }
-            else if (want >= 4) { w[want - 3] = 0.8; w[want - 2] = 0.53; w[want - 1] = 0.33; }
-            double total = 0, acc = 0;
-            for (double x : w) total += x;
-            for (uint32_t k = 0; k + 1 < want; k++) { acc += w[k]; made += (k ? "," : "") + std::to_string(acc / total); }
-            spec = made.c_str();
+    // groups of strings (walk_plan.h: plan_cuts), by the batch's bytes.  Those are device data (offsets[n] - offsets[0]): a caller that knows
+    // them says so (mfa_match_mixed_sized); otherwise they are read back ONCE per string count this object meets -- that call waits for the
+    // caller's stream -- and remembered (a later batch with the same count and other bytes gets the same grouping: a matter of speed only).
+    const char* spec = getenv("MFA_MIXED_CUTS");
+    uint64_t bytes = total_bytes;
+    if (!spec && bytes == 0) {
+        auto known = mx->bytes_of.find(n);
+        if (known != mx->bytes_of.end()) bytes = known->second;
+        else if (n >= 65536) {
+            uint64_t ends[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
+            HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
+            HIP_TRY(hipStreamSynchronize(cs));
+            bytes = ends[1] - ends[0];
+            if (mx->bytes_of.size() >= 64) mx->bytes_of.clear();
+            mx->bytes_of[n] = bytes;
         }
-        for (const char* q = spec; *q && cut.size() < MIX_MAX_GROUPS;) {
-            const uint64_t at = (uint64_t)((double)n * atof(q));
-            if (at > cut.back() && at < n) cut.push_back(at);
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
-        cut.push_back(n);
     }
+    const std::vector<uint64_t> cut = plan_cuts(n, bytes, table, spec);
     const uint32_t ng = (uint32_t)cut.size() - 1;
-    const char* re = getenv("MFA_REGIONS");
-    const char* ae = getenv("MFA_ACCEL");
-    const bool with_regions = !(re && re[0] == '0') && !(ae && ae[0] == '0');
-    int NW = env_int("MFA_MIXED_WALK_STREAMS", table ? 2 : 3);
-    if (NW < 1) NW = 1;
-    if (NW > (int)MIX_MAX_STREAMS) NW = MIX_MAX_STREAMS;
+    const bool with_regions = regions_enabled();
+    const int NW = mixed_walk_streams(table);
 
     // One automaton, one group: exactly the single-automaton call (mfa_match_batch: region pass, then the walk, on the caller's stream, with the
     // engine that call would choose) -- the hops to the internal streams and back cost such a batch 0.03-0.06 ms and buy it nothing.  (Cutting a
@@ -402,31 +259,13 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         return MFA_OK;
     }
 
-    // ---- the plan (table engine): one launch per group and run of consecutive segments whose automata have the same number of cells (a
-    // launch's kernel and its LDS footprint are those of its largest cell count); groups alternate between the walk streams, so that a
-    // group's walk may start while the one before it drains
+    // ---- what the call will launch, decided before anything is put on a stream (an error found here leaves the streams untouched)
     std::vector<MixLaunch> plan;
-    if (table)
-        for (uint32_t g = 0; g < ng; g++) {
-            const uint64_t lo = cut[g], hi = cut[g + 1];
-            uint32_t sa = 0;
-            while (sa + 1 < ns && seg_first[sa + 1] <= lo) sa++;
-            uint32_t sb = sa;
-            while (sb < ns && seg_first[sb] < hi) sb++;
-            for (uint32_t s0 = sa; s0 < sb;) {
-                uint32_t s1 = s0 + 1;
-                const uint32_t Kc = mx->K > 6 ? mx->K : mx->images[s0]->walk.K;
-                while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (mx->K > 6 || mx->images[s1]->walk.K == Kc)) s1++;
-                const uint64_t a = std::max(seg_first[s0], lo), b = std::min(seg_first[s1], hi);
-                if (b > a) {
-                    uint32_t ml = 1;
-                    for (uint32_t j = s0; j < s1; j++) ml = std::max(ml, mx->images[j]->walk.max_live);
-                    // the launch gets the blocks of ITS automata only (they lie back to back): less LDS per workgroup
-                    plan.push_back(MixLaunch{g, s0, s1, ml, Kc, mx->block_at[s0], s1 < ns ? mx->block_at[s1] : (uint32_t)mx->words.size(), a, b, (int)(g % (uint32_t)NW)});
-                }
-                s0 = s1;
-            }
-        }
+    if (table) {
+        std::vector<MixImage> imgs;
+        for (uint32_t s = 0; s < ns; s++) imgs.push_back(MixImage{mx->images[s]->walk.K, mx->images[s]->walk.max_live, mx->block_at[s]});
+        plan = plan_table_launches(cut, seg_first, imgs, mx->K, (uint32_t)mx->words.size(), NW);
+    }
     if (plan.size() > MIX_MAX_LAUNCHES) return MFA_ERR_UNSUPPORTED;      // (more runs of equal cell count than the object has launch slots: nothing was started)
     uint64_t* d_table = nullptr;
     if (with_regions) {
@@ -435,20 +274,8 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         d_table = d->d_regions;
     }
     // which stream walks which segment (generated kernels): first call one after the other (timed), then by cost
-    std::vector<int> where(ns, 0);
     const bool calibrating = !table && !d->calibrated;
-    if (!table && d->calibrated && d->ng_last == ng) {
-        // a segment's walk is released when the group that holds its first string is scanned (segments that straddle a cut are rare)
-        float free_at[MIX_MAX_STREAMS] = {0};
-        for (uint32_t s = 0, g = 0; s < ns; s++) {
-            while (g + 1 < ng && cut[g + 1] <= seg_first[s]) g++;
-            int best = 0;
-            for (int k = 1; k < NW; k++)
-                if (std::max(free_at[k], d->ready[g]) < std::max(free_at[best], d->ready[g])) best = k;
-            free_at[best] = std::max(free_at[best], d->ready[g]) + 1.5f * d->cost[s];      // beside the region pass a walk takes about 1.5 x its time alone
-            where[s] = best;
-        }
-    }
+    const std::vector<int> where = !table && d->calibrated && d->ng_last == ng ? assign_streams(cut, seg_first, ns, d->ready, d->cost.data(), NW) : std::vector<int>(ns, 0);
     for (int k = 0; k < NW; k++)
         if (!d->ws[k]) HIP_TRY(hipStreamCreateWithFlags(&d->ws[k], hipStreamNonBlocking));
     const uint32_t slot_t = (uint32_t)(d->calls % MIX_TIMINGS);
@@ -495,21 +322,16 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
                 if (L.g != g) continue;
                 void* wait_for = nullptr;                       // (the launch itself waits, behind its own preparations on the stream)
                 if (!waits[L.k]) { waits[L.k] = true; wait_for = d->ev_g[g]; }
-                uint32_t sf[WALK_MAX_SEG + 1], stb[WALK_MAX_SEG];
-                for (uint32_t j = 0; j <= L.s1 - L.s0; j++) sf[j] = (uint32_t)(std::min(std::max(seg_first[L.s0 + j], L.a), L.b) - L.a);
-                for (uint32_t j = 0; j < L.s1 - L.s0; j++) stb[j] = mx->block_at[L.s0 + j] - L.w0;
                 const WalkPlanInput pk{L.Kc, L.ml, mx->reversed, L.w1 - L.w0};
                 join.used[L.k] = true;
                 rc = launch_walk(pk, d->d_tables + L.w0, d->n_cus, d_bytes, d_offsets + L.a, L.b - L.a, d_results + L.a, d_table ? d_table + L.a * MFA_REGION_WORDS : nullptr,
-                                 L.s1 - L.s0, sf, stb, &d->d_spill[slot], &d->spill_bytes[slot], d->d_counters + 64 * slot, d->ws[L.k], &d->lean[slot], wait_for);
+                                 L.s1 - L.s0, L.sf, L.stb, &d->d_spill[slot], &d->spill_bytes[slot], d->d_counters + 64 * slot, d->ws[L.k], &d->lean[slot], wait_for);
                 if (rc != MFA_OK) return rc;
                 slot++;
             }
         } else {
-            uint32_t sa = 0;
-            while (sa + 1 < ns && seg_first[sa + 1] <= lo) sa++;
-            uint32_t sb = sa;
-            while (sb < ns && seg_first[sb] < hi) sb++;
+            uint32_t sa, sb;
+            segments_of(seg_first, ns, lo, hi, sa, sb);
             for (uint32_t s = sa; s < sb; s++) {
                 const uint64_t a = std::max(seg_first[s], lo), b = std::min(seg_first[s + 1], hi);
                 if (b <= a) continue;
@@ -575,36 +397,9 @@ int mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launch
 // The same with HOST pointers: copies the batch to the device, matches, copies the results back, synchronises (the host mirror's
 // match_mixed and the `diploma -match-mixed` command line; throughput is then bounded by the host link).
 int mfa_match_mixed_host(mfa_mixed_t* mx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, const uint64_t* seg_first, uint8_t* results, int device) {
-    if (!mx || !offsets || !seg_first || (!results && n)) return MFA_ERR_INVALID_ARG;
-    if (n == 0) return MFA_OK;
-    for (uint64_t k = 0; k < n; k++) {
-        if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
-        if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) return MFA_ERR_TOO_LONG;
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
-    HIP_TRY(hipSetDevice(device));
-    const uint64_t total = offsets[n] - offsets[0];
-    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint8_t* d_res = nullptr;
-    std::vector<uint64_t> rel(n + 1);
-    for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
-    int rc = MFA_OK;
-    hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_res, n);
-    if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    if (rc == MFA_OK) rc = match_mixed_impl(mx, d_bytes, d_off, n, seg_first, d_res, device, nullptr, total);
-    if (rc == MFA_OK) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    }
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_off) (void)hipFree(d_off);
-    if (d_res) (void)hipFree(d_res);
-    return rc;
+    if (!mx || !seg_first) return MFA_ERR_INVALID_ARG;
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t total) {
+        return match_mixed_impl(mx, d_bytes, d_off, n, seg_first, d_res, device, nullptr, total); });
 }
 
 // Device time of a recent mfa_match_mixed on `device`: from its first region launch to the end of its last region launch, and to the

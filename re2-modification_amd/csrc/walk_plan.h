@@ -1,0 +1,256 @@
+// What a walk launch and a mixed call will do, decided by pure functions: no HIP, no allocation, no stream.  walk_launch.hip reads the
+// environment, calls these, and then only allocates, enqueues and launches what they say; tests/emul/plan_emul.cpp runs the same
+// functions on a machine without a GPU (tests/test_walk_plan_cpu.py).  The layout of a wave's memory is walk.h's WalkLayout.
+#ifndef MFA_WALK_PLAN_H
+#define MFA_WALK_PLAN_H
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/mfa_hip.h"
+#include "walk.h"
+
+namespace mfa {
+
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e && *e ? atoi(e) : dflt;
+}
+inline bool env_is_off(const char* name) { const char* e = getenv(name); return e && e[0] == '0'; }
+// MFA_REGIONS=0 (or MFA_ACCEL=0): no region pass and no table: every step is executed (A/B runs)
+inline bool regions_enabled() { return !env_is_off("MFA_REGIONS") && !env_is_off("MFA_ACCEL"); }
+
+inline int walk_mode() {        // MFA_WALK: 0 automatic (default), 1 "table", 2 "jit"
+    const char* e = getenv("MFA_WALK");
+    return !e ? 0 : e[0] == 't' ? 1 : e[0] == 'j' ? 2 : 0;
+}
+
+// ---- one walk launch ---------------------------------------------------------------------------------------------------------------
+struct WalkPlanInput { uint32_t K, max_live; bool reversed; uint32_t table_words; };
+
+// Whether the lean kernel behind a table walk (walk.hip: strings without periodic stretches) has had anything to do lately: the kernel
+// reports the length of its queue (+ 1) to a word of pinned host memory, and a launch whose slot last saw an empty queue leaves the lean
+// kernel and the queue out (an empty launch beside a region pass costs the stream 0.1-0.35 ms: its workgroups -- 128 VGPRs, LDS for the
+// tables and the lists -- queue for room like any other) -- except every 32nd time, with a quarter of the grid, to notice when the input changes.
+struct LeanHint {
+    uint32_t* h_seen = nullptr;      // pinned, device-visible; 0 = nothing reported yet
+    uint32_t quiet = 0, launches = 0;
+};
+enum class Lean { off, on, probe };
+
+// every MFA_WALK_* / MFA_ACCEL value a launch depends on, read from the environment on every call
+struct WalkKnobs {
+    bool tables_global, images_global, accel, long_lists, stats;
+    int refill, want_c, wgs, waves_per_cu, grid_pct, spill_mb, lean;
+};
+inline WalkKnobs walk_knobs() {
+    WalkKnobs k;
+    k.tables_global = getenv("MFA_WALK_TABLES_GLOBAL") != nullptr;      // development: the tables stay in global memory
+    k.images_global = env_int("MFA_WALK_IMAGES_GLOBAL", 0) != 0;
+    k.accel = !env_is_off("MFA_ACCEL");
+    k.long_lists = env_int("MFA_WALK_LONG", 1) != 0;
+    k.stats = getenv("MFA_WALK_STATS") != nullptr;
+    k.refill = std::max(1, std::min(64, env_int("MFA_WALK_REFILL", 1)));
+    k.want_c = env_int("MFA_WALK_C", 0);
+    k.wgs = env_int("MFA_WALK_WGS", 0);                        // workgroups per CU to leave LDS for (0: by the size of the batch)
+    k.waves_per_cu = env_int("MFA_WALK_WAVES_PER_CU", 0);      // development knob (multiples of 4)
+    k.grid_pct = env_int("MFA_WALK_GRID_PCT", 100);
+    k.spill_mb = std::max(1, env_int("MFA_WALK_SPILL_MB", 2048));
+    k.lean = env_int("MFA_WALK_LEAN", 1);                      // 0: never, 2: always
+    return k;
+}
+
+// `seen`: what the last lean kernel of this slot that has ended found (+ 1; 0: none has reported yet)
+inline Lean lean_decide(uint32_t seen, LeanHint& h, const WalkKnobs& kn) {
+    h.quiet = seen == 1u ? h.quiet + 1u : 0u;
+    Lean d = Lean::on;
+    if (h.quiet >= 1u && kn.lean != 2) d = (h.launches & 31u) != 0u ? Lean::off : Lean::probe;
+    h.launches++;
+    return d;
+}
+
+// Fills everything of L but the pointers and the segment arrays of L.args.  The LDS capacity C of the lists: enough for the automata's
+// longest possible list if that leaves room for two workgroups per CU, else what does (longer lists spill).
+// lean: Lean::off also when the launch has no region table, MFA_ACCEL=0 or MFA_WALK_LEAN=0.
+inline int plan_walk(const WalkPlanInput& p, const WalkKnobs& kn, uint64_t n, int n_cus, uint32_t n_seg, Lean lean, WalkLaunch& L) {
+    if (n_seg == 0 || n_seg > WALK_MAX_SEG || n > 0xffffffffull) return MFA_ERR_INVALID_ARG;
+    L = WalkLaunch{};
+    WalkArgs& a = L.args;
+    a.n = n; a.n_seg = n_seg;
+    a.table_words = p.table_words;
+    a.shared_words = (p.table_words + 63u) & ~63u;
+    const size_t lds_max = WALK_LDS_BYTES / 4u;                 // words
+    // tables beyond a third of the LDS (or forced: development) stay in global memory
+    L.tables_global = a.shared_words > lds_max / 3u || kn.tables_global;
+    if (L.tables_global) a.shared_words = 0;
+    a.accel = kn.accel ? 1u : 0u;
+    a.refill = (uint32_t)kn.refill;
+    a.images_global = kn.images_global ? 1u : 0u;
+    L.K = p.K; L.reversed = p.reversed;
+    // one-cell automata with long lists (the 77-node ex. 8 -bnf / -reverse) have a kernel of their own, which finds a node's entry through a
+    // per-lane map in LDS: one byte per node and lane (automata of up to 128 nodes; beyond them the general kernel's key search)
+    const bool long_lists = p.K == 1 && p.max_live > 16u && p.max_live < 128u && kn.long_lists && !kn.stats;
+    L.kernel = kn.stats && p.K == 1 ? WalkKernel::stats : long_lists ? WalkKernel::long_k1 : WalkKernel::plain;
+    a.nm_words = long_lists ? (p.max_live + 1u + 3u) / 4u : 0u;
+    const auto layout = [&](uint32_t C, bool lean_walk) { return WalkLayout{p.K, C, p.max_live > C ? p.max_live - C : 1u, kn.images_global, lean_walk, a.nm_words}; };
+    const auto lds_words = [&](uint32_t C) { return (size_t)a.shared_words + 4u * (size_t)layout(C, false).lds_words(); };
+    // two workgroups per CU when the batch fills the device; a batch that does not even give every CU one workgroup leaves the LDS to that
+    // one: longer lists stay in LDS (the 77-node automata: lists of 10, three entries of them in LDS at two workgroups per CU)
+    const uint64_t cus = (uint64_t)(n_cus > 0 ? n_cus : 256), want = (n + 255) / 256;
+    const uint32_t wgs_goal = kn.wgs != 0 ? (uint32_t)kn.wgs : want <= cus ? 1u : 2u;
+    uint32_t C = std::max(1u, std::min(p.max_live, kn.want_c > 0 ? (uint32_t)kn.want_c : 8u));
+    while (C > 1 && kn.want_c <= 0 && lds_words(C) > lds_max / wgs_goal) C--;
+    while (C > 1 && lds_words(C) > lds_max) C--;
+    if (lds_words(C) > lds_max) return MFA_ERR_UNSUPPORTED;      // the tables alone fill the LDS
+    const WalkLayout full = layout(C, false), lean_lay = layout(C, true);
+    a.C = C; a.CX = full.CX;
+    L.lds_bytes = walk_lds_bytes(a.shared_words, full);
+    uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, lds_max / lds_words(C)));
+    if (kn.waves_per_cu > 0 && (uint64_t)(kn.waves_per_cu + 3) / 4 < per_cu) per_cu = (uint64_t)(kn.waves_per_cu + 3) / 4;
+    uint64_t grid = cus * per_cu;
+    // development: a fraction of the workgroups the device holds (fewer walk waves beside the region pass, each taking more tickets)
+    if (kn.grid_pct > 0 && kn.grid_pct < 100) grid = std::max<uint64_t>(1, grid * (uint64_t)kn.grid_pct / 100u);
+    if (grid > want) grid = want;
+    // What a wave may spill (list entries and probe images beyond the LDS capacity) is sized for the worst case -- every node of the launch's
+    // largest automaton alive at once -- per wave of the grid: 4.7 MB per wave for 1024 nodes and one cell.  The grid shrinks (the waves are
+    // persistent: fewer of them take more tickets each) until that fits a budget, 2 GiB by default; what does not fit with ONE workgroup is MFA_ERR_NOMEM.
+    const size_t per_wave = full.spill_words() * sizeof(uint32_t);
+    const size_t budget = (size_t)kn.spill_mb << 20;
+    while (grid > 1 && grid * 4u * per_wave > budget) grid = (grid + 1) / 2;
+    if (grid * 4u * per_wave > budget) return MFA_ERR_NOMEM;
+    L.grid = (unsigned)grid;
+    // the lean kernel behind it: the plain step only, lists of the same capacity, four workgroups per CU where the LDS allows; its waves'
+    // spill areas and the queue of string numbers share the buffer with this launch's.  A look (Lean::probe) takes a quarter of the grid.
+    L.lean_C = a.C; L.lean_CX = a.CX;
+    L.lean_lds_bytes = walk_lds_bytes(a.shared_words, lean_lay);
+    size_t lean_bytes = 0;
+    const uint64_t lean_per_cu = std::min<uint64_t>(4, (size_t)WALK_LDS_BYTES / L.lean_lds_bytes);
+    if (lean != Lean::off && lean_per_cu >= 1) {
+        uint64_t lg = cus * lean_per_cu;
+        if (lean == Lean::probe) lg = std::max<uint64_t>(1, lg / 4u);
+        if (lg > want) lg = want;
+        const size_t lean_per_wave = lean_lay.spill_words() * sizeof(uint32_t);
+        while (lg > 1 && lg * 4u * lean_per_wave > budget) lg = (lg + 1) / 2;
+        L.lean_grid = (unsigned)lg;
+        lean_bytes = (size_t)lg * 4u * lean_per_wave;
+    }
+    const size_t need = std::max((size_t)grid * 4u * per_wave, lean_bytes);
+    L.queue_at = (need + 255u) & ~(size_t)255u;
+    L.spill_bytes = L.queue_at + (L.lean_grid ? (size_t)n * sizeof(uint32_t) : 0);
+    if (L.kernel == WalkKernel::stats) L.lean_grid = 0;        // (the counting build has no lean kernel behind it)
+    L.counter_words = L.kernel == WalkKernel::stats ? 32u : 3u;      // ticket counter, queue length, the lean kernel's tickets
+    return MFA_OK;
+}
+
+// ---- a mixed call --------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t MIX_MAX_GROUPS = 12, MIX_MAX_STREAMS = 4, MIX_MAX_LAUNCHES = 24;
+
+inline int mixed_walk_streams(bool table) {
+    return std::max(1, std::min((int)MIX_MAX_STREAMS, env_int("MFA_MIXED_WALK_STREAMS", table ? 2 : 3)));
+}
+
+// Groups: ranges of strings, cut at fractions of the batch (a segment may straddle a cut).  Decreasing sizes: the walk of the last group
+// is what the call ends with.  spec: MFA_MIXED_CUTS (fractions, comma separated), or nullptr: by the batch's bytes.
+// How many groups pays depends on the batch's BYTES: a group's region launch should take about as long as a walk launch needs anyway
+// (a walk is latency-bound: ~0.3-0.5 ms for 20 000 strings as for 200 000): 1.3 GB per group, eight groups at most (measured: 10.7 GB of
+// 64 KiB strings 2.02 ms in eight groups, 2.28 ms in four; the 19.4 GB headline batch eight).  Cut finer, a small batch pays the walks'
+// latency once per group (a 1.9 GB batch of one automaton: 1.26 ms in eight groups against 0.52 ms in one; 34 ms against 9.8 ms
+// for the 77-node automaton).
+inline std::vector<uint64_t> plan_cuts(uint64_t n, uint64_t bytes, bool table, const char* spec) {
+    std::string made;
+    if (!spec) {
+        const double per_group = table ? 1.3e9 : 2.0e9;
+        const uint32_t most = table ? 8u : 5u;
+        uint32_t want = (uint32_t)std::min<double>(most, std::max(1.0, std::floor((double)bytes / per_group + 0.5)));
+        if (n < 65536) want = 1;
+        // sizes: equal, the last three groups 0.8 / 0.53 / 0.33 of that (two groups: 1, 0.6; three: 1, 0.8, 0.4)
+        std::vector<double> w(want, 1.0);
+        if (want == 2) w[1] = 0.6;
+        else if (want == 3) { w[1] = 0.8; w[2] = 0.4; }
+        else if (want >= 4) { w[want - 3] = 0.8; w[want - 2] = 0.53; w[want - 1] = 0.33; }
+        double total = 0, acc = 0;
+        for (double x : w) total += x;
+        for (uint32_t k = 0; k + 1 < want; k++) { acc += w[k]; made += (k ? "," : "") + std::to_string(acc / total); }
+        spec = made.c_str();
+    }
+    std::vector<uint64_t> cut{0};
+    for (const char* q = spec; *q && cut.size() < MIX_MAX_GROUPS;) {
+        const uint64_t at = (uint64_t)((double)n * atof(q));
+        if (at > cut.back() && at < n) cut.push_back(at);
+        while (*q && *q != ',') q++;
+        if (*q == ',') q++;
+    }
+    cut.push_back(n);
+    return cut;
+}
+
+// the segments [first, second) that have strings in [lo, hi)
+inline void segments_of(const uint64_t* seg_first, uint32_t ns, uint64_t lo, uint64_t hi, uint32_t& sa, uint32_t& sb) {
+    sa = 0;
+    while (sa + 1 < ns && seg_first[sa + 1] <= lo) sa++;
+    sb = sa;
+    while (sb < ns && seg_first[sb] < hi) sb++;
+}
+
+// Table engine: one launch per group and run of consecutive segments whose automata have the same number of cells (a launch's kernel and
+// its LDS footprint are those of its largest cell count; an object with an automaton of more than 6 cells walks all with that kernel: K);
+// groups alternate between the NW walk streams, so that a group's walk may start while the one before it drains.
+struct MixImage { uint32_t K, max_live, block_at; };      // block_at: word offset of the automaton's table block in the object's tables
+struct MixLaunch {
+    uint32_t g, s0, s1, ml, Kc, w0, w1;      // group, segments [s0, s1), longest list, cells, table words [w0, w1)
+    uint64_t a, b;                           // strings [a, b)
+    int k;                                   // walk stream
+    uint32_t sf[WALK_MAX_SEG + 1], stb[WALK_MAX_SEG];      // launch_walk's seg_first / seg_table
+};
+inline std::vector<MixLaunch> plan_table_launches(const std::vector<uint64_t>& cut, const uint64_t* seg_first, const std::vector<MixImage>& img, uint32_t K,
+                                                  uint32_t total_words, int NW) {
+    const uint32_t ns = (uint32_t)img.size();
+    std::vector<MixLaunch> plan;
+    for (uint32_t g = 0; g + 1 < cut.size(); g++) {
+        const uint64_t lo = cut[g], hi = cut[g + 1];
+        uint32_t sa, sb;
+        segments_of(seg_first, ns, lo, hi, sa, sb);
+        for (uint32_t s0 = sa; s0 < sb;) {
+            uint32_t s1 = s0 + 1;
+            const uint32_t Kc = K > 6 ? K : img[s0].K;
+            while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (K > 6 || img[s1].K == Kc)) s1++;
+            MixLaunch L{};
+            L.a = std::max(seg_first[s0], lo); L.b = std::min(seg_first[s1], hi);
+            if (L.b > L.a) {
+                L.g = g; L.s0 = s0; L.s1 = s1; L.Kc = Kc; L.k = (int)(g % (uint32_t)NW); L.ml = 1;
+                // the launch gets the blocks of ITS automata only (they lie back to back): less LDS per workgroup
+                L.w0 = img[s0].block_at; L.w1 = s1 < ns ? img[s1].block_at : total_words;
+                for (uint32_t j = s0; j < s1; j++) { L.ml = std::max(L.ml, img[j].max_live); L.stb[j - s0] = img[j].block_at - L.w0; }
+                for (uint32_t j = s0; j <= s1; j++) L.sf[j - s0] = (uint32_t)(std::min(std::max(seg_first[j], L.a), L.b) - L.a);
+                plan.push_back(L);
+            }
+            s0 = s1;
+        }
+    }
+    return plan;
+}
+
+// Generated kernels: which walk stream walks which segment, by measured cost (list scheduling with the groups' region times `ready` as
+// release times).  A segment's walk is released when the group that holds its first string is scanned (segments that straddle a cut are rare).
+inline std::vector<int> assign_streams(const std::vector<uint64_t>& cut, const uint64_t* seg_first, uint32_t ns, const float* ready, const float* cost, int NW) {
+    std::vector<int> where(ns, 0);
+    const uint32_t ng = (uint32_t)cut.size() - 1;
+    float free_at[MIX_MAX_STREAMS] = {0};
+    for (uint32_t s = 0, g = 0; s < ns; s++) {
+        while (g + 1 < ng && cut[g + 1] <= seg_first[s]) g++;
+        int best = 0;
+        for (int k = 1; k < NW; k++)
+            if (std::max(free_at[k], ready[g]) < std::max(free_at[best], ready[g])) best = k;
+        free_at[best] = std::max(free_at[best], ready[g]) + 1.5f * cost[s];      // beside the region pass a walk takes about 1.5 x its time alone
+        where[s] = best;
+    }
+    return where;
+}
+
+}  // namespace mfa
+
+#endif

@@ -86,13 +86,14 @@ struct SeqFeeder {
 
 template <int K, bool REV>
 static void run(const Batch& b, const std::vector<uint32_t>& T, uint32_t C, uint32_t CM, WaveStats* ws) {
-    const uint32_t CX = CM > C ? CM - C : 1u;
-    std::vector<uint32_t> lv(2 * C * Lay<K>::W, 0xdeadbeefu), ld(2 * C * Lay<K>::DW, 0xdeadbeefu), sb(C * Lay<K>::W, 0xdeadbeefu), sa(C * Lay<K>::DW, 0xdeadbeefu),
-        gv(2 * CX * Lay<K>::W, 0xdeadbeefu), gd(2 * CX * Lay<K>::DW, 0xdeadbeefu), gsb(CX * Lay<K>::W, 0xdeadbeefu), gsa(CX * Lay<K>::DW, 0xdeadbeefu), gq(CMP_CACHE * 4, 0xdeadbeefu);
+    // one lane's blocks of LDS and of the spill area, laid out as the kernel's (walk.h); the node map (WALK_NODE_MAP builds) is the lane's
+    const WalkLayout lay{(uint32_t)K, C, CM > C ? CM - C : 1u, false, false, (CM + 1u + 3u) / 4u, 1u};
+    std::vector<uint32_t> lds(lay.lds_words() + 1u, 0xdeadbeefu), spill(lay.spill_words(), 0xdeadbeefu);
     Store st;
-    std::vector<uint32_t> nm((CM + 1u + 3u) / 4u + 1u, 0xdeadbeefu);      // WALK_NODE_MAP builds: the lane's node map
-    st.nm = reinterpret_cast<uint8_t*>(nm.data()); st.nm_words = (CM + 1u + 3u) / 4u;
-    st.lv = lv.data(); st.ld = ld.data(); st.sb = sb.data(); st.sa = sa.data(); st.gv = gv.data(); st.gd = gd.data(); st.gsb = gsb.data(); st.gsa = gsa.data(); st.gq = gq.data(); st.CI = C; st.C = C; st.CX = CX;
+    st.C = lay.C; st.CX = lay.CX; st.CI = lay.CI();
+    st.lv = &lds[lay.lv()]; st.ld = &lds[lay.ld()]; st.sb = &lds[lay.sb()]; st.sa = &lds[lay.sa()];
+    st.nm = reinterpret_cast<uint8_t*>(&lds[lay.nm()]); st.nm_words = lay.nm_words;
+    st.gv = &spill[lay.gv()]; st.gd = &spill[lay.gd()]; st.gsb = &spill[lay.gsb()]; st.gsa = &spill[lay.gsa()]; st.gq = &spill[lay.gq()];
     uint64_t rtc[MFA_RT_CACHED] = {0};
     SeqFeeder feed;
     feed.n = b.n;

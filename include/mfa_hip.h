@@ -145,10 +145,10 @@ int  mfa_match_batch_regions(mfa_image_t* img, const uint8_t* d_bytes, const uin
                              uint8_t* d_results, const uint64_t* d_table, int device, void* stream);
 
 /* ---- mixed batches --------------------------------------------------------------------------------
- * ONE batch whose strings belong to several memory automata, segment by segment (the 10-example attack
+ * ONE batch whose strings belong to several automata, segment by segment (the 10-example attack
  * corpus is one byte buffer, one offset array and ten segments).  Replaces: running the loop of
  * match.cpp:21-31 once per automaton.  A mixed object holds the automata's tables back to back, per
- * device; the images must outlive it, scan in the same direction and fit the table-driven walk
+ * device; the images must outlive it, and its memory automata scan in the same direction and fit the table-driven walk
  * (MFA_ERR_UNSUPPORTED otherwise).  One call runs the region pass over the batch in a few groups of
  * consecutive segments and walks each group -- all its automata in ONE launch, any lane any automaton --
  * as soon as its regions are known: the region launches go to `stream` itself, the walks to internal streams, so that
@@ -156,7 +156,24 @@ int  mfa_match_batch_regions(mfa_image_t* img, const uint8_t* d_bytes, const uin
  * behind it).  Calls on one object are ordered one behind the other, also when they come on different streams (the object's
  * table and work areas are shared).  `stream` sees the call as a single operation: it waits for the internal streams before the call
  * returns, ALSO when the call returns an error (whatever was started is ordered before the caller's next
- * operation on `stream`). */
+ * operation on `stream`).
+ *
+ * Memory-less automata (MFA_KIND_NFA) in a mixed object.  The images may be of either kind, in any order; a memory-less one may scan in
+ * either direction whatever the others do.  Memory-less segments have no use for regions: the region launches are clipped to the runs of
+ * memory segments (an object without a memory automaton launches none, and mfa_mixed_last_ms reports region_ms 0), and the memory-less
+ * segments are walked on an internal stream of their own, behind the call's entry only, beside the region launches.  With MFA_MIXED_DFA=1
+ * every segment whose table fits the tiled table kernel -- table plus input tile at most 64 KiB of LDS, up to 55 state sets -- shares ONE launch of
+ * dfa_mixed_kernel: any workgroup any automaton, a workgroup reloads its table only when the automaton changes.  Every other memory-less
+ * segment gets a launch of its own, exactly mfa_match_batch on its strings: larger tables, every memory-less segment when MFA_WALK=jit
+ * selects the per-segment schedule, and segments of MFA_MIXED_DFA_OWN strings or more (default 32768), for which a launch of their own is
+ * the better deal.  MFA_MIXED_DFA=0, the DEFAULT until the shared launch has been measured against the per-image calls (the 32768 is
+ * an estimate for the same reason), gives every memory-less segment its own launch.  Both are read per call.
+ * Inside the shared launch a string of MFA_DFA_SPLIT_MIN bytes or more is walked WHOLE by its lane -- the call then takes as long as that
+ * string; only launches of their own have the split path for long strings.  Such a corpus belongs in mfa_match_batch, or its segment in a
+ * launch of its own (MFA_MIXED_DFA_OWN).  Result bytes: 0 or 1; the shared launch answers a string beyond MFA_MAX_STRING_BYTES with 2 and
+ * does not walk it, a launch of its own answers what mfa_match_batch answers for that image.
+ * Nothing is read back and nothing is uploaded per call (the segments travel as kernel arguments), so a call stays legal inside a
+ * stream capture under the conditions above, once a first call has uploaded the tables.  mfa_mixed_last_dfa tells what the last call did. */
 typedef struct mfa_mixed mfa_mixed_t;
 int  mfa_mixed_create(mfa_image_t* const* images, uint32_t n_images, mfa_mixed_t** out);
 void mfa_mixed_destroy(mfa_mixed_t* mx);
@@ -185,6 +202,10 @@ int  mfa_mixed_timing(mfa_mixed_t* mx, int device, uint32_t back, float* region_
 /* what the last call on `device` launched (any pointer may be NULL): region launches, walk launches, groups of strings, and
  * gated, always 0 (kept for compatibility) */
 int  mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launches, uint32_t* walk_launches, uint32_t* groups, uint32_t* gated);
+/* what the last call on `device` did with its memory-less segments (any pointer may be NULL): launches of the multi-table kernel, launches of
+ * single segments, and the items (segments) and strings inside the multi-table launches.  The walk launches of mfa_mixed_last_launches are
+ * memory-automaton walks only.  Same locking and errors as mfa_mixed_last_launches. */
+int  mfa_mixed_last_dfa(mfa_mixed_t* mx, int device, uint32_t* multi_launches, uint32_t* own_launches, uint32_t* items, uint64_t* strings);
 
 /* The result vector of a batch as a bitmap: bit k % 8 of byte k / 8 of d_bitmap ((n + 7) / 8 bytes, device memory) = string k was accepted
  * (result code 1).  Asynchronous on `stream`.  What a process sends when the results of a batch sharded over several GPUs are gathered

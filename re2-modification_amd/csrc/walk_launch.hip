@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "dfa_mixed.h"
 #include "mfa_internal.h"
 #include "walk.h"
 
@@ -86,6 +87,9 @@ using namespace mfa;
 //   * generated kernels (default while they are the faster walk on small automata): one launch per segment, spread over a few walk
 //     streams by measured cost -- the first call on a device runs the walks one after the other and times them, later calls give
 //     each walk to the stream that can start it first (list scheduling with the groups' region times as release times).
+// Memory-less automata (MFA_KIND_NFA) need no regions: the region launches leave their strings out, and their segments are walked by the
+// table kernels on an internal stream of their own, behind the call's entry event only -- the eligible ones in ONE launch of
+// dfa_mixed_kernel (dfa_mixed.hip), the others in a launch each (walk_plan.h: plan_dfa_items).
 constexpr uint32_t MIX_TIMINGS = 32;      // (MIX_MAX_GROUPS, MIX_MAX_STREAMS, MIX_MAX_LAUNCHES: walk_plan.h)
 
 struct mfa_mixed {
@@ -94,6 +98,9 @@ struct mfa_mixed {
     std::vector<uint32_t>   block_at;       // word offset of image k's block
     uint32_t K = 1, max_live = 1;
     bool reversed = false, table_ok = true;
+    // memory-less automata: per image, 1 = memory-less; those among them the multi-table launch takes; their tables as that launch reads them
+    std::vector<uint8_t>    is_dfa, dfa_eligible, dfa_tables;
+    uint32_t n_mem = 0, n_dfa = 0;
     std::mutex mu;
     std::map<uint64_t, uint64_t> bytes_of;                     // string count of a batch -> its bytes (read back once, see mfa_match_mixed)
     struct Dev {
@@ -103,6 +110,9 @@ struct mfa_mixed {
         hipEvent_t ev_g[MIX_MAX_GROUPS] = {nullptr};           // group g's regions are known (timed)
         hipEvent_t ev_w[MIX_MAX_STREAMS] = {nullptr};          // end of a walk stream's work
         hipEvent_t ev_in = nullptr;
+        uint8_t* d_dfa = nullptr;                              // dfa_tables on this device (uploaded when a call first has items)
+        uint32_t last_dfa_multi = 0, last_dfa_own = 0, last_dfa_items = 0; uint64_t last_dfa_strings = 0;
+        bool no_regions[MIX_TIMINGS] = {false};                // a call of the ring that had nothing to scan
         // timing of the last MIX_TIMINGS calls (a ring): first region launch, end of the last region launch, end of the call
         hipEvent_t ev_r0[MIX_TIMINGS] = {nullptr}, ev_r1[MIX_TIMINGS] = {nullptr}, ev_end[MIX_TIMINGS] = {nullptr};
         uint64_t calls = 0;
@@ -130,23 +140,32 @@ int mfa_mixed_create(mfa_image_t* const* images, uint32_t n_images, mfa_mixed_t*
     for (uint32_t k = 0; k < n_images; k++) {
         mfa_image* img = images[k];
         if (!img) { delete mx; return MFA_ERR_INVALID_ARG; }
-        if (img->host.h.kind != MFA_KIND_MFA) { delete mx; return MFA_ERR_UNSUPPORTED; }      // memory automata (tabulated ones have no regions to share)
-        if (!img->walk_ok) mx->table_ok = false;
-        if (k == 0) mx->reversed = img->walk.reversed;
-        else if (mx->reversed != img->walk.reversed) mx->table_ok = false;                      // one scan direction per table launch
         mx->images.push_back(img);
+        const bool dfa = img->host.h.kind != MFA_KIND_MFA;                                      // (tabulated: no regions, no live lists; any direction)
+        mx->is_dfa.push_back(dfa ? 1 : 0);
+        mx->dfa_eligible.push_back(dfa && dfa_mixed_eligible(img->host) ? 1 : 0);
+        if (dfa) { mx->n_dfa++; continue; }
+        if (!img->walk_ok) mx->table_ok = false;
+        if (mx->n_mem++ == 0) mx->reversed = img->walk.reversed;
+        else if (mx->reversed != img->walk.reversed) mx->table_ok = false;                      // one scan direction per table launch
         mx->K = std::max(mx->K, img->walk.K);
         mx->max_live = std::max(mx->max_live, img->walk.max_live);
     }
     if (mx->table_ok)
         for (mfa_image* img : mx->images) {
             mx->block_at.push_back((uint32_t)mx->words.size());
+            if (img->host.h.kind != MFA_KIND_MFA) continue;      // (no block)
             if (mx->K > 6 && img->walk.K <= 6) {                  // a kernel for more than 6 cells reads 3-word edges
                 WalkTables wide;
                 if (build_walk_tables(img->host, wide, true) != MFA_OK) { mx->table_ok = false; break; }
                 mx->words.insert(mx->words.end(), wide.words.begin(), wide.words.end());
             } else mx->words.insert(mx->words.end(), img->walk.words.begin(), img->walk.words.end());
         }
+    if (mx->n_dfa) {
+        std::vector<const HostImage*> hosts;
+        for (mfa_image* img : mx->images) hosts.push_back(&img->host);
+        mx->dfa_tables = dfa_mixed_pack(hosts, mx->dfa_eligible);
+    }
     *out = mx;
     return MFA_OK;
 }
@@ -161,6 +180,7 @@ void mfa_mixed_destroy(mfa_mixed_t* mx) {
         for (hipStream_t w : d.ws) if (w) (void)hipStreamSynchronize(w);
         if (d.calls > 0) (void)hipEventSynchronize(d.ev_end[(d.calls - 1) % MIX_TIMINGS]);      // (region launches on a caller's stream)
         if (d.d_tables) (void)hipFree(d.d_tables);
+        if (d.d_dfa) (void)hipFree(d.d_dfa);
         if (d.d_regions) (void)hipFree(d.d_regions);
         for (uint32_t* p : d.d_spill) if (p) (void)hipFree(p);
         for (LeanHint& h : d.lean) lean_hint_free(h);
@@ -184,7 +204,7 @@ static int mixed_device(mfa_mixed* mx, int device, mfa_mixed::Dev** out) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     d.n_cus = prop.multiProcessorCount;
-    if (mx->table_ok) {
+    if (mx->table_ok && mx->n_mem) {
         HIP_TRY(hipMalloc((void**)&d.d_tables, mx->words.size() * 4));
         HIP_TRY(hipMemcpy(d.d_tables, mx->words.data(), mx->words.size() * 4, hipMemcpyHostToDevice));
     }
@@ -223,6 +243,8 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     // caller's stream -- and remembered (a later batch with the same count and other bytes gets the same grouping: a matter of speed only).
     const char* spec = getenv("MFA_MIXED_CUTS");
     uint64_t bytes = total_bytes;
+    const bool has_mem = mx->n_mem != 0;                      // (without a memory automaton nothing is grouped: the bytes are not needed)
+    if (!has_mem) { spec = nullptr; bytes = 1; }
     if (!spec && bytes == 0) {
         auto known = mx->bytes_of.find(n);
         if (known != mx->bytes_of.end()) bytes = known->second;
@@ -238,8 +260,8 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     }
     const std::vector<uint64_t> cut = plan_cuts(n, bytes, table, spec);
     const uint32_t ng = (uint32_t)cut.size() - 1;
-    const bool with_regions = regions_enabled();
-    const int NW = mixed_walk_streams(table);
+    const bool with_regions = regions_enabled() && has_mem;
+    const int NW = has_mem ? mixed_walk_streams(table) : 0;
 
     // One automaton, one group: exactly the single-automaton call (mfa_match_batch: region pass, then the walk, on the caller's stream, with the
     // engine that call would choose) -- the hops to the internal streams and back cost such a batch 0.03-0.06 ms and buy it nothing.  (Cutting a
@@ -255,7 +277,9 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         HIP_TRY(hipEventRecord(d->ev_end[slot1], cs));
         if (rc != MFA_OK) return rc;
         d->timed = true; d->calls++; d->ng_last = 1;
-        d->last_region_launches = with_regions ? 1u : 0u; d->last_walk_launches = 1; d->last_groups = 1;
+        d->last_region_launches = with_regions ? 1u : 0u; d->last_walk_launches = has_mem ? 1u : 0u; d->last_groups = 1;
+        d->no_regions[slot1] = !has_mem;
+        d->last_dfa_multi = 0; d->last_dfa_own = has_mem ? 0u : 1u; d->last_dfa_items = 0; d->last_dfa_strings = 0;
         return MFA_OK;
     }
 
@@ -264,9 +288,26 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     if (table) {
         std::vector<MixImage> imgs;
         for (uint32_t s = 0; s < ns; s++) imgs.push_back(MixImage{mx->images[s]->walk.K, mx->images[s]->walk.max_live, mx->block_at[s]});
-        plan = plan_table_launches(cut, seg_first, imgs, mx->K, (uint32_t)mx->words.size(), NW);
+        plan = plan_table_launches(cut, seg_first, imgs, mx->K, (uint32_t)mx->words.size(), NW, mx->n_dfa ? mx->is_dfa.data() : nullptr);
     }
     if (plan.size() > MIX_MAX_LAUNCHES) return MFA_ERR_UNSUPPORTED;      // (more runs of equal cell count than the object has launch slots: nothing was started)
+    // the memory-less segments: the items of the multi-table launch, and the segments with a launch of their own (walk_plan.h)
+    DfaPlan dfa;
+    if (mx->n_dfa) {
+        std::vector<DfaImage> di;
+        for (uint32_t s = 0; s < ns; s++)
+            di.push_back(DfaImage{mx->is_dfa[s] != 0, mx->dfa_eligible[s] != 0, mx->images[s]->host.h.is_reversed != 0,
+                                  mx->is_dfa[s] ? dfa_mixed_table_bytes(mx->images[s]->host) : 0u});
+        dfa = plan_dfa_items(seg_first, di, table, dfa_knobs());
+        if (!dfa.items.empty() && !d->d_dfa) {
+            HIP_TRY(hipMalloc((void**)&d->d_dfa, mx->dfa_tables.size()));
+            HIP_TRY(hipMemcpy(d->d_dfa, mx->dfa_tables.data(), mx->dfa_tables.size(), hipMemcpyHostToDevice));
+        }
+    }
+    const bool has_dfa = !dfa.items.empty() || !dfa.own.empty();
+    // the stream of the memory-less segments: one beyond the walk streams while the object may have one, else the last walk stream (they go first)
+    const int KD = has_dfa ? std::min(NW, (int)MIX_MAX_STREAMS - 1) : -1;
+    const int NS = std::max(NW, KD + 1);
     uint64_t* d_table = nullptr;
     if (with_regions) {
         rc = ctx_reserve((void**)&d->d_regions, &d->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
@@ -274,9 +315,9 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
         d_table = d->d_regions;
     }
     // which stream walks which segment (generated kernels): first call one after the other (timed), then by cost
-    const bool calibrating = !table && !d->calibrated;
+    const bool calibrating = !table && !d->calibrated && has_mem;
     const std::vector<int> where = !table && d->calibrated && d->ng_last == ng ? assign_streams(cut, seg_first, ns, d->ready, d->cost.data(), NW) : std::vector<int>(ns, 0);
-    for (int k = 0; k < NW; k++)
+    for (int k = 0; k < NS; k++)
         if (!d->ws[k]) HIP_TRY(hipStreamCreateWithFlags(&d->ws[k], hipStreamNonBlocking));
     const uint32_t slot_t = (uint32_t)(d->calls % MIX_TIMINGS);
     // ---- from here on work goes to the internal streams.  Whatever happens, the caller's stream is made to wait for all of it before this
@@ -293,14 +334,28 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
             if (hipEventRecord(d->ev_end[slot_t], cs) != hipSuccess) { err = MFA_ERR_HIP; (void)hipStreamSynchronize(cs); }
         }
         ~Join() { run(); }
-    } join{d, cs, NW, slot_t};
+    } join{d, cs, NS, slot_t};
     // (the object's buffers -- table, counters, spill areas -- are shared by its calls: a call starts behind the end of the one before it,
     // whichever stream that one came on)
     if (d->calls > 0 && d->last_cs != cs) HIP_TRY(hipStreamWaitEvent(cs, d->ev_end[(d->calls - 1) % MIX_TIMINGS], 0));      // (the walk streams start behind ev_in: below)
     d->last_cs = cs;
     HIP_TRY(hipEventRecord(d->ev_in, cs));
     join.started = true;
-    for (int k = 0; k < NW; k++) HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_in, 0));
+    for (int k = 0; k < NS; k++) HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_in, 0));
+    // the memory-less segments wait for nothing else: they run beside the region launches
+    uint32_t dfa_multi = 0;
+    if (has_dfa) {
+        join.used[KD] = true;
+        for (size_t i0 = 0; i0 < dfa.items.size(); i0 += kDfaMaxItems) {
+            rc = launch_dfa_mixed(dfa, i0, std::min(dfa.items.size(), i0 + kDfaMaxItems), d->d_dfa, d->n_cus, d_bytes, d_offsets, n, d_results, d->ws[KD]);
+            if (rc != MFA_OK) return rc;
+            dfa_multi++;
+        }
+        for (uint32_t s : dfa.own) {
+            rc = mfa_match_batch(mx->images[s], d_bytes, d_offsets + seg_first[s], seg_first[s + 1] - seg_first[s], d_results + seg_first[s], device, d->ws[KD]);
+            if (rc != MFA_OK) return rc;
+        }
+    }
     // The region launches go to the CALLER's stream: back-to-back calls pass from the last walk of one to the first region launch of the next
     // through ONE event (walk stream -> caller's stream) instead of three through a region stream of the object's own: 0.02 ms a call.
     HIP_TRY(hipEventRecord(d->ev_r0[slot_t], cs));
@@ -309,12 +364,32 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     for (uint32_t g = 0; g < ng; g++) {
         const uint64_t lo = cut[g], hi = cut[g + 1];
         // a group's event: the table engine's is its region launch's completion signal (no packet of its own between region launches)
-        if (with_regions) {
+        bool g_event = false;                                   // the group's event is its (last) region launch's completion signal
+        if (with_regions && !mx->n_dfa) {
             rc = launch_region_scan(d->n_cus, d_bytes, d_offsets + lo, hi - lo, d_table + lo * MFA_REGION_WORDS, cs, table ? 128u : 256u, table ? d->ev_g[g] : nullptr);
             if (rc != MFA_OK) return rc;
             region_launches++;
+            g_event = table;
+        } else if (with_regions) {
+            // an object with memory-less automata: one launch per run of memory segments in the group -- their strings are not scanned
+            uint32_t ra, rb;
+            segments_of(seg_first, ns, lo, hi, ra, rb);
+            std::vector<std::pair<uint64_t, uint64_t>> runs;
+            for (uint32_t s = ra; s < rb; s++) {
+                const uint64_t a = std::max(seg_first[s], lo), b = std::min(seg_first[s + 1], hi);
+                if (mx->is_dfa[s] || b <= a) continue;
+                if (!runs.empty() && runs.back().second == a) runs.back().second = b; else runs.emplace_back(a, b);
+            }
+            for (size_t r = 0; r < runs.size(); r++) {
+                const bool last = r + 1 == runs.size();
+                rc = launch_region_scan(d->n_cus, d_bytes, d_offsets + runs[r].first, runs[r].second - runs[r].first, d_table + runs[r].first * MFA_REGION_WORDS, cs,
+                                        table ? 128u : 256u, table && last ? d->ev_g[g] : nullptr);
+                if (rc != MFA_OK) return rc;
+                region_launches++;
+                g_event = table;
+            }
         }
-        if (!(with_regions && table)) HIP_TRY(hipEventRecord(d->ev_g[g], cs));
+        if (!g_event) HIP_TRY(hipEventRecord(d->ev_g[g], cs));
         // a stream's first launch of this group waits for the group's event
         bool waits[MIX_MAX_STREAMS] = {false};
         if (table) {
@@ -334,7 +409,7 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
             segments_of(seg_first, ns, lo, hi, sa, sb);
             for (uint32_t s = sa; s < sb; s++) {
                 const uint64_t a = std::max(seg_first[s], lo), b = std::min(seg_first[s + 1], hi);
-                if (b <= a) continue;
+                if (b <= a || mx->is_dfa[s]) continue;
                 const int k = where[s];
                 if (!waits[k]) { waits[k] = true; HIP_TRY(hipStreamWaitEvent(d->ws[k], d->ev_g[g], 0)); }
                 join.used[k] = true;
@@ -352,11 +427,13 @@ static int match_mixed_impl(mfa_mixed_t* mx, const uint8_t* d_bytes, const uint6
     d->calls++;
     d->ng_last = ng;
     d->last_region_launches = region_launches; d->last_walk_launches = slot; d->last_groups = ng;
+    d->no_regions[slot_t] = region_launches == 0 && mx->n_dfa != 0;
+    d->last_dfa_multi = dfa_multi; d->last_dfa_own = (uint32_t)dfa.own.size(); d->last_dfa_items = (uint32_t)dfa.items.size(); d->last_dfa_strings = dfa.strings;
     if (calibrating) {                                        // once per device: the walks' costs and the groups' region times
         HIP_TRY(hipEventSynchronize(d->ev_end[slot_t]));
         for (uint32_t s = 0; s < ns; s++) {
             float ms = 0.0f;
-            if (seg_first[s + 1] > seg_first[s] && mfa_last_kernel_ms(mx->images[s], device, &ms) == MFA_OK) d->cost[s] = ms;
+            if (seg_first[s + 1] > seg_first[s] && !mx->is_dfa[s] && mfa_last_kernel_ms(mx->images[s], device, &ms) == MFA_OK) d->cost[s] = ms;
         }
         for (uint32_t g = 0; g < ng; g++) {
             // the calibration pass runs a group's walks before the next group's region launch is reached by nothing: region launches
@@ -394,6 +471,20 @@ int mfa_mixed_last_launches(mfa_mixed_t* mx, int device, uint32_t* region_launch
     return MFA_OK;
 }
 
+// what the last call on `device` did with its memory-less segments (any pointer may be NULL): multi-table launches, launches of single
+// segments, and the items and strings of the multi-table launches
+int mfa_mixed_last_dfa(mfa_mixed_t* mx, int device, uint32_t* multi_launches, uint32_t* own_launches, uint32_t* items, uint64_t* strings) {
+    if (!mx) return MFA_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(mx->mu);
+    auto it = mx->dev.find(device);
+    if (it == mx->dev.end() || !it->second.timed) return MFA_ERR_INVALID_ARG;
+    if (multi_launches) *multi_launches = it->second.last_dfa_multi;
+    if (own_launches) *own_launches = it->second.last_dfa_own;
+    if (items) *items = it->second.last_dfa_items;
+    if (strings) *strings = it->second.last_dfa_strings;
+    return MFA_OK;
+}
+
 // The same with HOST pointers: copies the batch to the device, matches, copies the results back, synchronises (the host mirror's
 // match_mixed and the `diploma -match-mixed` command line; throughput is then bounded by the host link).
 int mfa_match_mixed_host(mfa_mixed_t* mx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, const uint64_t* seg_first, uint8_t* results, int device) {
@@ -413,7 +504,7 @@ int mfa_mixed_timing(mfa_mixed_t* mx, int device, uint32_t back, float* region_m
     mfa_mixed::Dev& d = it->second;
     const uint32_t k = (uint32_t)((d.calls - 1 - back) % MIX_TIMINGS);
     HIP_TRY(hipEventSynchronize(d.ev_end[k]));
-    if (region_ms) HIP_TRY(hipEventElapsedTime(region_ms, d.ev_r0[k], d.ev_r1[k]));
+    if (region_ms) { if (d.no_regions[k]) *region_ms = 0.0f; else HIP_TRY(hipEventElapsedTime(region_ms, d.ev_r0[k], d.ev_r1[k])); }
     if (span_ms) HIP_TRY(hipEventElapsedTime(span_ms, d.ev_r0[k], d.ev_end[k]));
     return MFA_OK;
 }

@@ -206,8 +206,10 @@ struct MixLaunch {
     int k;                                   // walk stream
     uint32_t sf[WALK_MAX_SEG + 1], stb[WALK_MAX_SEG];      // launch_walk's seg_first / seg_table
 };
+// no_walk: per segment, 1 = a memory-less automaton's (walked by the table kernels: plan_dfa_items below): no walk launch holds it, and a
+// run of segments ends in front of it.  nullptr: every segment is a memory automaton's.
 inline std::vector<MixLaunch> plan_table_launches(const std::vector<uint64_t>& cut, const uint64_t* seg_first, const std::vector<MixImage>& img, uint32_t K,
-                                                  uint32_t total_words, int NW) {
+                                                  uint32_t total_words, int NW, const uint8_t* no_walk = nullptr) {
     const uint32_t ns = (uint32_t)img.size();
     std::vector<MixLaunch> plan;
     for (uint32_t g = 0; g + 1 < cut.size(); g++) {
@@ -215,9 +217,10 @@ inline std::vector<MixLaunch> plan_table_launches(const std::vector<uint64_t>& c
         uint32_t sa, sb;
         segments_of(seg_first, ns, lo, hi, sa, sb);
         for (uint32_t s0 = sa; s0 < sb;) {
+            if (no_walk && no_walk[s0]) { s0++; continue; }
             uint32_t s1 = s0 + 1;
             const uint32_t Kc = K > 6 ? K : img[s0].K;
-            while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (K > 6 || img[s1].K == Kc)) s1++;
+            while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (K > 6 || img[s1].K == Kc) && !(no_walk && no_walk[s1])) s1++;
             MixLaunch L{};
             L.a = std::max(seg_first[s0], lo); L.b = std::min(seg_first[s1], hi);
             if (L.b > L.a) {
@@ -251,6 +254,57 @@ inline std::vector<int> assign_streams(const std::vector<uint64_t>& cut, const u
     return where;
 }
 
+// ---- the memory-less segments of a mixed call -----------------------------------------------------------------------------------------
+// They need no regions, so they are walked beside the region pass, behind the call's entry event only.  Segments whose table fits the
+// tiled table kernel's LDS ("eligible": kernels.hip, launch_dfa_walk's 64 KiB rule) share ONE launch of dfa_mixed_kernel (dfa_mixed.hip);
+// the others -- tables in L2, tables beyond 64 KiB with the tile, every memory-less segment of a call on the per-segment schedule
+// (MFA_WALK=jit), and segments so large that a launch of their own pays -- get a launch of their own through launch_dfa_walk.
+// An item is what the multi-table launch is given: one segment's strings.  The kernel cuts an item into slices of kDfaSliceStrings
+// strings, one per lane of a workgroup; a workgroup takes a run of consecutive slices (dfa_slice_lo).
+constexpr uint32_t kDfaSliceStrings = 256;      // one workgroup, one string per lane
+constexpr uint32_t kDfaMaxItems = 96;           // items per launch: they travel as kernel arguments (no upload, nothing that outlives the launch)
+// Neither default rests on a measurement yet (tools/mixed_dfa.py has not been run on an MI355X).  Until it has, the
+// multi-table launch is OFF unless MFA_MIXED_DFA=1 asks for it -- every memory-less segment then gets the launch mfa_match_batch gives it,
+// code whose speed is known -- and the size from which a segment leaves the multi-table launch is an estimate: 32768 strings of 1 KiB are
+// 32 MiB, about what one workgroup per CU-slot of the tiled kernel's own grid takes in one round.
+constexpr int      kDfaMultiDefault = 0;        // MFA_MIXED_DFA
+constexpr uint64_t kDfaOwnDefault = 32768;      // MFA_MIXED_DFA_OWN
+
+// slices of an item; the first slice of workgroup `wg` of `wgs` (its last: the next workgroup's first): consecutive slices, so that a
+// workgroup changes its table as seldom as possible
+constexpr uint64_t dfa_slices_of(uint64_t count) { return (count + kDfaSliceStrings - 1) / kDfaSliceStrings; }
+constexpr uint64_t dfa_slice_lo(uint64_t slices, uint64_t wg, uint64_t wgs) { return slices * wg / wgs; }
+
+struct DfaImage { bool memoryless, eligible, reversed; uint32_t table_bytes; };      // table_bytes: the fused LDS table (n_states * kDfaRow * 2)
+struct DfaItem { uint64_t first; uint32_t count, image; };                         // strings [first, first + count) of the batch, automaton `image`
+struct DfaKnobs { bool multi; uint64_t own_min; };
+inline DfaKnobs dfa_knobs() {
+    DfaKnobs k;
+    k.multi = env_int("MFA_MIXED_DFA", kDfaMultiDefault) != 0;      // 0: every memory-less segment gets its own launch; 1: the multi-table launch
+    const char* e = getenv("MFA_MIXED_DFA_OWN");              // strings from which a segment gets its own launch
+    k.own_min = e && *e ? strtoull(e, nullptr, 10) : kDfaOwnDefault;
+    return k;
+}
+struct DfaPlan {
+    std::vector<DfaItem> items;      // in segment order: slices of one automaton lie side by side
+    std::vector<uint32_t> own;       // segments with a launch of their own
+    uint32_t table_bytes = 0;        // the largest table of the items
+    uint64_t strings = 0, slices = 0;      // of the items
+};
+// table_schedule: the call walks its memory automata with the table engine (else every memory-less segment gets its own launch)
+inline DfaPlan plan_dfa_items(const uint64_t* seg_first, const std::vector<DfaImage>& img, bool table_schedule, const DfaKnobs& kn) {
+    DfaPlan P;
+    for (uint32_t s = 0; s < (uint32_t)img.size(); s++) {
+        const uint64_t cnt = seg_first[s + 1] - seg_first[s];
+        if (!img[s].memoryless || cnt == 0) continue;
+        if (!kn.multi || !table_schedule || !img[s].eligible || cnt >= kn.own_min || cnt > 0xffffffffull) { P.own.push_back(s); continue; }
+        P.items.push_back(DfaItem{seg_first[s], (uint32_t)cnt, s});
+        P.table_bytes = std::max(P.table_bytes, img[s].table_bytes);
+        P.strings += cnt;
+        P.slices += dfa_slices_of(cnt);
+    }
+    return P;
+}
 }  // namespace mfa
 
 #endif

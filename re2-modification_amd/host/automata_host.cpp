@@ -289,9 +289,14 @@ void MFA::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n
 vector<bool> MFA::match_batch(const vector<string>& strs) { return Automata::match_batch(strs); }
 
 vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs) {
+    return match_mixed(vector<Automata*>(automata.begin(), automata.end()), strs);
+}
+
+// automata of either kind, as compile() returns them (image_blob() is virtual: an MFA behind an Automata* gives its own image)
+vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector<vector<string>>& strs) {
     if (automata.empty() || automata.size() != strs.size()) throw std::runtime_error("match_mixed: one list of strings per automaton");
     vector<mfa_image_t*> images;
-    for (MFA* m : automata) images.push_back(m->image_for_match());
+    for (Automata* m : automata) images.push_back(m->image_for_match());
     mfa_mixed_t* mx = nullptr;
     int rc = mfa_mixed_create(images.data(), (uint32_t)images.size(), &mx);
     if (rc != MFA_OK) fail("mfa_mixed_create", rc);

@@ -115,7 +115,9 @@ public:
 #define MemoryState pair<int, pair<MemoryNode*, Memory>>
 
 class MFA;
+class Automata;
 vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs);
+vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector<vector<string>>& strs);
 
 class Automata {
 public:
@@ -150,7 +152,7 @@ public:
     int devices = 0;
 
 protected:
-    friend vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs);
+    friend vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector<vector<string>>& strs);
     mfa_image* image_for_match();
     mfa_image* cached_image_ = nullptr;
     vector<uint8_t> cached_blob_;

@@ -3,6 +3,7 @@
 //   diploma -match N                                          timing series over test/example_N (example_runner.cpp)
 //   diploma -dump  [-thompson|-glushkov|-mfa]                 regex token -> automaton image as text
 //   diploma -match-file <gt|mfa> <file>                       matchers/match_mfa.cpp counterparts
+//   diploma -match-mixed [-bnf|-reverse|-ssnf|-all] FILE...   one regex and its strings per file, all files in ONE device call
 #include <algorithm>
 #include <cstring>
 #include <fstream>
@@ -82,24 +83,47 @@ int main(int argc, char* argv[]) {
         if (argc > 2 && std::strcmp(argv[1], "-match-mixed") == 0) {
             // diploma -match-mixed FILE...: every file holds a regex (line 1) and strings (one per line); all of them are matched by
             // ONE device call; prints the 0/1 lines of file 1, then of file 2, ...
-            vector<MFA*> automata;
+            // diploma -match-mixed -bnf|-reverse|-ssnf|-all FILE...: each regex goes through compile() as in `-match` with these flags and is
+            // whichever kind compile() returns, with or without memory; a file's answers follow the lines compile() prints for it, as in `-match`; without a flag every regex becomes a memory automaton (toMFA)
+            bool bnf = false, reverse = false, ssnf = false, compiled = false;
+            int first = 2;
+            for (; first < argc && argv[first][0] == '-'; first++) {
+                const string flag = argv[first];
+                if (flag == "-all") bnf = reverse = ssnf = true;
+                else if (flag == "-bnf") bnf = true;
+                else if (flag == "-reverse") reverse = bnf = true;
+                else if (flag == "-ssnf") ssnf = true;
+                else { std::cerr << "diploma: -match-mixed: unknown flag " << flag << "\n"; return 1; }
+                compiled = true;
+            }
+            vector<Automata*> automata;
             vector<vector<string>> strs;
-            std::ostringstream sink;
-            for (int a = 2; a < argc; a++) {
+            vector<string> headers;                                  // with a flag: what compile() prints for a file goes in front of the file's answers, as in `-match`
+            for (int a = first; a < argc; a++) {
+                std::ostringstream sink;
                 std::ifstream f(argv[a]);
                 if (!f.is_open()) { cout << "ERROR\n"; return 1; }
                 string regex, line;
                 std::getline(f, regex);
                 std::streambuf* old = cout.rdbuf(sink.rdbuf());      // compile() prints its header lines
                 Regexp* re = Regexp::parse_regexp(regex);
-                re->is_backref_correct();
-                automata.push_back(re->to_binary_tree()->toMFA());
+                if (compiled) {
+                    bool is_mfa = false;
+                    automata.push_back(re->compile(is_mfa, reverse, bnf, ssnf));
+                } else {
+                    re->is_backref_correct();
+                    automata.push_back(re->to_binary_tree()->toMFA());
+                }
                 cout.rdbuf(old);
+                headers.push_back(compiled ? sink.str() : string());
                 strs.emplace_back();
                 while (std::getline(f, line)) strs.back().push_back(line);
             }
-            for (const auto& r : match_mixed(automata, strs))
-                for (bool b : r) cout << (b ? 1 : 0) << "\n";
+            const vector<vector<bool>> results = match_mixed(automata, strs);
+            for (size_t k = 0; k < results.size(); k++) {
+                cout << headers[k];
+                for (bool b : results[k]) cout << (b ? 1 : 0) << "\n";
+            }
             return 0;
         }
         if (argc > 3 && std::strcmp(argv[1], "-match-file") == 0) {

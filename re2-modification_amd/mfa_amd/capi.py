@@ -18,7 +18,7 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_match_batch_regions", "mfa_region_scan", "mfa_match_batch_host", "mfa_last_kernel_ms", "mfa_last_region_ms",
            "mfa_device_count", "mfa_last_hip_error", "mfa_strerror", "mfa_version",
            "mfa_mixed_create", "mfa_mixed_destroy", "mfa_match_mixed", "mfa_match_mixed_sized", "mfa_match_mixed_host", "mfa_mixed_last_ms", "mfa_mixed_timing",
-           "mfa_mixed_last_launches", "mfa_pack_result_bitmap", "mfa_last_dfa_split"]
+           "mfa_mixed_last_launches", "mfa_mixed_last_dfa", "mfa_pack_result_bitmap", "mfa_last_dfa_split"]
 
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
 
@@ -76,6 +76,8 @@ def lib():
         L.mfa_match_mixed.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, i32, vp]
         L.mfa_match_mixed_sized.argtypes = [vp, vp, vp, u64, u64, ctypes.POINTER(u64), vp, i32, vp]
         L.mfa_mixed_last_launches.argtypes = [vp, i32] + [ctypes.POINTER(ctypes.c_uint32)] * 4
+        if hasattr(L, "mfa_mixed_last_dfa"):              # (as above: an older build)
+            L.mfa_mixed_last_dfa.argtypes = [vp, i32] + [ctypes.POINTER(ctypes.c_uint32)] * 3 + [ctypes.POINTER(u64)]
         L.mfa_pack_result_bitmap.argtypes = [vp, u64, vp, vp]
         L.mfa_match_mixed_host.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, i32]
         L.mfa_mixed_last_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
@@ -186,7 +188,7 @@ class Image:
 
 
 class Mixed:
-    """A mixed-batch handle (mfa_mixed_t*): several memory automata matched against the segments of ONE batch."""
+    """A mixed-batch handle (mfa_mixed_t*): several automata, with or without memory, matched against the segments of ONE batch."""
 
     def __init__(self, images):
         self._images = list(images)                      # the images must outlive the handle
@@ -217,6 +219,12 @@ class Mixed:
         v = [ctypes.c_uint32() for _ in range(4)]
         _check(lib().mfa_mixed_last_launches(self._h, device, *[ctypes.byref(x) for x in v]), "mfa_mixed_last_launches")
         return {"region_launches": v[0].value, "walk_launches": v[1].value, "groups": v[2].value, "gated": bool(v[3].value)}
+
+    def last_dfa(self, device=0):
+        """what the last call did with its memory-less segments: {"multi_launches", "own_launches", "items", "strings"}"""
+        v = [ctypes.c_uint32() for _ in range(3)] + [ctypes.c_uint64()]
+        _check(lib().mfa_mixed_last_dfa(self._h, device, *[ctypes.byref(x) for x in v]), "mfa_mixed_last_dfa")
+        return {"multi_launches": v[0].value, "own_launches": v[1].value, "items": v[2].value, "strings": v[3].value}
 
     def last_ms(self, device=0, back=0):
         """(region launches, first region launch to last walk) of the call `back` calls ago (0 = the last one), in ms"""

@@ -119,6 +119,41 @@ int  mfa_image_specialize(mfa_image_t* img);
 int  mfa_match_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                      uint8_t* d_results, int device, void* stream);
 
+/* ---- strings in pieces (memory-less automata) -----------------------------------------------------
+ * The walk of a tabulated automaton (MFA_KIND_NFA) is a fold over the input and its whole state between two bytes is ONE number, the
+ * state set it is in.  The resume call takes that number in and hands it out, so a string may arrive in pieces -- a log in blocks, a
+ * file larger than device memory, a string beyond MFA_MAX_STRING_BYTES -- one call per round of pieces.
+ * Pointers, batch layout, the 16-byte read rule and asynchrony are those of the plain batch call above.  d_states: n words of device
+ * memory, read and written in place: on entry word k is the state string k has reached so far (MFA_DFA_STATE_START for its first
+ * piece), on return the state after this piece.  d_results may be NULL (a caller that wants the answer after the last piece only);
+ * otherwise results[k] is what the plain call would answer for the concatenation of the pieces given so far.
+ * The words are the image's plain state-set numbers.  They mean something only to images made from the same blob by the same build
+ * of this library: DO NOT STORE THEM, and do not carry them from one automaton to another.
+ * SCAN ORDER: pieces are given in the order the automaton scans.  For an image with is_reversed (mfa_image_info) that is from the
+ * END of the string: its LAST piece goes into the first call, its first piece into the last.
+ * Equivalence: cut a string into pieces anywhere, empty pieces included, and give them in scan order -- state and result byte are
+ * those of one call on the whole string; a call on whole strings with every word MFA_DFA_STATE_START answers byte for byte what the
+ * plain call answers.
+ * Errors on the device are sticky: a word on entry that names no state set of the image (MFA_DFA_STATE_INVALID among them), or a
+ * piece longer than MFA_MAX_STRING_BYTES, leaves MFA_DFA_STATE_INVALID and result 2, and so does every later call on that word.  The
+ * SUM of a string's pieces has no limit.  A string that enters dead (MFA_DFA_STATE_DEAD) leaves dead with result 0 and its bytes are
+ * not read.
+ * Every table form is covered (LDS up to 127 state sets, L2 up to MFA_MAX_DFA_STATES; MFA_DFA_KERNEL=packed has no resume form and
+ * takes the LDS table).  A piece of MFA_DFA_SPLIT_MIN bytes or more on an LDS-table image is cut across the GPU as described above --
+ * the fold starts from the string's word -- with the same knobs, the same quiet-workspace rule and the same report through
+ * the split-report call below; the call is legal inside a stream capture under the same conditions and re-entrant per (image, device, stream).
+ * MFA_ERR_UNSUPPORTED: a memory automaton (its state holds spans of the input; there is no number to hand over).
+ * MFA_ERR_INVALID_ARG: d_states is NULL.  Both are answered before the device is touched. */
+#define MFA_DFA_STATE_DEAD    0u           /* the empty set: absorbing, rejecting */
+#define MFA_DFA_STATE_START   1u           /* {start}: what a string's first piece is given */
+#define MFA_DFA_STATE_INVALID 0xffffffffu
+int  mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                            uint32_t* d_states, uint8_t* d_results, int device, void* stream);
+/* the same with HOST pointers (copy in, match, copy states and results out, synchronise); a piece beyond the limit is the sticky
+ * error above, not MFA_ERR_TOO_LONG */
+int  mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                                 uint32_t* states, uint8_t* results, int device);
+
 /* ---- region tables -------------------------------------------------------------------------------
  * Before a memory automaton walks a batch, one streaming pass over the batch (region_scan_kernel)
  * finds every string's periodic regions -- stretches with s[j] == s[j+q], q <= 8 -- and leaves them in
@@ -221,7 +256,7 @@ int  mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t
 /* Device-side time of the last match kernel launched through this image on
  * `device`, in milliseconds, measured with HIP events recorded on the launch stream
  * around the kernel alone (for a memory-less image: the table kernel and the plan, chunk and fold kernels of the split path
- * behind it).  Synchronises on the stop event. */
+ * behind it; a resume call is covered in the same way).  Synchronises on the stop event. */
 int  mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms);
 /* What the split path of the last match call on this image and device did (any pointer may be NULL):
  * strings it took, chunks it cut them into, the chunk size in bytes the device chose.

@@ -322,6 +322,63 @@ int mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t*
         return mfa_match_batch(img, d_bytes, d_off, n, d_res, device, nullptr); });
 }
 
+int mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
+                           uint8_t* d_results, int device, void* stream) {
+    if (!img || !d_offsets) return MFA_ERR_INVALID_ARG;
+    if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;      // a memory automaton's state holds spans of the input: nothing to hand over
+    if (!d_states) return MFA_ERR_INVALID_ARG;
+    if (n == 0) return MFA_OK;
+    std::lock_guard<std::mutex> lk(img->mu);
+    DeviceState* ds = nullptr;
+    int rc = device_prepare(img, device, &ds);
+    if (rc != MFA_OK) return rc;
+    LaunchCtx* cx = nullptr;
+    rc = ctx_acquire(*ds, stream, &cx);
+    if (rc != MFA_OK) return rc;
+    struct DoneGuard {                                          // as in match_impl
+        LaunchCtx* cx; void* stream;
+        ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
+    } done_guard{cx, stream};
+    img->last_kernel = MFA_KERNEL_TABLE;
+    return launch_dfa_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, d_states, d_results, stream);
+}
+
+// host pointers: stage the pieces and the states, match, copy states (and results, unless NULL) back, synchronise.  No length check
+// here: a piece beyond the limit is the device's sticky error, not a refused call.
+int mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint32_t* states, uint8_t* results,
+                                int device) {
+    if (!img || !offsets) return MFA_ERR_INVALID_ARG;
+    if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;
+    if (!states) return MFA_ERR_INVALID_ARG;
+    if (n == 0) return MFA_OK;
+    for (uint64_t k = 0; k < n; k++)
+        if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
+    int rc = check_device(device);
+    if (rc != MFA_OK) return rc;
+    const uint64_t total = offsets[n] - offsets[0];
+    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint32_t* d_st = nullptr; uint8_t* d_res = nullptr;
+    std::vector<uint64_t> rel(n + 1);
+    for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
+    hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_st, n * sizeof(uint32_t));
+    if (e == hipSuccess && results) e = hipMalloc((void**)&d_res, n);
+    if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_st, states, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+    if (rc == MFA_OK) rc = mfa_match_batch_resume(img, d_bytes, d_off, n, d_st, d_res, device, nullptr);
+    if (rc == MFA_OK) {
+        e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(states, d_st, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && results) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+    }
+    for (void* p : {(void*)d_bytes, (void*)d_off, (void*)d_st, (void*)d_res})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {
     if (!img || !ms) return MFA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(img->mu);

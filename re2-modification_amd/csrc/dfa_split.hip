@@ -132,6 +132,28 @@ dfa_chunk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__
 // One block per queued string; maps are stored in scan order, so both directions fold alike.  The string's maps come into LDS a tile at a time with loads whose addresses do not depend on any
 // state (so no global round trip waits for another), 256 >> lanes_log2 runs of the tile are composed side by side for every start
 // state, and lane 0 takes the string's state through the runs' maps: per tile, tile / runs + runs dependent LDS reads.
+// all 256 lanes of the block: the state string q reaches from st_in over its maps, left in *s_st (read it behind a barrier)
+__device__ __forceinline__ void fold_string(const SplitEntry* __restrict__ queue, uint32_t q, const uint8_t* __restrict__ maps, uint32_t lanes_log2,
+                                            uint32_t st_in, uint32_t* s_tile, uint8_t* s_runs, uint32_t* s_st) {
+    const uint32_t lanes = 1u << lanes_log2, runs = 256u >> lanes_log2, tile_maps = kFoldTileBytes >> lanes_log2;
+    const uint32_t r = threadIdx.x >> lanes_log2, j = threadIdx.x & (lanes - 1u);
+    const uint32_t first = queue[q].first, nc = queue[q].nc;
+    if (threadIdx.x == 0) *s_st = st_in;
+    for (uint32_t t0 = 0; t0 < nc; t0 += tile_maps) {
+        const uint32_t cnt = nc - t0 < tile_maps ? nc - t0 : tile_maps;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(maps + ((uint64_t)(first + t0) << lanes_log2));
+        __syncthreads();                                  // the tile's last readers are done
+        for (uint32_t w = threadIdx.x; w < (cnt << lanes_log2) / 4u; w += 256u) s_tile[w] = src[w];
+        __syncthreads();
+        const uint32_t per = split_fold_per(cnt, runs);
+        const uint32_t m0 = r * per < cnt ? r * per : cnt, m1 = m0 + per < cnt ? m0 + per : cnt;
+        s_runs[threadIdx.x] = (uint8_t)split_fold_run(reinterpret_cast<const uint8_t*>(s_tile), lanes, m0, m1, j + 1u);
+        __syncthreads();
+        if (threadIdx.x == 0) *s_st = split_fold_run(s_runs, lanes, 0u, runs, *s_st);
+    }
+    __syncthreads();
+}
+
 __global__ void __launch_bounds__(256)
 dfa_fold_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
                 const uint8_t* __restrict__ maps, uint32_t lanes_log2, uint8_t* __restrict__ results) {
@@ -140,25 +162,29 @@ dfa_fold_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restri
     __shared__ uint32_t s_tile[kFoldTileBytes / 4];
     __shared__ uint8_t s_runs[256];
     __shared__ uint32_t s_st;
-    const uint32_t lanes = 1u << lanes_log2, runs = 256u >> lanes_log2, tile_maps = kFoldTileBytes >> lanes_log2;
-    const uint32_t r = threadIdx.x >> lanes_log2, j = threadIdx.x & (lanes - 1u);
     for (uint32_t q = blockIdx.x; q < n_q; q += gridDim.x) {
-        const uint32_t first = queue[q].first, nc = queue[q].nc;
-        if (threadIdx.x == 0) s_st = 1u;                      // state 1 = {start}
-        for (uint32_t t0 = 0; t0 < nc; t0 += tile_maps) {
-            const uint32_t cnt = nc - t0 < tile_maps ? nc - t0 : tile_maps;
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(maps + ((uint64_t)(first + t0) << lanes_log2));
-            __syncthreads();                                  // the tile's last readers are done
-            for (uint32_t w = threadIdx.x; w < (cnt << lanes_log2) / 4u; w += 256u) s_tile[w] = src[w];
-            __syncthreads();
-            const uint32_t per = split_fold_per(cnt, runs);
-            const uint32_t m0 = r * per < cnt ? r * per : cnt, m1 = m0 + per < cnt ? m0 + per : cnt;
-            s_runs[threadIdx.x] = (uint8_t)split_fold_run(reinterpret_cast<const uint8_t*>(s_tile), lanes, m0, m1, j + 1u);
-            __syncthreads();
-            if (threadIdx.x == 0) s_st = split_fold_run(s_runs, lanes, 0u, runs, s_st);
-        }
-        __syncthreads();
+        fold_string(queue, q, maps, lanes_log2, 1u, s_tile, s_runs, &s_st);      // state 1 = {start}
         if (threadIdx.x == 0) results[queue[q].sid] = accept_tab[s_st];
+    }
+}
+
+// The fold of mfa_match_batch_resume: a queued string starts from its word of `states` (a state that walks: the main kernel queues no
+// other, dfa_resume.hip) and the state it reaches is written back there; results may be NULL.
+__global__ void __launch_bounds__(256)
+dfa_fold_resume_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
+                       const uint8_t* __restrict__ maps, uint32_t lanes_log2, uint32_t* __restrict__ states, uint8_t* __restrict__ results) {
+    const uint32_t n_q = hdr[SPLIT_H_STRINGS];
+    if (n_q == 0) return;
+    __shared__ uint32_t s_tile[kFoldTileBytes / 4];
+    __shared__ uint8_t s_runs[256];
+    __shared__ uint32_t s_st;
+    for (uint32_t q = blockIdx.x; q < n_q; q += gridDim.x) {
+        const uint64_t sid = queue[q].sid;
+        fold_string(queue, q, maps, lanes_log2, states[sid], s_tile, s_runs, &s_st);
+        if (threadIdx.x == 0) {
+            states[sid] = s_st;
+            if (results != nullptr) results[sid] = accept_tab[s_st];
+        }
     }
 }
 
@@ -224,7 +250,7 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
 
 template <bool REV>
 static int split_tail_dir(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
-                          uint8_t* d_results, hipStream_t s) {
+                          uint8_t* d_results, hipStream_t s, uint32_t* d_states) {
     hipLaunchKernelGGL(dfa_plan_kernel, dim3(1), dim3(kPlanThreads), 0, s, d_offsets, sl.args.hdr, sl.args.queue, sl.args.qcap, sl.arena_chunks,
                        sl.chunk_min, sl.map_cap, sl.args.seen);
     HIP_TRY(hipGetLastError());
@@ -239,17 +265,21 @@ static int split_tail_dir(const HostImage& img, DeviceState& ds, const SplitLaun
     hipLaunchKernelGGL(dfa_chunk_kernel<REV>, dim3(n_cus * (unsigned)per_cu), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_byte_class,
                        img.dfa_states, img.n_classes, d_bytes, d_offsets, (const uint32_t*)sl.args.hdr, sl.args.queue, sl.maps, sl.lanes_log2);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dfa_fold_kernel, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept, (const uint32_t*)sl.args.hdr,
-                       (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_results);
+    if (d_states != nullptr)
+        hipLaunchKernelGGL(dfa_fold_resume_kernel, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept, (const uint32_t*)sl.args.hdr,
+                           (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_states, d_results);
+    else
+        hipLaunchKernelGGL(dfa_fold_kernel, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept, (const uint32_t*)sl.args.hdr,
+                           (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_results);
     HIP_TRY(hipGetLastError());
     return MFA_OK;
 }
 
 int split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
-               uint8_t* d_results, void* stream) {
+               uint8_t* d_results, void* stream, uint32_t* d_states) {
     if (sl.args.hdr == nullptr) return MFA_OK;
-    return img.h.is_reversed ? split_tail_dir<true>(img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream)
-                             : split_tail_dir<false>(img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream);
+    return img.h.is_reversed ? split_tail_dir<true>(img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream, d_states)
+                             : split_tail_dir<false>(img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream, d_states);
 }
 
 }  // namespace mfa

@@ -124,8 +124,12 @@ struct SplitLaunch {
 };
 bool split_applies(const HostImage& img);
 int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+// d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
-                uint8_t* d_results, void* stream);
+                uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
+// dfa_resume.hip: the walk of launch_dfa_walk with every string's state read from and written to d_states; d_results may be NULL
+int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint32_t* d_states, uint8_t* d_results, void* stream);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

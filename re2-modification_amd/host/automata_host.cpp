@@ -177,8 +177,65 @@ extern "C" int diploma_partition_by_bytes(const uint64_t* offsets, uint64_t n, u
     return 0;
 }
 
+namespace {
+
+constexpr uint64_t kPieceBytes = 8ull << 20;      // pieces of a string beyond the device's per-call limit; a multiple of 16
+
+// piece r IN SCAN ORDER of the string [b, e) cut every kPieceBytes from the end the scan starts at; empty once the string is used up
+void piece_of(uint64_t b, uint64_t e, uint64_t r, bool reversed, uint64_t* lo, uint64_t* hi) {
+    const uint64_t len = e - b, skip = r * kPieceBytes < len ? r * kPieceBytes : len, take = len - skip < kPieceBytes ? len - skip : kPieceBytes;
+    if (reversed) { *hi = e - skip; *lo = *hi - take; }
+    else { *lo = b + skip; *hi = *lo + take; }
+}
+
+// the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call
+void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
+    uint64_t rounds = 1;
+    for (uint64_t k : which) rounds = std::max(rounds, (offsets[k + 1] - offsets[k] + kPieceBytes - 1) / kPieceBytes);
+    vector<uint32_t> states(which.size(), MFA_DFA_STATE_START);
+    vector<uint8_t> res(which.size()), stage;
+    vector<uint64_t> off(which.size() + 1);
+    for (uint64_t r = 0; r < rounds; r++) {
+        stage.clear();
+        off[0] = 0;
+        for (size_t j = 0; j < which.size(); j++) {
+            uint64_t lo, hi;
+            piece_of(offsets[which[j]], offsets[which[j] + 1], r, reversed, &lo, &hi);
+            stage.insert(stage.end(), bytes + lo, bytes + hi);
+            off[j + 1] = stage.size();
+        }
+        stage.resize(stage.size() + 16);
+        const int rc = mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), r + 1 == rounds ? res.data() : nullptr, device);
+        if (rc != MFA_OK) fail("mfa_match_batch_resume_host", rc);
+    }
+    for (size_t j = 0; j < which.size(); j++) results[which[j]] = res[j];
+}
+
+}  // namespace
+
 void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     mfa_image* img = image_for_match();
+    mfa_image_info info;
+    if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA) {
+        vector<uint64_t> longs;
+        for (uint64_t k = 0; k < n; k++)
+            if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) longs.push_back(k);
+        if (!longs.empty()) {
+            // the runs of shorter strings between them lie back to back in the caller's buffer: each takes the one call it always took
+            uint64_t from = 0;
+            for (size_t j = 0; j <= longs.size(); j++) {
+                const uint64_t to = j < longs.size() ? longs[j] : n;
+                if (to > from) match_packed_short(img, bytes, offsets + from, to - from, results + from);
+                from = to + 1;
+            }
+            match_in_pieces(img, info.is_reversed != 0, bytes, offsets, longs, results, device);
+            return;
+        }
+    }
+    match_packed_short(img, bytes, offsets, n, results);
+}
+
+void Automata::match_packed_short(mfa_image* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     // the devices of the node: all of them by default (north_star: "the string batch shards trivially across the 8 GPUs of one node")
     const int count = mfa_device_count();
     int want = devices;
@@ -223,6 +280,35 @@ bool Automata::match(const string& str) {
     uint8_t res = 0;
     match_packed(reinterpret_cast<const uint8_t*>(str.data()), off, 1, &res);
     return res != 0;
+}
+
+// ---- Automata::Stream -----------------------------------------------------------------------------------
+
+Automata::Stream::Stream(Automata& automata) : automata_(automata) { reset(); }
+
+void Automata::Stream::reset() {
+    state_ = MFA_DFA_STATE_START;
+    feed(string());                              // the answer for the empty text
+}
+
+void Automata::Stream::feed(const string& block) {
+    mfa_image* img = automata_.image_for_match();
+    mfa_image_info info;
+    int rc = mfa_image_get_info(img, &info);
+    if (rc != MFA_OK) fail("mfa_image_get_info", rc);
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(block.data());
+    vector<uint8_t> stage;
+    for (uint64_t r = 0; r == 0 || r * kPieceBytes < block.size(); r++) {
+        uint64_t lo, hi;
+        piece_of(0, block.size(), r, info.is_reversed != 0, &lo, &hi);
+        stage.assign(bytes + lo, bytes + hi);
+        stage.resize(stage.size() + 16);
+        const uint64_t off[2] = {0, hi - lo};
+        uint8_t res = 0;
+        rc = mfa_match_batch_resume_host(img, stage.data(), off, 1, &state_, &res, automata_.device);
+        if (rc != MFA_OK) fail("mfa_match_batch_resume_host", rc);
+        accepted_ = res == 1;
+    }
 }
 
 // ---- MFA ----------------------------------------------------------------------------------------------
@@ -302,8 +388,17 @@ vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector
     if (rc != MFA_OK) fail("mfa_mixed_create", rc);
     vector<uint64_t> off{0}, seg{0};
     vector<uint8_t> bytes;
-    for (const auto& list : strs) {
-        for (const string& s : list) { bytes.insert(bytes.end(), s.begin(), s.end()); off.push_back(bytes.size()); }
+    // a string of a memory-less automaton beyond the device's per-call limit stands in the batch as an empty one and is matched by itself, in pieces
+    vector<std::pair<size_t, const string*>> longs;      // (index in the batch, the string)
+    vector<Automata*> long_owner;
+    for (size_t k = 0; k < strs.size(); k++) {
+        mfa_image_info info;
+        const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA;
+        for (const string& s : strs[k]) {
+            if (memory_less && s.size() > MFA_MAX_STRING_BYTES) { longs.push_back({off.size() - 1, &s}); long_owner.push_back(automata[k]); }
+            else bytes.insert(bytes.end(), s.begin(), s.end());
+            off.push_back(bytes.size());
+        }
         seg.push_back(off.size() - 1);
     }
     bytes.resize(bytes.size() + 16);
@@ -312,6 +407,7 @@ vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector
     rc = mfa_match_mixed_host(mx, bytes.data(), off.data(), n, seg.data(), res.data(), automata[0]->device);
     mfa_mixed_destroy(mx);
     if (rc != MFA_OK) fail("mfa_match_mixed_host", rc);
+    for (size_t j = 0; j < longs.size(); j++) res[longs[j].first] = long_owner[j]->Automata::match(*longs[j].second);
     vector<vector<bool>> out;
     for (size_t k = 0; k < strs.size(); k++) out.emplace_back(res.begin() + seg[k], res.begin() + seg[k + 1]);
     return out;

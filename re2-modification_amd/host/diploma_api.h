@@ -135,7 +135,10 @@ public:
     void changeFinalState(Node* new_final);
     bool isDeterministic();
 
-    // reference automata.cpp:177-210, on the GPU (a batch of one)
+    // reference automata.cpp:177-210, on the GPU (a batch of one).  A memory-less automaton takes strings of any length: one beyond the
+    // device's per-call limit (MFA_MAX_STRING_BYTES) is cut into pieces of 8 MiB that go through mfa_match_batch_resume_host round by
+    // round, last piece first for a reversed automaton; match_batch, match_packed and the memory-less segments of match_mixed do the
+    // same, and the shorter strings of the batch take the one call they always took.  A memory automaton refuses such a string as before.
     bool match(const string& str);
     // the same for many strings in one launch; result[k] is what match(strs[k]) returns
     vector<bool> match_batch(const vector<string>& strs);
@@ -151,9 +154,26 @@ public:
     // fewer strings than twice the devices) go to `device` alone.  Environment: DIPLOMA_DEVICES=N overrides this field.
     int devices = 0;
 
+    // A memory-less automaton on text that arrives in blocks (a log, a file larger than memory): feed() the blocks in the order the
+    // automaton scans -- front to back, and for a reversed automaton (is_reversed) LAST block first -- and accepted() tells whether the
+    // text fed so far matches, what match() answers for the concatenation.  Every feed() is one device call (mfa_match_batch_resume_host);
+    // blocks of any size.  The automaton must outlive the stream and must not change while it is fed.  A memory automaton throws.
+    class Stream {
+    public:
+        explicit Stream(Automata& automata);
+        void feed(const string& block);
+        bool accepted() const { return accepted_; }
+        void reset();                           // back to the empty text
+    private:
+        Automata& automata_;
+        uint32_t  state_ = 0;                   // the state-set number the device hands back; meaningless outside this object
+        bool      accepted_ = false;
+    };
+
 protected:
     friend vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector<vector<string>>& strs);
     mfa_image* image_for_match();
+    void match_packed_short(mfa_image* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results);      // every string within the per-call limit
     mfa_image* cached_image_ = nullptr;
     vector<uint8_t> cached_blob_;
 };

@@ -1,6 +1,7 @@
 // `diploma` command line (reference main.cpp:9-87).
 //   diploma -match [-bnf] [-reverse] [-ssnf] [-all] [-log]    regex token, then string tokens until `exit`
 //   diploma -match N                                          timing series over test/example_N (example_runner.cpp)
+//   diploma -match-blocks N [-bnf] [-reverse] [-ssnf] [-all]  as -match for a memory-less regex, every token fed to an Automata::Stream N bytes at a time
 //   diploma -dump  [-thompson|-glushkov|-mfa]                 regex token -> automaton image as text
 //   diploma -match-file <gt|mfa> <file>                       matchers/match_mfa.cpp counterparts
 //   diploma -match-mixed [-bnf|-reverse|-ssnf|-all] FILE...   one regex and its strings per file, all files in ONE device call
@@ -130,6 +131,31 @@ int main(int argc, char* argv[]) {
             string regex;
             cin >> regex;
             if (std::strcmp(argv[2], "gt") == 0) match_gt(regex, argv[3]); else match_mfa(regex, argv[3]);
+            return 0;
+        }
+        if (argc > 2 && std::strcmp(argv[1], "-match-blocks") == 0) {
+            // text that arrives in blocks: compile() as in `-match`, then every token goes through an Automata::Stream in blocks of N bytes,
+            // in the order the automaton scans (a reversed one is fed the token's last block first); one 0/1 line per token
+            const size_t block = (size_t)std::strtoull(argv[2], nullptr, 10);
+            if (block == 0) { std::cerr << "diploma: -match-blocks: block size?\n"; return 1; }
+            set<string> flags;
+            for (int i = 3; i < argc; i++) flags.insert(argv[i]);
+            const bool all = flags.count("-all") != 0, reverse = all || flags.count("-reverse"), bnf = reverse || flags.count("-bnf"), ssnf = all || flags.count("-ssnf");
+            string regex, text;
+            cin >> regex;
+            bool is_mfa = false;
+            Automata* automata = Regexp::parse_regexp(regex)->compile(is_mfa, reverse, bnf, ssnf, false);
+            if (is_mfa) { std::cerr << "diploma: -match-blocks: the regex needs memory; only a memory-less automaton carries its state from block to block\n"; return 1; }
+            Automata::Stream stream(*automata);
+            while (cin >> text && text != "exit") {
+                stream.reset();
+                const size_t n_blocks = (text.size() + block - 1) / block;
+                for (size_t k = 0; k < n_blocks; k++) {
+                    const size_t j = automata->is_reversed ? n_blocks - 1 - k : k;
+                    stream.feed(text.substr(j * block, block));
+                }
+                cout << (stream.accepted() ? 1 : 0) << endl;
+            }
             return 0;
         }
         if (argc > 1 && std::strcmp(argv[1], "-match") == 0) {

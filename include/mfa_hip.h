@@ -106,8 +106,19 @@ int  mfa_image_specialize(mfa_image_t* img);
  * side by side for every start state, and the chunks' state maps are composed in scan order: the time of a call follows the bytes
  * in the batch.  The answers are the same.  All of it runs inside this call on `stream`, with no read-back and no wait, so the call
  * stays asynchronous and legal inside a stream capture (once a first call has allocated the workspace).
- * Limits: automata whose table lives in LDS, that is up to 127 state sets, both scan directions; larger tables (kept in L2) and
- * memory automata are matched as before whatever the lengths.  At most 16384 long strings per call are cut, the others are walked
+ * Limits: memory-less automata only, every table size, both scan directions; memory automata are matched as before whatever the lengths.
+ * "For every start state" holds for tables that live in LDS, up to 127 state sets.  A table kept in L2 (255 to MFA_MAX_DFA_STATES state
+ * sets) has too many states for that: every chunk is walked from ONE state -- the first chunk from the true one, the others from a guess,
+ * the state reached over the MFA_DFA_SPEC_LOOKBACK bytes (default 256) in front of the chunk from {start} or, if that walk dies, from a
+ * "home" state chosen per image -- then MFA_DFA_SPEC_ROUNDS launches (default 3, at most 8; fixed when the call is enqueued) walk again every
+ * chunk that was not started from what its predecessor ended in, and a last step follows each string's chunks from its true state and walks
+ * serially whatever still does not join up.  The answers are exact whatever the guesses were; an automaton whose state never converges (a
+ * counter such as (a^150)*) costs the time of the one-lane walk plus the rounds.  Both defaults are ESTIMATES until DESIGN.md section 4.8 has
+ * the sweep.  Each chunk then takes 12 bytes of the arena (about 2.5 MB per overlapping launch).  MFA_DFA_SPEC=0 turns this off for the large
+ * tables only.  mfa_last_dfa_spec tells what repairing cost.  For these tables a launch workspace starts in the quiet state described below:
+ * the first batch with a long string that a workspace (one per stream in use) meets is walked whole, as every such batch was before, and from
+ * its next call on long strings are cut, for good; MFA_DFA_SPLIT=2 cuts from the first call on.
+ * At most 16384 long strings per call are cut, the others are walked
  * whole.  The chunk size is chosen on the device: max(MFA_DFA_CHUNK (default 4096), round_up(bytes of the long strings / 131072, 16)),
  * so the maps fit a fixed arena (about 1.1 to 22 MB per overlapping launch, by the number of state sets) whatever the batch holds.
  * A launch workspace (one per stream in use) whose last four calls met no long string leaves the extra launches out; the first batch
@@ -139,9 +150,9 @@ int  mfa_match_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d
  * SUM of a string's pieces has no limit.  A string that enters dead (MFA_DFA_STATE_DEAD) leaves dead with result 0 and its bytes are
  * not read.
  * Every table form is covered (LDS up to 127 state sets, L2 up to MFA_MAX_DFA_STATES; MFA_DFA_KERNEL=packed has no resume form and
- * takes the LDS table).  A piece of MFA_DFA_SPLIT_MIN bytes or more on an LDS-table image is cut across the GPU as described above --
- * the fold starts from the string's word -- with the same knobs, the same quiet-workspace rule and the same report through
- * the split-report call below; the call is legal inside a stream capture under the same conditions and re-entrant per (image, device, stream).
+ * takes the LDS table).  A piece of MFA_DFA_SPLIT_MIN bytes or more is cut across the GPU as described above, whatever the table's size --
+ * on an LDS table the fold starts from the string's word, on an L2 table the piece's first chunk does -- with the same knobs, the same
+ * quiet-workspace rule and the same report through the split-report calls below; a word that is dead or in error is never cut; the call is legal inside a stream capture under the same conditions and re-entrant per (image, device, stream).
  * MFA_ERR_UNSUPPORTED: a memory automaton (its state holds spans of the input; there is no number to hand over).
  * MFA_ERR_INVALID_ARG: d_states is NULL.  Both are answered before the device is touched. */
 #define MFA_DFA_STATE_DEAD    0u           /* the empty set: absorbing, rejecting */
@@ -255,15 +266,20 @@ int  mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t
 
 /* Device-side time of the last match kernel launched through this image on
  * `device`, in milliseconds, measured with HIP events recorded on the launch stream
- * around the kernel alone (for a memory-less image: the table kernel and the plan, chunk and fold kernels of the split path
- * behind it; a resume call is covered in the same way).  Synchronises on the stop event. */
+ * around the kernel alone (for a memory-less image: the table kernel and the kernels of the split path behind it -- plan, chunk and
+ * fold, or for a table in L2 plan, chunk walk, repair rounds and resolve; a resume call is covered in the same way).  Synchronises on the stop event. */
 int  mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms);
 /* What the split path of the last match call on this image and device did (any pointer may be NULL):
  * strings it took, chunks it cut them into, the chunk size in bytes the device chose.
- * All 0 when the path did not run (no long string, a memory automaton, a table in L2, MFA_DFA_SPLIT=0, or a call
+ * All 0 when the path did not run (no long string, a memory automaton, MFA_DFA_SPLIT=0, a table in L2 with MFA_DFA_SPEC=0, or a call
  * that left the split launches out because its workspace had met no long string lately).
  * Synchronises on that call's last event and reads the figures back with a blocking copy, holding the image's lock: for tests and tools. */
 int  mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes);
+/* What repairing the guesses cost in the last match call on this image and device, for a table in L2 (any pointer may be NULL): chunks
+ * walked again by the repair rounds, strings whose chunks still did not join up so that the last step walked their rest serially, and the
+ * bytes walked that way.  All 0 when that path did not run (see above; an LDS table has no guesses).  Same locking, synchronisation and
+ * errors as mfa_last_dfa_split. */
+int  mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, uint64_t* serial_strings, uint64_t* serial_bytes);
 /* Device-side time of the region pass of that launch (0 if it ran none). */
 int  mfa_last_region_ms(mfa_image_t* img, int device, float* ms);
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "mfa_internal.h"
+#include "dfa_spec_core.h"
 
 namespace mfa {
 
@@ -77,7 +78,7 @@ int ctx_acquire(DeviceState& ds, void* stream, LaunchCtx** out) {
         ds.ctxs.push_back(cx);
         pick = cx;
     }
-    pick->used = true; pick->stream = stream; pick->ran_regions = false; pick->split_ran = false;
+    pick->used = true; pick->stream = stream; pick->ran_regions = false; pick->split_ran = false; pick->spec_ran = false;
     ds.last = pick;
     *out = pick;
     return MFA_OK;
@@ -179,6 +180,7 @@ int mfa_image_create(const void* blob, size_t n_bytes, mfa_image_t** out) {
     int rc = parse_blob(blob, n_bytes, img->host);
     if (rc == MFA_OK) rc = img->host.h.kind == MFA_KIND_MFA ? check_mfa_invariants(img->host) : tabulate_nfa(img->host);
     if (rc != MFA_OK) { delete img; return rc; }
+    if (spec_applies(img->host)) img->host.dfa_home = spec_home_state(img->host.dfa_trans.data(), img->host.dfa_states, img->host.n_classes);
     if (img->host.h.kind == MFA_KIND_MFA) {
         img->walk_ok = build_walk_tables(img->host, img->walk) == MFA_OK;
         if (!img->walk_ok && !jit_enabled(img->host)) { delete img; return MFA_ERR_UNSUPPORTED; }      // no kernel could walk it
@@ -406,6 +408,24 @@ int mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t
     if (strings) *strings = h[SPLIT_H_STRINGS];
     if (chunks) *chunks = h[SPLIT_H_CHUNKS];
     if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
+    return MFA_OK;
+}
+
+int mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, uint64_t* serial_strings, uint64_t* serial_bytes) {
+    if (!img) return MFA_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(img->mu);
+    auto it = img->dev.find(device);
+    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
+    LaunchCtx& cx = *it->second.last;
+    uint32_t h[SPLIT_H_WORDS] = {0};
+    if (cx.spec_ran) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_done));
+        HIP_TRY(hipMemcpy(h, cx.d_split, sizeof h, hipMemcpyDeviceToHost));
+    }
+    if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
+    if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
+    if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
     return MFA_OK;
 }
 

@@ -7,7 +7,8 @@
 //   dfa_resume_big_kernel     table in global memory, resident in L2 (up to 2^20 state sets)
 // The SGPR-packed form of dfa_tiled_kernel (MFA_DFA_KERNEL=packed) has no resume twin: such a call takes the LDS form.
 // A piece of split_min bytes or more on an LDS table is queued for the split path exactly as in kernels.hip (split_take); the fold
-// behind it (dfa_split.hip: dfa_fold_resume_kernel) starts from the string's word and writes word and result.
+// behind it (dfa_split.hip: dfa_fold_resume_kernel) starts from the string's word and writes word and result.  On an L2 table the launcher
+// takes dfa_spec.hip's twin of dfa_resume_big_kernel, which queues such pieces for the kernels of that file.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -166,8 +167,17 @@ static int launch_resume_dir(const HostImage& img, DeviceState& ds, LaunchCtx& c
     if (blocks == 0) blocks = 1;
     if ((size_t)img.dfa_states * kDfaRow > 0xffffu) {                               // beyond 16-bit pre-multiplied states: table in L2
         if (blocks > (uint64_t)ds.n_cus * 8) blocks = (uint64_t)ds.n_cus * 8;
-        cx.split_ran = false;
+        SplitLaunch sl;                                                              // long pieces: dfa_spec.hip, as in kernels.hip
+        int rc = spec_begin(img, cx, n, s, &sl);
+        if (rc != MFA_OK) return rc;
         HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
+        if (sl.args.split_min != 0u) {
+            rc = spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, d_states, (unsigned)blocks);
+            if (rc == MFA_OK) rc = spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
+            if (rc != MFA_OK) return rc;
+            HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
+            return MFA_OK;
+        }
         if (img.dfa_states <= 0xffffu)
             hipLaunchKernelGGL((dfa_resume_big_kernel<REV, uint16_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,
                                ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results);

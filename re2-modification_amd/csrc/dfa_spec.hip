@@ -1,0 +1,273 @@
+// Long strings of memory-less automata whose table is walked in L2 (255 to 2^20 state sets: dfa_big_kernel's), cut across the whole GPU
+// (gfx950).  dfa_split.hip walks every chunk from every start state; that is out of the question here, so every chunk is walked from
+// ONE state -- a guess -- and wrong guesses are repaired a bounded number of times, then resolved exactly (dfa_spec_core.h has the scheme
+// and is checked on the CPU: tests/emul).  Queue, plan, chunk geometry, knobs and the quiet-workspace rule are dfa_split.hip's:
+//   memset(header) -> dfa_spec_big_kernel (queues long strings: split_take) -> dfa_plan_kernel -> dfa_spec_walk_kernel
+//     -> MFA_DFA_SPEC_ROUNDS x dfa_spec_repair_kernel -> dfa_spec_resolve_kernel
+// all on the caller's stream, with no read-back; the number of launches is fixed when the call is enqueued.  Successive launches on one
+// stream are the only ordering: no kernel here spins or waits for another workgroup, every loop is bounded by a chunk's or a string's bytes.
+// Records: per chunk start_used and TWO end words.  Repair round r reads the ends round r - 1 left in end[(r - 1) & 1] and writes every
+// chunk's end to end[r & 1] (walked again, or copied), so no lane reads a word another lane of the same launch writes; start_used[c]
+// is read and written by the lane of chunk c alone.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "mfa_internal.h"
+#include "dfa_spec_core.h"
+
+namespace mfa {
+
+// ---- main kernels: dfa_big_kernel and dfa_resume_big_kernel with the queue ------------------------------------
+// One string per lane, table in global memory, byte classes in LDS; both walk with resume_piece_big.  A string of sp.split_min bytes or more
+// is handed to the kernels below (split_take); with sp.hdr == NULL (quiet workspace) the lane walks it and split_take reports it.
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
+                    const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results, const SplitArgs sp) {
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
+        const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        if (sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // queued: dfa_spec_resolve_kernel writes results[sid]
+        results[sid] = accept_tab[resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, b, e, 1u)];
+    }
+}
+
+// Dead and invalid words are never queued (their bytes are not read), an over-long piece is the sticky error: dfa_resume.hip's rules.
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_resume_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_states,
+                           uint32_t n_classes, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
+                           uint32_t* __restrict__ states, uint8_t* __restrict__ results, const SplitArgs sp) {
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
+        const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        uint32_t st = resume_enter(states[sid], n_states, e - b);
+        const bool walks = resume_walks(st);
+        if (walks && sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // word and result are the resolve kernel's
+        if (walks) st = resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, b, e, st);
+        states[sid] = st;
+        if (results != nullptr) results[sid] = resume_result(accept_tab, st);
+    }
+}
+
+// ---- chunks ------------------------------------------------------------------------------------------
+struct SpecChunk { uint32_t q, k; uint64_t b, e, lo, hi; };     // chunk k (scan order) of queued string q = [b, e): the bytes [lo, hi)
+
+// the string of arena chunk c: the last queue entry with first <= c (c < the plan's chunk count, n_q >= 1)
+template <bool REV>
+__device__ __forceinline__ SpecChunk spec_chunk(const SplitEntry* __restrict__ queue, uint32_t n_q, const uint64_t* __restrict__ offsets, uint32_t chunk, uint32_t c) {
+    uint32_t lo = 0u, hi = n_q;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (queue[mid].first <= c) lo = mid; else hi = mid;
+    }
+    SpecChunk r;
+    r.q = lo; r.k = c - queue[lo].first;
+    const uint64_t sid = queue[lo].sid;
+    r.b = offsets[sid]; r.e = offsets[sid + 1u];
+    split_chunk_range<REV>(r.b, r.e, chunk, queue[lo].nc, r.k, &r.lo, &r.hi);
+    return r;
+}
+
+// Round 0, one lane per chunk: chunk 0 of a string from its true state (1, or its word of `states`), every other from a guess.
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_walk_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ byte_class, uint32_t n_classes, const uint8_t* __restrict__ bytes,
+                     const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
+                     uint32_t* __restrict__ start_used, uint32_t* __restrict__ end0, const uint32_t* __restrict__ states, uint32_t home, uint32_t lookback) {
+    const uint32_t n_chunks = hdr[SPLIT_H_CHUNKS];
+    if ((uint64_t)blockIdx.x * blockDim.x >= n_chunks) return;      // (no long string: every block leaves here)
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    const uint32_t chunk = hdr[SPLIT_H_CHUNK], n_q = hdr[SPLIT_H_STRINGS];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += stride) {
+        const SpecChunk ch = spec_chunk<REV>(queue, n_q, offsets, chunk, (uint32_t)c);
+        uint32_t st;
+        if (ch.k == 0u) st = states != nullptr ? states[queue[ch.q].sid] : 1u;
+        else {
+            uint64_t from, to;
+            spec_lookback_range<REV>(ch.b, ch.e, ch.lo, ch.hi, lookback, &from, &to);
+            st = spec_guess<REV, T>(trans, s_class, n_classes, bytes, from, to, home);
+        }
+        start_used[c] = st;
+        end0[c] = resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, ch.lo, ch.hi, st);
+    }
+}
+
+// One repair round, one lane per chunk: walked again from what its predecessor ended in, if that is not what it was walked from.
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_repair_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ byte_class, uint32_t n_classes, const uint8_t* __restrict__ bytes,
+                       const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
+                       uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_prev, uint32_t* __restrict__ end_next) {
+    const uint32_t n_chunks = hdr[SPLIT_H_CHUNKS];
+    if ((uint64_t)blockIdx.x * blockDim.x >= n_chunks) return;
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    const uint32_t chunk = hdr[SPLIT_H_CHUNK], n_q = hdr[SPLIT_H_STRINGS];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += stride) {
+        const SpecChunk ch = spec_chunk<REV>(queue, n_q, offsets, chunk, (uint32_t)c);
+        const uint32_t used = start_used[c], prev = ch.k != 0u ? end_prev[c - 1u] : used;
+        if (!spec_needs_rewalk(ch.k, used, prev)) { end_next[c] = end_prev[c]; continue; }
+        start_used[c] = prev;
+        end_next[c] = resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, ch.lo, ch.hi, prev);
+        atomicAdd(&hdr[SPEC_H_REWALKED], 1u);
+    }
+}
+
+// ---- resolve -----------------------------------------------------------------------------------------
+// One lane per queued string: the state it reaches from st over its records, walking the rest serially where they do not join up.
+template <bool REV, class T>
+__device__ __forceinline__ uint32_t spec_resolve_string(const T* __restrict__ trans, const uint8_t* s_class, uint32_t n_classes, const uint8_t* __restrict__ bytes,
+                                                        const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
+                                                        uint32_t q, const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin, uint32_t st) {
+    const uint32_t first = queue[q].first, nc = queue[q].nc;
+    const uint32_t c = spec_resolve(start_used + first, end_fin + first, nc, &st);
+    if (c < nc) {
+        const uint64_t sid = queue[q].sid, b = offsets[sid], e = offsets[sid + 1u];
+        uint64_t lo, hi, from, to;
+        split_chunk_range<REV>(b, e, hdr[SPLIT_H_CHUNK], nc, c, &lo, &hi);
+        spec_rest_range<REV>(b, e, lo, hi, &from, &to);
+        st = resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, from, to, st);
+        atomicAdd(&hdr[SPEC_H_SERIAL_STRINGS], 1u);
+        atomicAdd(reinterpret_cast<unsigned long long*>(&hdr[SPEC_H_SERIAL_BYTES]), (unsigned long long)(to - from));
+    }
+    return st;
+}
+
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_resolve_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
+                        const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
+                        const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin, uint8_t* __restrict__ results) {
+    const uint32_t n_q = hdr[SPLIT_H_STRINGS];
+    if ((uint64_t)blockIdx.x * blockDim.x >= n_q) return;
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_q; q += gridDim.x * blockDim.x)
+        results[queue[q].sid] = accept_tab[spec_resolve_string<REV, T>(trans, s_class, n_classes, bytes, offsets, hdr, queue, q, start_used, end_fin, 1u)];
+}
+
+// mfa_match_batch_resume: from the string's word (a state that walks: the main kernel queues no other), which gets the state reached
+template <bool REV, class T>
+__global__ void __launch_bounds__(256)
+dfa_spec_resolve_resume_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
+                               const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr,
+                               const SplitEntry* __restrict__ queue, const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin,
+                               uint32_t* __restrict__ states, uint8_t* __restrict__ results) {
+    const uint32_t n_q = hdr[SPLIT_H_STRINGS];
+    if ((uint64_t)blockIdx.x * blockDim.x >= n_q) return;
+    __shared__ uint8_t s_class[256];
+    s_class[threadIdx.x] = byte_class[threadIdx.x];
+    __syncthreads();
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_q; q += gridDim.x * blockDim.x) {
+        const uint64_t sid = queue[q].sid;
+        const uint32_t st = spec_resolve_string<REV, T>(trans, s_class, n_classes, bytes, offsets, hdr, queue, q, start_used, end_fin, states[sid]);
+        states[sid] = st;
+        if (results != nullptr) results[sid] = accept_tab[st];
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------
+bool spec_applies(const HostImage& img) {
+    // the tables launch_dfa_walk and launch_dfa_resume give the L2 kernels: beyond 16-bit pre-multiplied states, 255 state sets and more
+    // (split_applies has those up to 127; 128 to 254 are outside both, as they are outside mfa_match_batch)
+    return img.h.kind == MFA_KIND_NFA && (size_t)img.dfa_states * kDfaRow > 0xffffu;
+}
+
+// arena: start_used[map_cap], end[2][map_cap]
+static constexpr size_t kSpecWordsPerChunk = 3;
+
+int spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
+    *out = SplitLaunch{};
+    cx.split_ran = false;
+    cx.spec_ran = false;
+    const char* on = getenv("MFA_DFA_SPEC");
+    if ((on && on[0] == '0') || !spec_applies(img)) return MFA_OK;
+    uint64_t rounds = env_u64("MFA_DFA_SPEC_ROUNDS", kSpecRounds), lookback = env_u64("MFA_DFA_SPEC_LOOKBACK", kSpecLookback);
+    out->spec_rounds = (uint32_t)(rounds > kSpecRoundsMax ? kSpecRoundsMax : rounds);
+    out->spec_lookback = (uint32_t)(lookback > MFA_MAX_STRING_BYTES ? MFA_MAX_STRING_BYTES : lookback);
+    // A workspace starts QUIET here: until it has met a long string once (the twin main kernel then writes 3 to the pinned word) it launches the
+    // main kernel alone, so traffic of short strings never pays for the seven launches behind it, and the first batch with long strings on
+    // a workspace is walked whole, as it was before this path existed; from the next call on the workspace keeps the tail for good.
+    // MFA_DFA_SPLIT=2 launches the tail from the first call on.
+    const int rc = split_begin_arena(cx, n, stream, out, kSpecWordsPerChunk * sizeof(uint32_t), true);
+    cx.spec_ran = cx.split_ran;
+    return rc;
+}
+
+template <bool REV, class T>
+static int spec_main_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                        uint8_t* d_results, hipStream_t s, uint32_t* d_states, unsigned blocks) {
+    if (d_states != nullptr)
+        hipLaunchKernelGGL((dfa_spec_resume_big_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
+                           img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results, sl.args);
+    else
+        hipLaunchKernelGGL((dfa_spec_big_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
+                           img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
+    HIP_TRY(hipGetLastError());
+    return MFA_OK;
+}
+
+template <bool REV, class T>
+static int spec_tail_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                        uint8_t* d_results, hipStream_t s, uint32_t* d_states) {
+    const int rc = split_plan(sl, d_offsets, s);
+    if (rc != MFA_OK) return rc;
+    const T* trans = (const T*)ds.d_dfa_trans;
+    uint32_t* start_used = reinterpret_cast<uint32_t*>(sl.maps);
+    uint32_t* end[2] = {start_used + sl.map_cap, start_used + 2u * (size_t)sl.map_cap};
+    // one lane per chunk, the chunk count is the plan's: a grid for every chunk the arena holds, blocks beyond the count leave at once
+    const unsigned n_cus = (unsigned)(ds.n_cus > 0 ? ds.n_cus : 256);
+    unsigned blocks = (sl.map_cap + 255u) / 256u;
+    if (blocks > n_cus * 8u) blocks = n_cus * 8u;
+    hipLaunchKernelGGL((dfa_spec_walk_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
+                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, end[0], (const uint32_t*)d_states, img.dfa_home, sl.spec_lookback);
+    HIP_TRY(hipGetLastError());
+    for (uint32_t r = 1; r <= sl.spec_rounds; r++) {
+        hipLaunchKernelGGL((dfa_spec_repair_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
+                           sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, (const uint32_t*)end[(r - 1u) & 1u], end[r & 1u]);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t* end_fin = end[sl.spec_rounds & 1u];
+    const unsigned q_blocks = (sl.args.qcap + 255u) / 256u;
+    if (d_states != nullptr)
+        hipLaunchKernelGGL((dfa_spec_resolve_resume_kernel<REV, T>), dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes,
+                           d_bytes, d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_states, d_results);
+    else
+        hipLaunchKernelGGL((dfa_spec_resolve_kernel<REV, T>), dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes,
+                           d_bytes, d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_results);
+    HIP_TRY(hipGetLastError());
+    return MFA_OK;
+}
+
+#define MFA_SPEC_DISPATCH(FN, ...)                                                                                  \
+    (img.h.is_reversed ? (img.dfa_states <= 0xffffu ? FN<true, uint16_t>(__VA_ARGS__) : FN<true, uint32_t>(__VA_ARGS__))  \
+                       : (img.dfa_states <= 0xffffu ? FN<false, uint16_t>(__VA_ARGS__) : FN<false, uint32_t>(__VA_ARGS__)))
+
+int spec_main(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+              uint8_t* d_results, void* stream, uint32_t* d_states, unsigned blocks) {
+    return MFA_SPEC_DISPATCH(spec_main_go, img, ds, sl, d_bytes, d_offsets, n, d_results, (hipStream_t)stream, d_states, blocks);
+}
+
+int spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+              uint8_t* d_results, void* stream, uint32_t* d_states) {
+    if (sl.args.hdr == nullptr) return MFA_OK;
+    return MFA_SPEC_DISPATCH(spec_tail_go, img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream, d_states);
+}
+
+#undef MFA_SPEC_DISPATCH
+
+}  // namespace mfa

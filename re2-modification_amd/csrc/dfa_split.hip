@@ -189,7 +189,7 @@ dfa_fold_resume_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-static uint64_t env_u64(const char* name, uint64_t dflt) {
+uint64_t env_u64(const char* name, uint64_t dflt) {
     const char* e = getenv(name);
     if (!e || !*e) return dflt;
     char* end = nullptr;
@@ -204,9 +204,19 @@ bool split_applies(const HostImage& img) {
 int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
     *out = SplitLaunch{};
     cx.split_ran = false;
+    cx.spec_ran = false;
+    if (!split_applies(img)) return MFA_OK;
+    out->lanes_log2 = split_lanes_log2(img.dfa_states);
+    return split_begin_arena(cx, n, stream, out, (size_t)1 << out->lanes_log2, false);
+}
+
+// What split_begin and spec_begin (dfa_spec.hip) share: the knobs, the quiet-workspace rule, queue and arena -- `per_chunk` bytes of arena for
+// each of the map_cap chunks the plan can hand out -- and the zeroed header.  *out is the caller's, cleared but for what it has set itself.
+// start_quiet: a workspace counts as quiet from its first call on, not after kSplitQuietCalls calls without a long string (dfa_spec.hip).
+int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet) {
     const char* on = getenv("MFA_DFA_SPLIT");
     // (n < 2^31: the queue counter is a 32-bit word that every long string increments, also when the queue is full; it must not wrap)
-    if ((on && on[0] == '0') || !split_applies(img) || n >= 0x80000000ull) return MFA_OK;
+    if ((on && on[0] == '0') || n >= 0x80000000ull) return MFA_OK;
     uint64_t split_min = env_u64("MFA_DFA_SPLIT_MIN", kSplitMinDefault);
     if (split_min == 0) split_min = 1;
     out->args.split_min = split_min;
@@ -224,7 +234,7 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
         const uint32_t seen = *(volatile uint32_t*)cx.split_seen;
         if (seen == 3u) cx.split_keep = true;
         cx.split_quiet = seen == 1u ? cx.split_quiet + 1u : 0u;
-        if (!cx.split_keep && cx.split_quiet >= kSplitQuietCalls && !(on && on[0] == '2')) return MFA_OK;      // args.hdr stays NULL: no tail
+        if (!cx.split_keep && (start_quiet || cx.split_quiet >= kSplitQuietCalls) && !(on && on[0] == '2')) return MFA_OK;      // args.hdr stays NULL: no tail
     }
     uint64_t chunk_min = (env_u64("MFA_DFA_CHUNK", kSplitChunkMin) + 15u) & ~(uint64_t)15;
     if (chunk_min < 16u) chunk_min = 16u;
@@ -232,12 +242,11 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
     uint64_t arena = env_u64("MFA_DFA_ARENA", kSplitArenaChunks);       // (tests shrink it to see the chunk size grow)
     if (arena < 1u) arena = 1u;
     if (arena > kSplitArenaChunks) arena = kSplitArenaChunks;
-    out->lanes_log2 = split_lanes_log2(img.dfa_states);
     out->chunk_min = (uint32_t)chunk_min;
     out->arena_chunks = (uint32_t)arena;
     out->map_cap = (uint32_t)split_map_capacity(arena, kSplitQueueCap);
     const size_t queue_at = 256, maps_at = queue_at + (size_t)kSplitQueueCap * sizeof(SplitEntry);
-    int rc = ctx_reserve((void**)&cx.d_split, &cx.split_bytes, maps_at + ((size_t)out->map_cap << out->lanes_log2));
+    int rc = ctx_reserve((void**)&cx.d_split, &cx.split_bytes, maps_at + (size_t)out->map_cap * per_chunk);
     if (rc != MFA_OK) return rc;
     out->args.hdr = reinterpret_cast<uint32_t*>(cx.d_split);
     out->args.queue = reinterpret_cast<SplitEntry*>(cx.d_split + queue_at);
@@ -248,12 +257,19 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
     return MFA_OK;
 }
 
+// the plan kernel behind a main kernel that was given sl.args (also launched by dfa_spec.hip: spec_tail)
+int split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream) {
+    hipLaunchKernelGGL(dfa_plan_kernel, dim3(1), dim3(kPlanThreads), 0, (hipStream_t)stream, d_offsets, sl.args.hdr, sl.args.queue, sl.args.qcap,
+                       sl.arena_chunks, sl.chunk_min, sl.map_cap, sl.args.seen);
+    HIP_TRY(hipGetLastError());
+    return MFA_OK;
+}
+
 template <bool REV>
 static int split_tail_dir(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                           uint8_t* d_results, hipStream_t s, uint32_t* d_states) {
-    hipLaunchKernelGGL(dfa_plan_kernel, dim3(1), dim3(kPlanThreads), 0, s, d_offsets, sl.args.hdr, sl.args.queue, sl.args.qcap, sl.arena_chunks,
-                       sl.chunk_min, sl.map_cap, sl.args.seen);
-    HIP_TRY(hipGetLastError());
+    const int rc = split_plan(sl, d_offsets, s);
+    if (rc != MFA_OK) return rc;
     // 127 state sets: 65 532 bytes of table + 256 static, just above 64 KiB -- more than any other kernel here asks for, within the 160 KiB
     // a workgroup may have on gfx950 (tests/test_dfa_split_gpu.py runs that shape)
     const size_t lds = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t);

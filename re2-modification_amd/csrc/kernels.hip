@@ -303,7 +303,19 @@ int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const 
         uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * 8;
         if (blocks > cap) blocks = cap;
         if (blocks == 0) blocks = 1;
+        // long strings of such a table: dfa_spec.hip.  Its main kernel is dfa_big_kernel with the queue; MFA_DFA_SPLIT=0, MFA_DFA_SPEC=0 and
+        // n >= 2^31 leave split_min 0 and launch dfa_big_kernel itself
+        SplitLaunch sl;
+        int rc = spec_begin(img, cx, n, s, &sl);
+        if (rc != MFA_OK) return rc;
         HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
+        if (sl.args.split_min != 0u) {
+            rc = spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, nullptr, (unsigned)blocks);
+            if (rc == MFA_OK) rc = spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
+            if (rc != MFA_OK) return rc;
+            HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
+            return MFA_OK;
+        }
 #define BIG_GO(REVV)                                                                                                                                         \
     do {                                                                                                                                                     \
         if (img.dfa_states <= 0xffffu)                                                                                                                       \

@@ -31,6 +31,7 @@ struct HostImage {
     std::vector<uint32_t>      edge_begin;  // n_nodes + 1
     std::vector<mfa_blob_edge> edges;
 
+    uint32_t              dfa_home = 1;        // MFA_KIND_NFA, tables in L2: second seed of dfa_spec.hip's guesses (dfa_spec_core.h: spec_home_state)
     // MFA_KIND_NFA only: the reference's step function (automata.cpp:98-128) tabulated
     // over its reachable state sets.  State 0 = the empty set (absorbing, rejects),
     // state 1 = {start}.
@@ -76,6 +77,7 @@ struct LaunchCtx {
     uint32_t            split_quiet = 0;       // calls in a row that found "no long string" there
     bool                split_keep = false;    // a launch without the split kernels met a long string once: this workspace keeps them
     bool                split_ran = false;     // this launch has the split kernels behind its main kernel
+    bool                spec_ran = false;      //   ... those of dfa_spec.hip (a table in L2): its header holds the words of mfa_last_dfa_spec
 };
 
 struct DeviceState {
@@ -121,12 +123,25 @@ struct SplitLaunch {
     SplitArgs args{};
     uint8_t*  maps = nullptr;
     uint32_t  lanes_log2 = 0, chunk_min = 0, arena_chunks = 0, map_cap = 0;
+    uint32_t  spec_rounds = 0, spec_lookback = 0;      // dfa_spec.hip: repair launches and lookback bytes of this call (`maps` holds its records)
 };
+uint64_t env_u64(const char* name, uint64_t dflt);
 bool split_applies(const HostImage& img);
 int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet);
+int  split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream);
 // d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                 uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
+// dfa_spec.hip: the same three steps for tables in L2 (128 state sets and more).  spec_begin leaves out->args.split_min == 0 when the path is
+// off (the caller then launches the kernel it always has); otherwise spec_main launches the main kernel that queues long strings -- d_states
+// != NULL: the one of mfa_match_batch_resume -- and spec_tail the kernels behind it (none when out->args.hdr == NULL).
+bool spec_applies(const HostImage& img);
+int  spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+int  spec_main(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+               uint8_t* d_results, void* stream, uint32_t* d_states, unsigned blocks);
+int  spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+               uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
 // dfa_resume.hip: the walk of launch_dfa_walk with every string's state read from and written to d_states; d_results may be NULL
 int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint32_t* d_states, uint8_t* d_results, void* stream);

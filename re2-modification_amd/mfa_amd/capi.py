@@ -19,7 +19,7 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_device_count", "mfa_last_hip_error", "mfa_strerror", "mfa_version",
            "mfa_mixed_create", "mfa_mixed_destroy", "mfa_match_mixed", "mfa_match_mixed_sized", "mfa_match_mixed_host", "mfa_mixed_last_ms", "mfa_mixed_timing",
            "mfa_mixed_last_launches", "mfa_mixed_last_dfa", "mfa_pack_result_bitmap", "mfa_last_dfa_split",
-           "mfa_match_batch_resume", "mfa_match_batch_resume_host"]
+           "mfa_match_batch_resume", "mfa_match_batch_resume_host", "mfa_last_dfa_spec"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
@@ -74,6 +74,8 @@ def lib():
         L.mfa_last_kernel_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
         if hasattr(L, "mfa_last_dfa_split"):              # (a library of an older build given by MFA_LIB_PATH for an A/B run lacks it)
             L.mfa_last_dfa_split.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "mfa_last_dfa_spec"):               # (as above: an older build)
+            L.mfa_last_dfa_spec.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.mfa_mixed_create.argtypes = [ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp)]
         L.mfa_mixed_destroy.argtypes = [vp]
         L.mfa_mixed_destroy.restype = None
@@ -203,6 +205,13 @@ class Image:
         st, ch, cb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mfa_last_dfa_split(self._h, device, ctypes.byref(st), ctypes.byref(ch), ctypes.byref(cb)), "mfa_last_dfa_split")
         return st.value, ch.value, cb.value
+
+    def last_dfa_spec(self, device=0):
+        """(rewalked_chunks, serial_strings, serial_bytes) of the split path for long strings on a table in L2 in the last match call: what
+        repairing the guessed start states cost; (0, 0, 0) if that path did not run"""
+        rw, ss, sb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mfa_last_dfa_spec(self._h, device, ctypes.byref(rw), ctypes.byref(ss), ctypes.byref(sb)), "mfa_last_dfa_spec")
+        return rw.value, ss.value, sb.value
 
     def close(self):
         if self._h:

@@ -87,7 +87,7 @@ dfa_mixed_kernel(const MixDfaArgs a, const uint8_t* __restrict__ tables, const u
         const MixDfaDesc d = descs[image];
         if (image != held) {
             __syncthreads();                      // (the other waves may still be walking with the table that goes)
-            mix_fill_table(s_next, reinterpret_cast<const uint16_t*>(tables + d.trans_at), tables + d.class_at, d.n_states, d.n_classes, threadIdx.x, 256u);
+            dfa_fill_table(s_next, reinterpret_cast<const uint16_t*>(tables + d.trans_at), tables + d.class_at, d.n_states, d.n_classes, threadIdx.x, 256u);
             __syncthreads();
             held = image;
         }
@@ -114,9 +114,7 @@ int launch_dfa_mixed(const DfaPlan& plan, size_t i0, size_t i1, const uint8_t* d
         slices += dfa_slices_of(it.count);
     }
     const size_t lds = kMixTileBytes + plan.table_bytes;
-    uint64_t per_cu = (160u * 1024u) / lds;                  // resident workgroups a CU's LDS allows (at most 8: 32 waves)
-    if (per_cu > 8) per_cu = 8;
-    uint64_t blocks = slices, cap = (uint64_t)(n_cus > 0 ? n_cus : 256) * per_cu;
+    uint64_t blocks = slices, cap = (uint64_t)(n_cus > 0 ? n_cus : 256) * lds_blocks_per_cu(lds);
     if (blocks > cap) blocks = cap;
     static bool lds_allowed[64] = {false};                   // per device, once: the kernel may take up to 64 KiB of dynamic LDS
     int dev = 0;

@@ -1,5 +1,5 @@
 // The multi-table walk of a mixed call's memory-less segments (dfa_mixed.hip), the part that can be wrong without a GPU: what an
-// automaton's tables look like in the object's upload, how the fused table is filled, which 128-byte line of its string a lane walks
+// automaton's tables look like in the object's upload, which 128-byte line of its string a lane walks
 // next and which bytes of it, the walk of one line, and the 16-byte piece of a line that is staged.  Included by the kernel and,
 // with the one-lane shim of tests/emul/, by the host harness tests/emul/dfa_mixed_emul.cpp.
 #ifndef MFA_DFA_MIXED_CORE_H
@@ -27,15 +27,6 @@ static constexpr uint32_t kMixLdsMax = 64u * 1024u;                      // tile
 // rows [n_states][n_classes], the accept bytes [n_states], the byte classes [256].  n_states == 0: not in the upload (a memory
 // automaton, or a memory-less one that is not eligible).
 struct MixDfaDesc { uint32_t trans_at, accept_at, class_at, n_states, n_classes, reversed; };
-
-// entry (state, byte) of the fused table = next state * kDfaRow; thread `tid` of `threads` fills its share
-__host__ __device__ inline void mix_fill_table(uint16_t* s_next, const uint16_t* trans, const uint8_t* byte_class, uint32_t n_states, uint32_t n_classes,
-                                               uint32_t tid, uint32_t threads) {
-    for (uint32_t k = tid; k < n_states * 256u; k += threads) {
-        const uint32_t st = k >> 8, b = k & 255u;
-        s_next[st * kDfaRow + b] = (uint16_t)(trans[st * n_classes + byte_class[b]] * kDfaRow);
-    }
-}
 
 // 16 bytes of a line: nothing beyond offsets[n] of the whole batch rounded up to 16 is read (total16), and nothing for a lane without work
 __device__ __forceinline__ uint4 mix_stage16(const uint8_t* bytes, uint64_t addr, uint64_t total16, bool wanted) {

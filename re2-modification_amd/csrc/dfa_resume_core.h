@@ -1,5 +1,5 @@
-// The part of the resume path for memory-less automata (dfa_resume.hip: a string given in pieces, its state carried from call to
-// call) that can be wrong without a GPU: which state a piece is entered with, when that state is an error, the walk of one piece
+// The part of the resume path for memory-less automata (the RESUME instantiations of the kernels, dfa_split.h: a string given in pieces,
+// its state carried from call to call) that can be wrong without a GPU: which state a piece is entered with, when that state is an error, the walk of one piece
 // from a given state, the answer that belongs to a state.  Included by the kernels and, with the one-lane shim of tests/emul/, by
 // the host harness tests/emul/dfa_resume_emul.cpp.
 //
@@ -37,7 +37,7 @@ __device__ inline uint32_t resume_piece(const uint16_t* s_next, const uint8_t* b
     return split_chunk_walk<REV>(s_next, bytes, b, e, st * kDfaRow) / kDfaRow;
 }
 
-// The same on the plain table trans[state][class] of dfa_big_kernel (16- or 32-bit entries, any number of state sets).
+// The same on the plain table trans[state][class] of dfa_spec_big_kernel (16- or 32-bit entries, any number of state sets).
 template <bool REV, class T>
 __device__ inline uint32_t resume_piece_big(const T* trans, const uint8_t* byte_class, uint32_t n_classes, const uint8_t* bytes, uint64_t b,
                                             uint64_t e, uint32_t st) {

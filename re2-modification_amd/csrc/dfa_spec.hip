@@ -1,4 +1,4 @@
-// Long strings of memory-less automata whose table is walked in L2 (255 to 2^20 state sets: dfa_big_kernel's), cut across the whole GPU
+// Memory-less automata whose table is walked in L2 (255 to 2^20 state sets): the main kernel, and its long strings cut across the whole GPU
 // (gfx950).  dfa_split.hip walks every chunk from every start state; that is out of the question here, so every chunk is walked from
 // ONE state -- a guess -- and wrong guesses are repaired a bounded number of times, then resolved exactly (dfa_spec_core.h has the scheme
 // and is checked on the CPU: tests/emul).  Queue, plan, chunk geometry, knobs and the quiet-workspace rule are dfa_split.hip's:
@@ -18,42 +18,26 @@
 
 namespace mfa {
 
-// ---- main kernels: dfa_big_kernel and dfa_resume_big_kernel with the queue ------------------------------------
-// One string per lane, table in global memory, byte classes in LDS; both walk with resume_piece_big.  A string of sp.split_min bytes or more
-// is handed to the kernels below (split_take); with sp.hdr == NULL (quiet workspace) the lane walks it and split_take reports it.
-template <bool REV, class T>
+// ---- main kernel ------------------------------------------------------------------------------------------
+// THE kernel for tables in L2 (launch_dfa_walk, launch_dfa_resume: spec_main is the one place that launches it).  One string per lane, 32-bit
+// state, table in global memory -- resident in L2 up to a few MiB, 16-bit entries up to 65535 state sets and 32-bit entries beyond -- and
+// only the byte classes in LDS; the walk is resume_piece_big.  A string of sp.split_min bytes or more is handed to the kernels below
+// (split_take); with sp.hdr == NULL (quiet workspace) the lane walks it and split_take reports it; sp.split_min == 0 (MFA_DFA_SPEC=0,
+// MFA_DFA_SPLIT=0, n >= 2^31): the queue is off and every string is walked here.  RESUME: dfa_split.h has the policy.
+template <bool REV, class T, bool RESUME>
 __global__ void __launch_bounds__(256)
-dfa_spec_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
-                    const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results, const SplitArgs sp) {
+dfa_spec_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_states,
+                    uint32_t n_classes, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
+                    uint32_t* __restrict__ states, uint8_t* __restrict__ results, const SplitArgs sp) {
     __shared__ uint8_t s_class[256];
     s_class[threadIdx.x] = byte_class[threadIdx.x];
     __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
         const uint64_t b = offsets[sid], e = offsets[sid + 1];
-        if (sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // queued: dfa_spec_resolve_kernel writes results[sid]
-        results[sid] = accept_tab[resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, b, e, 1u)];
-    }
-}
-
-// Dead and invalid words are never queued (their bytes are not read), an over-long piece is the sticky error: dfa_resume.hip's rules.
-template <bool REV, class T>
-__global__ void __launch_bounds__(256)
-dfa_spec_resume_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_states,
-                           uint32_t n_classes, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-                           uint32_t* __restrict__ states, uint8_t* __restrict__ results, const SplitArgs sp) {
-    __shared__ uint8_t s_class[256];
-    s_class[threadIdx.x] = byte_class[threadIdx.x];
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
-        const uint64_t b = offsets[sid], e = offsets[sid + 1];
-        uint32_t st = resume_enter(states[sid], n_states, e - b);
-        const bool walks = resume_walks(st);
-        if (walks && sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // word and result are the resolve kernel's
-        if (walks) st = resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, b, e, st);
-        states[sid] = st;
-        if (results != nullptr) results[sid] = resume_result(accept_tab, st);
+        const StateEntry r = state_begin<RESUME>(states, n_states, sid, e - b, sp);
+        if (r.taken) continue;                                        // queued: word and result are dfa_spec_resolve_kernel's
+        state_end<RESUME>(states, results, accept_tab, sid, r.walks ? resume_piece_big<REV, T>(trans, s_class, n_classes, bytes, b, e, r.st) : r.st);
     }
 }
 
@@ -146,27 +130,13 @@ __device__ __forceinline__ uint32_t spec_resolve_string(const T* __restrict__ tr
     return st;
 }
 
-template <bool REV, class T>
+// RESUME (mfa_match_batch_resume): from the string's word (a state that walks: the main kernel queues no other), which gets the state reached
+template <bool REV, class T, bool RESUME>
 __global__ void __launch_bounds__(256)
 dfa_spec_resolve_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
                         const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
-                        const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin, uint8_t* __restrict__ results) {
-    const uint32_t n_q = hdr[SPLIT_H_STRINGS];
-    if ((uint64_t)blockIdx.x * blockDim.x >= n_q) return;
-    __shared__ uint8_t s_class[256];
-    s_class[threadIdx.x] = byte_class[threadIdx.x];
-    __syncthreads();
-    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_q; q += gridDim.x * blockDim.x)
-        results[queue[q].sid] = accept_tab[spec_resolve_string<REV, T>(trans, s_class, n_classes, bytes, offsets, hdr, queue, q, start_used, end_fin, 1u)];
-}
-
-// mfa_match_batch_resume: from the string's word (a state that walks: the main kernel queues no other), which gets the state reached
-template <bool REV, class T>
-__global__ void __launch_bounds__(256)
-dfa_spec_resolve_resume_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class, uint32_t n_classes,
-                               const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ hdr,
-                               const SplitEntry* __restrict__ queue, const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin,
-                               uint32_t* __restrict__ states, uint8_t* __restrict__ results) {
+                        const uint32_t* __restrict__ start_used, const uint32_t* __restrict__ end_fin, uint32_t* __restrict__ states,
+                        uint8_t* __restrict__ results) {
     const uint32_t n_q = hdr[SPLIT_H_STRINGS];
     if ((uint64_t)blockIdx.x * blockDim.x >= n_q) return;
     __shared__ uint8_t s_class[256];
@@ -174,9 +144,9 @@ dfa_spec_resolve_resume_kernel(const T* __restrict__ trans, const uint8_t* __res
     __syncthreads();
     for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_q; q += gridDim.x * blockDim.x) {
         const uint64_t sid = queue[q].sid;
-        const uint32_t st = spec_resolve_string<REV, T>(trans, s_class, n_classes, bytes, offsets, hdr, queue, q, start_used, end_fin, states[sid]);
-        states[sid] = st;
-        if (results != nullptr) results[sid] = accept_tab[st];
+        const uint32_t st = spec_resolve_string<REV, T>(trans, s_class, n_classes, bytes, offsets, hdr, queue, q, start_used, end_fin,
+                                                        state_of_queued<RESUME>(states, sid));
+        state_end<RESUME>(states, results, accept_tab, sid, st);
     }
 }
 
@@ -199,7 +169,7 @@ int spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, Sp
     uint64_t rounds = env_u64("MFA_DFA_SPEC_ROUNDS", kSpecRounds), lookback = env_u64("MFA_DFA_SPEC_LOOKBACK", kSpecLookback);
     out->spec_rounds = (uint32_t)(rounds > kSpecRoundsMax ? kSpecRoundsMax : rounds);
     out->spec_lookback = (uint32_t)(lookback > MFA_MAX_STRING_BYTES ? MFA_MAX_STRING_BYTES : lookback);
-    // A workspace starts QUIET here: until it has met a long string once (the twin main kernel then writes 3 to the pinned word) it launches the
+    // A workspace starts QUIET here: until it has met a long string once (the main kernel then writes 3 to the pinned word) it launches the
     // main kernel alone, so traffic of short strings never pays for the seven launches behind it, and the first batch with long strings on
     // a workspace is walked whole, as it was before this path existed; from the next call on the workspace keeps the tail for good.
     // MFA_DFA_SPLIT=2 launches the tail from the first call on.
@@ -211,12 +181,9 @@ int spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, Sp
 template <bool REV, class T>
 static int spec_main_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_results, hipStream_t s, uint32_t* d_states, unsigned blocks) {
-    if (d_states != nullptr)
-        hipLaunchKernelGGL((dfa_spec_resume_big_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
-                           img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results, sl.args);
-    else
-        hipLaunchKernelGGL((dfa_spec_big_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
-                           img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
+    auto kern = d_states != nullptr ? dfa_spec_big_kernel<REV, T, true> : dfa_spec_big_kernel<REV, T, false>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class, img.dfa_states, img.n_classes,
+                       d_bytes, d_offsets, n, d_states, d_results, sl.args);
     HIP_TRY(hipGetLastError());
     return MFA_OK;
 }
@@ -243,12 +210,9 @@ static int spec_tail_go(const HostImage& img, DeviceState& ds, const SplitLaunch
     }
     const uint32_t* end_fin = end[sl.spec_rounds & 1u];
     const unsigned q_blocks = (sl.args.qcap + 255u) / 256u;
-    if (d_states != nullptr)
-        hipLaunchKernelGGL((dfa_spec_resolve_resume_kernel<REV, T>), dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes,
-                           d_bytes, d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_states, d_results);
-    else
-        hipLaunchKernelGGL((dfa_spec_resolve_kernel<REV, T>), dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes,
-                           d_bytes, d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_results);
+    auto resolve = d_states != nullptr ? dfa_spec_resolve_kernel<REV, T, true> : dfa_spec_resolve_kernel<REV, T, false>;
+    hipLaunchKernelGGL(resolve, dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes, d_bytes, d_offsets, sl.args.hdr,
+                       (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_states, d_results);
     HIP_TRY(hipGetLastError());
     return MFA_OK;
 }

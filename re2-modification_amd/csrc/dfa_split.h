@@ -1,9 +1,10 @@
-// What the one-string-per-lane kernels (kernels.hip) and the split path (dfa_split.hip) share on the device: the plan header, the
-// queue of long strings, and the one place where a string is handed from the former to the latter.
+// What the one-string-per-lane kernels (kernels.hip, dfa_spec.hip) and the split paths (dfa_split.hip, dfa_spec.hip) share on the device:
+// the plan header, the queue of long strings, the one place where a string is handed from the former to the latter, and the policy that
+// says where a string's state comes from and where it goes (every kernel has a plain and a resume instantiation of ONE body).
 #ifndef MFA_DFA_SPLIT_H
 #define MFA_DFA_SPLIT_H
 
-#include "dfa_split_core.h"
+#include "dfa_resume_core.h"      // and dfa_split_core.h
 
 namespace mfa {
 
@@ -46,6 +47,39 @@ __device__ __forceinline__ bool split_take(const SplitArgs& sp, uint64_t sid) {
     sp.queue[slot].sid = sid;
     return true;
 }
+
+// ---- state policy --------------------------------------------------------------------------------------
+// RESUME == false (mfa_match_batch): every string starts at state 1 = {start}, is always walked, and results[sid] = accept_tab[state].
+// RESUME == true (mfa_match_batch_resume): the state is read from and written back to states[sid] under the rules of dfa_resume_core.h
+// (resume_enter, resume_walks, resume_result), and results may be NULL.  A compile-time parameter: the plain instantiations read no
+// word of `states` and test nothing.
+// What a lane does with string sid of `len` bytes: the state it enters with (`st`, a plain state number), whether it walks the bytes
+// (`walks`; false: the state leaves as it came), and whether the split path has taken the string (`taken`: the lane then leaves word
+// and result alone -- the fold or the resolve kernel behind it writes them).  Dead and invalid words are never queued.
+struct StateEntry { uint32_t st; bool walks, taken; };
+
+template <bool RESUME>
+__device__ __forceinline__ StateEntry state_begin(const uint32_t* states, uint32_t n_states, uint64_t sid, uint64_t len, const SplitArgs& sp) {
+    StateEntry r;
+    r.st = RESUME ? resume_enter(states[sid], n_states, len) : 1u;
+    r.walks = !RESUME || resume_walks(r.st);
+    r.taken = r.walks && sp.split_min != 0u && len >= sp.split_min && split_take(sp, sid);
+    return r;
+}
+
+template <bool RESUME>
+__device__ __forceinline__ void state_end(uint32_t* states, uint8_t* results, const uint8_t* accept_tab, uint64_t sid, uint32_t st) {
+    if (RESUME) {
+        states[sid] = st;
+        if (results != nullptr) results[sid] = resume_result(accept_tab, st);
+    } else {
+        results[sid] = accept_tab[st];
+    }
+}
+
+// a queued string in the kernel that finishes it (fold, resolve): it was taken with a state that walks, still in its word
+template <bool RESUME>
+__device__ __forceinline__ uint32_t state_of_queued(const uint32_t* states, uint64_t sid) { return RESUME ? states[sid] : 1u; }
 #endif
 
 }  // namespace mfa

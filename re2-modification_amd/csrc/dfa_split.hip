@@ -1,8 +1,8 @@
 // Long strings of memory-less automata, cut across the whole GPU (gfx950).  The kernels of kernels.hip walk one string per lane, so
 // the time of a call is set by its longest string.  Here a string with len >= split_min is cut into chunks; dfa_chunk_kernel
 // computes every chunk's map (state reached, for every live start state: lanes are (chunk, start state) pairs), dfa_fold_kernel
-// composes a string's maps in scan order and writes its result.  Everything runs on the caller's stream, behind the main kernel
-// that queued the strings, with no read-back: the device counts the long strings, chooses the chunk size and hands the chunks out.
+// composes a string's maps in scan order and writes its result (and, for a string in pieces, its state).  Everything runs on the caller's
+// stream, behind the main kernel that queued the strings, with no read-back: the device counts the long strings, chooses the chunk size and hands the chunks out.
 //   memset(header) -> main kernel (queues long strings: split_take) -> dfa_plan_kernel -> dfa_chunk_kernel -> dfa_fold_kernel
 // Geometry, chunk size, the chunk walk and the composition of maps are in dfa_split_core.h (checked on the CPU: tests/emul).
 #include <hip/hip_runtime.h>
@@ -85,10 +85,7 @@ dfa_chunk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__
     extern __shared__ uint32_t lds[];
     __shared__ uint32_t s_alive[64];
     uint16_t* s_next = reinterpret_cast<uint16_t*>(lds);
-    for (uint32_t k = threadIdx.x; k < n_states * 256u; k += blockDim.x) {
-        const uint32_t st = k >> 8, b = k & 255u;
-        s_next[st * kDfaRow + b] = (uint16_t)(trans[st * n_classes + byte_class[b]] * kDfaRow);
-    }
+    dfa_fill_table(s_next, trans, byte_class, n_states, n_classes, threadIdx.x, blockDim.x);
     const uint32_t chunk = hdr[SPLIT_H_CHUNK], n_q = hdr[SPLIT_H_STRINGS];
     const uint32_t lanes = 1u << lanes_log2, per_block = 256u >> lanes_log2;
     const uint32_t slot = threadIdx.x >> lanes_log2, j = threadIdx.x & (lanes - 1u);
@@ -154,25 +151,12 @@ __device__ __forceinline__ void fold_string(const SplitEntry* __restrict__ queue
     __syncthreads();
 }
 
+// RESUME (mfa_match_batch_resume): a queued string starts from its word of `states` instead of 1 and the state it reaches is written back
+// there; results may then be NULL (dfa_split.h has the policy).
+template <bool RESUME>
 __global__ void __launch_bounds__(256)
 dfa_fold_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
-                const uint8_t* __restrict__ maps, uint32_t lanes_log2, uint8_t* __restrict__ results) {
-    const uint32_t n_q = hdr[SPLIT_H_STRINGS];
-    if (n_q == 0) return;
-    __shared__ uint32_t s_tile[kFoldTileBytes / 4];
-    __shared__ uint8_t s_runs[256];
-    __shared__ uint32_t s_st;
-    for (uint32_t q = blockIdx.x; q < n_q; q += gridDim.x) {
-        fold_string(queue, q, maps, lanes_log2, 1u, s_tile, s_runs, &s_st);      // state 1 = {start}
-        if (threadIdx.x == 0) results[queue[q].sid] = accept_tab[s_st];
-    }
-}
-
-// The fold of mfa_match_batch_resume: a queued string starts from its word of `states` (a state that walks: the main kernel queues no
-// other, dfa_resume.hip) and the state it reaches is written back there; results may be NULL.
-__global__ void __launch_bounds__(256)
-dfa_fold_resume_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restrict__ hdr, const SplitEntry* __restrict__ queue,
-                       const uint8_t* __restrict__ maps, uint32_t lanes_log2, uint32_t* __restrict__ states, uint8_t* __restrict__ results) {
+                const uint8_t* __restrict__ maps, uint32_t lanes_log2, uint32_t* __restrict__ states, uint8_t* __restrict__ results) {
     const uint32_t n_q = hdr[SPLIT_H_STRINGS];
     if (n_q == 0) return;
     __shared__ uint32_t s_tile[kFoldTileBytes / 4];
@@ -180,11 +164,8 @@ dfa_fold_resume_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* _
     __shared__ uint32_t s_st;
     for (uint32_t q = blockIdx.x; q < n_q; q += gridDim.x) {
         const uint64_t sid = queue[q].sid;
-        fold_string(queue, q, maps, lanes_log2, states[sid], s_tile, s_runs, &s_st);
-        if (threadIdx.x == 0) {
-            states[sid] = s_st;
-            if (results != nullptr) results[sid] = accept_tab[s_st];
-        }
+        fold_string(queue, q, maps, lanes_log2, state_of_queued<RESUME>(states, sid), s_tile, s_runs, &s_st);
+        if (threadIdx.x == 0) state_end<RESUME>(states, results, accept_tab, sid, s_st);
     }
 }
 
@@ -273,20 +254,14 @@ static int split_tail_dir(const HostImage& img, DeviceState& ds, const SplitLaun
     // 127 state sets: 65 532 bytes of table + 256 static, just above 64 KiB -- more than any other kernel here asks for, within the 160 KiB
     // a workgroup may have on gfx950 (tests/test_dfa_split_gpu.py runs that shape)
     const size_t lds = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t);
-    uint64_t per_cu = (160u * 1024u) / (lds + 512u);
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
+    const uint64_t per_cu = lds_blocks_per_cu(lds + 512u);
     const unsigned n_cus = (unsigned)(ds.n_cus > 0 ? ds.n_cus : 256);
     HIP_TRY(hipFuncSetAttribute((const void*)dfa_chunk_kernel<REV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(dfa_chunk_kernel<REV>, dim3(n_cus * (unsigned)per_cu), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_byte_class,
                        img.dfa_states, img.n_classes, d_bytes, d_offsets, (const uint32_t*)sl.args.hdr, sl.args.queue, sl.maps, sl.lanes_log2);
     HIP_TRY(hipGetLastError());
-    if (d_states != nullptr)
-        hipLaunchKernelGGL(dfa_fold_resume_kernel, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept, (const uint32_t*)sl.args.hdr,
-                           (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_states, d_results);
-    else
-        hipLaunchKernelGGL(dfa_fold_kernel, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept, (const uint32_t*)sl.args.hdr,
-                           (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_results);
+    hipLaunchKernelGGL(d_states != nullptr ? dfa_fold_kernel<true> : dfa_fold_kernel<false>, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept,
+                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_states, d_results);
     HIP_TRY(hipGetLastError());
     return MFA_OK;
 }

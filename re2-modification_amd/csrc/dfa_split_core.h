@@ -16,6 +16,15 @@ namespace mfa {
 
 static constexpr uint32_t kDfaRow = 258;     // 16-bit entries per state row of the fused LDS table (256 + 2 pad)
 
+// entry (state, byte) of the fused table = next state * kDfaRow; thread `tid` of `threads` fills its share
+__host__ __device__ inline void dfa_fill_table(uint16_t* s_next, const uint16_t* trans, const uint8_t* byte_class, uint32_t n_states, uint32_t n_classes,
+                                               uint32_t tid, uint32_t threads) {
+    for (uint32_t k = tid; k < n_states * 256u; k += threads) {
+        const uint32_t st = k >> 8, b = k & 255u;
+        s_next[st * kDfaRow + b] = (uint16_t)(trans[st * n_classes + byte_class[b]] * kDfaRow);
+    }
+}
+
 // ---- geometry ----------------------------------------------------------------------------------------
 // The chunk grid of the string [b, e) is anchored at b rounded DOWN to 16 and has a pitch of `chunk` bytes (a multiple of 16):
 // every chunk border inside the string is 16-byte aligned in memory, only the string's first and last chunk are ragged.

@@ -22,65 +22,42 @@ namespace mfa {
 // `break` (automata.cpp:186-188,196-198).  Input is read 16 bytes per lane per load.
 // (kDfaRow, the row stride: 16-bit entries per state row, 256 + 2 pad -- dfa_split_core.h)
 // sp: strings of sp.split_min bytes and more go to the split path (dfa_split.h: split_take); sp.split_min == 0: none does.
+// RESUME: where a string's state comes from and where it goes (dfa_split.h has the policy; mfa_match_batch: false, mfa_match_batch_resume: true).
+// (Tables beyond 16-bit pre-multiplied states stay in global memory: dfa_spec.hip has their kernel.)
 
+// One lane: the state reached from st (= state * kDfaRow) over [b, e), one 16-byte block per round.
 template <bool REV>
+__device__ __forceinline__ uint32_t dfa_walk_blocks(const uint16_t* s_next, const uint8_t* __restrict__ bytes, uint64_t b, uint64_t e, uint32_t st) {
+    uint64_t p = REV ? e : b;                                         // forward: next byte to consume; reverse: one past it
+    while ((REV ? p > b : p < e) && st != 0u) {
+        const uint64_t blk = (REV ? p - 1u : p) & ~(uint64_t)15;
+        const uint32_t lo = REV ? (b > blk ? (uint32_t)(b - blk) : 0u) : (uint32_t)(p - blk);
+        const uint32_t hi = REV ? (uint32_t)(p - blk) : ((e - blk) < 16u ? (uint32_t)(e - blk) : 16u);
+        st = split_step16<REV>(s_next, st, load16(bytes, blk), lo, hi);
+        p = REV ? blk : blk + 16u;
+    }
+    return st;
+}
+
+// Two byte loops, chosen by the policy: the plain instantiation walks block by block (dfa_walk_blocks: 32 VGPRs, 8 waves per SIMD), the
+// resume one with four blocks in flight (split_chunk_walk: twice the registers).  DESIGN.md section 4.7 has what was measured.
+template <bool REV, bool RESUME>
 __global__ void __launch_bounds__(256)
-dfa_walk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__ accept_tab,
-                const uint8_t* __restrict__ byte_class, uint32_t n_states, uint32_t n_classes,
-                const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-                uint8_t* __restrict__ results, const SplitArgs sp) {
+dfa_walk_kernel(const uint16_t* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class,
+                uint32_t n_states, uint32_t n_classes, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
+                uint32_t* __restrict__ states, uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     uint16_t* s_next = reinterpret_cast<uint16_t*>(lds);             // [n_states][kDfaRow], entry = next_state * kDfaRow
-    for (uint32_t k = threadIdx.x; k < n_states * 256u; k += blockDim.x) {
-        const uint32_t st = k >> 8, b = k & 255u;
-        s_next[st * kDfaRow + b] = (uint16_t)(trans[st * n_classes + byte_class[b]] * kDfaRow);
-    }
+    dfa_fill_table(s_next, trans, byte_class, n_states, n_classes, threadIdx.x, blockDim.x);
     __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
         const uint64_t b = offsets[sid], e = offsets[sid + 1];
-        if (sp.split_min != 0u && e - b >= sp.split_min && split_take(sp, sid)) continue;      // queued: dfa_fold_kernel writes results[sid]
-        uint32_t st = kDfaRow;                                        // state 1 = {start}
-        if (!REV) {
-            uint64_t p = b;
-            while (p < e && st != 0u) {
-                const uint64_t blk = p & ~(uint64_t)15;
-                const uint4 d = load16(bytes, blk);
-                const uint32_t w[4] = {d.x, d.y, d.z, d.w};
-                const uint32_t lo = (uint32_t)(p - blk), hi = (e - blk) < 16u ? (uint32_t)(e - blk) : 16u;
-                if (lo == 0u && hi == 16u) {
-#pragma unroll
-                    for (int k = 0; k < 16; k++) st = s_next[st + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 16; k++) {
-                        const uint32_t nx = s_next[st + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
-                        st = ((uint32_t)k >= lo && (uint32_t)k < hi) ? nx : st;
-                    }
-                }
-                p = blk + 16u;
-            }
-        } else {
-            uint64_t p = e;                                           // exclusive upper end, walk downwards
-            while (p > b && st != 0u) {
-                const uint64_t blk = (p - 1u) & ~(uint64_t)15;
-                const uint4 d = load16(bytes, blk);
-                const uint32_t w[4] = {d.x, d.y, d.z, d.w};
-                const uint32_t hi = (uint32_t)(p - blk), lo = b > blk ? (uint32_t)(b - blk) : 0u;
-                if (lo == 0u && hi == 16u) {
-#pragma unroll
-                    for (int k = 15; k >= 0; k--) st = s_next[st + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
-                } else {
-#pragma unroll
-                    for (int k = 15; k >= 0; k--) {
-                        const uint32_t nx = s_next[st + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
-                        st = ((uint32_t)k >= lo && (uint32_t)k < hi) ? nx : st;
-                    }
-                }
-                p = blk;
-            }
-        }
-        results[sid] = accept_tab[st / kDfaRow];
+        const StateEntry r = state_begin<RESUME>(states, n_states, sid, e - b, sp);
+        if (r.taken) continue;                                        // queued: dfa_fold_kernel writes word and result
+        uint32_t st = r.st;
+        if (r.walks) st = (RESUME ? split_chunk_walk<REV>(s_next, bytes, b, e, st * kDfaRow) : dfa_walk_blocks<REV>(s_next, bytes, b, e, st * kDfaRow)) / kDfaRow;
+        state_end<RESUME>(states, results, accept_tab, sid, st);
     }
 }
 
@@ -108,21 +85,19 @@ static constexpr uint32_t kTileRow = kLine + 16;         // row stride in the LD
 static constexpr uint32_t kLineLanes = kLine / 16;       // lanes that fetch one row, 16 bytes each
 static constexpr uint32_t kFetches = kLineLanes;         // 64 / kLineLanes strings per load instruction -> kLineLanes instructions per round
 
-template <bool REV, bool PACKED, int NLIT>
+template <bool REV, bool PACKED, int NLIT, bool RESUME>
 __global__ void __launch_bounds__(256)
 dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t* __restrict__ accept_tab,
                  const uint8_t* __restrict__ byte_class, uint32_t n_states, uint32_t n_classes,
                  const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-                 uint8_t* __restrict__ results, const SplitArgs sp) {
+                 uint32_t* __restrict__ states, uint8_t* __restrict__ results, const SplitArgs sp) {
+    static_assert(!(PACKED && RESUME), "the SGPR-packed form carries no state across calls: such a call takes the LDS form");
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint8_t* tile = reinterpret_cast<uint8_t*>(lds) + wave * (64u * kTileRow);
     uint16_t* s_next = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(lds) + 4u * 64u * kTileRow);
     if (!PACKED) {
-        for (uint32_t k = threadIdx.x; k < n_states * 256u; k += blockDim.x) {
-            const uint32_t st = k >> 8, b = k & 255u;
-            s_next[st * kDfaRow + b] = (uint16_t)(trans[st * n_classes + byte_class[b]] * kDfaRow);
-        }
+        dfa_fill_table(s_next, trans, byte_class, n_states, n_classes, threadIdx.x, blockDim.x);
         __syncthreads();
     }
     const uint64_t total16 = (offsets[n] + 15u) & ~(uint64_t)15;
@@ -137,11 +112,11 @@ dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t
         const bool have = sid < n;
         const uint64_t b = have ? offsets[sid] : 0;
         uint64_t e = have ? offsets[sid + 1] : 0;
-        bool taken = false;                       // queued for the split path: empty here, and its result byte is dfa_fold_kernel's
-        if (sp.split_min != 0u && e - b >= sp.split_min) taken = split_take(sp, sid);
-        if (taken) e = b;
+        StateEntry r{RESUME ? 0u : 1u, !RESUME, false};
+        if (have) r = state_begin<RESUME>(states, n_states, sid, e - b, sp);
+        if (!r.walks || r.taken) e = b;           // dead, in error, or queued for the split path (word and result are dfa_fold_kernel's): empty here
         uint64_t p = REV ? e : b;                 // forward: next byte to consume; reverse: one past it
-        uint32_t st = PACKED ? 1u : kDfaRow;      // state 1 = {start}
+        uint32_t st = PACKED ? 1u : (r.walks ? r.st : 0u) * kDfaRow;
         bool active = have && (REV ? p > b : p < e);
         if (__any(active)) {                      // (a wave of empty strings has nothing to read)
         uint64_t line = (REV ? p - 1u : p) & ~(uint64_t)(kLine - 1u);
@@ -217,39 +192,10 @@ dfa_tiled_kernel(DfaPacked pk, const uint16_t* __restrict__ trans, const uint8_t
             line = (REV ? p - 1u : p) & ~(uint64_t)(kLine - 1u);
         }
         }
-        if (have && !taken) results[sid] = PACKED ? (uint8_t)((pk.accept_mask >> st) & 1u) : accept_tab[st / kDfaRow];
-    }
-}
-
-// Tabulated automata whose table does not fit LDS (more than 127 state sets): the table stays in global memory -- resident in L2
-// up to a few MiB, 16-bit entries up to 65535 state sets and 32-bit entries beyond -- and only the byte classes go to LDS.  One
-// string per lane, 32-bit state.
-template <bool REV, class T>
-__global__ void __launch_bounds__(256)
-dfa_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ accept_tab, const uint8_t* __restrict__ byte_class,
-               uint32_t n_classes, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
-               uint8_t* __restrict__ results) {
-    __shared__ uint8_t s_class[256];
-    s_class[threadIdx.x] = byte_class[threadIdx.x];
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t sid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < n; sid += stride) {
-        const uint64_t b = offsets[sid], e = offsets[sid + 1];
-        uint32_t st = 1u;                                             // state 1 = {start}, state 0 = the empty set
-        uint64_t p = REV ? e : b;
-        while ((REV ? p > b : p < e) && st != 0u) {
-            const uint64_t blk = (REV ? p - 1u : p) & ~(uint64_t)15;
-            const uint4 d = load16(bytes, blk);
-            const uint32_t w[4] = {d.x, d.y, d.z, d.w};
-            const uint32_t lo = b > blk ? (uint32_t)(b - blk) : 0u, hi = (e - blk) < 16u ? (uint32_t)(e - blk) : 16u;
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const int k = REV ? 15 - j : j;
-                if ((uint32_t)k >= lo && (uint32_t)k < hi) st = trans[st * n_classes + s_class[(w[k >> 2] >> (8 * (k & 3))) & 0xffu]];
-            }
-            p = REV ? blk : blk + 16u;
+        if (have && !r.taken) {
+            if (PACKED) results[sid] = (uint8_t)((pk.accept_mask >> st) & 1u);
+            else state_end<RESUME>(states, results, accept_tab, sid, r.walks ? st / kDfaRow : r.st);
         }
-        results[sid] = accept_tab[st];
     }
 }
 
@@ -271,117 +217,91 @@ static bool make_packed(const HostImage& img, DfaPacked& pk) {
     return true;
 }
 
-template <bool REV, bool PACKED, int NLIT>
-static int launch_dfa_tiled(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const DfaPacked& pk, const uint8_t* d_bytes,
-                            const uint64_t* d_offsets, uint64_t n, uint8_t* d_results, hipStream_t s) {
+// One launch of a kernel with the fused table in LDS (`lds` bytes of it and, tiled, the input tile), between split_begin and split_tail.
+// head: what the kernel takes in front of the arguments all of them share.
+template <class Kern, class... Head>
+static int launch_lds(Kern kern, size_t lds, const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                      uint64_t n, uint32_t* d_states, uint8_t* d_results, hipStream_t s, const Head&... head) {
     SplitLaunch sl;
     int rc = split_begin(img, cx, n, s, &sl);
     if (rc != MFA_OK) return rc;
-    size_t lds = 4 * 64 * kTileRow + (PACKED ? 0 : (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t));
-    uint64_t per_cu = (160u * 1024u) / lds;                 // resident blocks a CU's LDS allows (at most 8: 32 waves)
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * per_cu;
+    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(lds);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    auto kern = dfa_tiled_kernel<REV, PACKED, NLIT>;
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, pk, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
-                       img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, head..., (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
+                       img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results, sl.args);
     HIP_TRY(hipGetLastError());
-    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
+    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
     if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }
 
-int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
-                    uint64_t n, uint8_t* d_results, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
+// Which kernel: table in L2 (dfa_spec.hip) or fused in LDS, there tiled (table + tile <= 64 KiB), SGPR-packed, or untiled.
+template <bool REV, bool RESUME>
+static int launch_dfa(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
     if ((size_t)img.dfa_states * kDfaRow > 0xffffu) {                               // beyond 16-bit pre-multiplied states: table in L2
         uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * 8;
         if (blocks > cap) blocks = cap;
         if (blocks == 0) blocks = 1;
-        // long strings of such a table: dfa_spec.hip.  Its main kernel is dfa_big_kernel with the queue; MFA_DFA_SPLIT=0, MFA_DFA_SPEC=0 and
-        // n >= 2^31 leave split_min 0 and launch dfa_big_kernel itself
+        // long strings of such a table are cut by dfa_spec.hip; MFA_DFA_SPLIT=0, MFA_DFA_SPEC=0 and n >= 2^31 leave split_min 0: the same
+        // kernel with the queue off, and no tail
         SplitLaunch sl;
         int rc = spec_begin(img, cx, n, s, &sl);
         if (rc != MFA_OK) return rc;
         HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-        if (sl.args.split_min != 0u) {
-            rc = spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, nullptr, (unsigned)blocks);
-            if (rc == MFA_OK) rc = spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
-            if (rc != MFA_OK) return rc;
-            HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-            return MFA_OK;
-        }
-#define BIG_GO(REVV)                                                                                                                                         \
-    do {                                                                                                                                                     \
-        if (img.dfa_states <= 0xffffu)                                                                                                                       \
-            hipLaunchKernelGGL((dfa_big_kernel<REVV, uint16_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,  \
-                               ds.d_byte_class, img.n_classes, d_bytes, d_offsets, n, d_results);                                                            \
-        else                                                                                                                                                 \
-            hipLaunchKernelGGL((dfa_big_kernel<REVV, uint32_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint32_t*)ds.d_dfa_trans, ds.d_dfa_accept,  \
-                               ds.d_byte_class, img.n_classes, d_bytes, d_offsets, n, d_results);                                                            \
-    } while (0)
-        if (img.h.is_reversed)
-            BIG_GO(true);
-        else
-            BIG_GO(false);
-#undef BIG_GO
-        HIP_TRY(hipGetLastError());
+        rc = spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, d_states, (unsigned)blocks);
+        if (rc == MFA_OK) rc = spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
+        if (rc != MFA_OK) return rc;
         HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
         return MFA_OK;
     }
-    {
-        const char* mode = getenv("MFA_DFA_KERNEL");                                 // "simple" selects the untiled walk
-        if (!(mode && mode[0] == 's')) {
-            DfaPacked pk;
-            // measured on MI355X, (a|b)*abb, 1M x 1 KiB: table in LDS 4.58 TB/s (3.25 when the packed form was measured: 2.65),
-            // untiled 1.0 TB/s -- the LDS table is the default, "packed" selects the SGPR form
-            const bool packed = mode && mode[0] == 'p' && make_packed(img, pk);
-            if ((size_t)img.dfa_states * kDfaRow * 2 + 4 * 64 * kTileRow <= 64 * 1024) {
-#define MFA_DFA_GO(REVV, P, NL) return launch_dfa_tiled<REVV, P, NL>(img, ds, cx, pk, d_bytes, d_offsets, n, d_results, s)
-                if (packed && pk.n_lit <= 4) {
-                    if (img.h.is_reversed) {
-                        switch (pk.n_lit) { case 0: MFA_DFA_GO(true, true, 0); case 1: MFA_DFA_GO(true, true, 1); case 2: MFA_DFA_GO(true, true, 2);
-                                            case 3: MFA_DFA_GO(true, true, 3); default: MFA_DFA_GO(true, true, 4); }
-                    } else {
-                        switch (pk.n_lit) { case 0: MFA_DFA_GO(false, true, 0); case 1: MFA_DFA_GO(false, true, 1); case 2: MFA_DFA_GO(false, true, 2);
-                                            case 3: MFA_DFA_GO(false, true, 3); default: MFA_DFA_GO(false, true, 4); }
-                    }
-                }
-                if (img.h.is_reversed) MFA_DFA_GO(true, false, 0);
-                MFA_DFA_GO(false, false, 0);
-#undef MFA_DFA_GO
+    const size_t table = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t), tile = 4 * 64 * kTileRow;
+    const char* mode = getenv("MFA_DFA_KERNEL");                                     // "simple" selects the untiled walk
+    if (!(mode && mode[0] == 's') && table + tile <= 64 * 1024) {
+        // measured on MI355X, (a|b)*abb, 1M x 1 KiB: table in LDS 4.58 TB/s (3.25 when the packed form was measured: 2.65),
+        // untiled 1.0 TB/s -- the LDS table is the default, "packed" selects the SGPR form (which has no resume instantiation)
+        DfaPacked pk{};
+        if (!RESUME && mode && mode[0] == 'p' && make_packed(img, pk) && pk.n_lit <= 4) {
+#define MFA_DFA_PACKED(NL) launch_lds(dfa_tiled_kernel<REV, true, NL, false>, tile, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk)
+            switch (pk.n_lit) {
+                case 0: return MFA_DFA_PACKED(0);
+                case 1: return MFA_DFA_PACKED(1);
+                case 2: return MFA_DFA_PACKED(2);
+                case 3: return MFA_DFA_PACKED(3);
+                default: return MFA_DFA_PACKED(4);
             }
+#undef MFA_DFA_PACKED
         }
+        return launch_lds(dfa_tiled_kernel<REV, false, 0, RESUME>, table + tile, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk);
     }
-    size_t lds = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t);
-    if (lds > 64 * 1024) return MFA_ERR_UNSUPPORTED;
-    uint64_t blocks = (n + 255) / 256;
-    uint64_t cap = (uint64_t)ds.n_cus * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    SplitLaunch sl;
-    int rc = split_begin(img, cx, n, s, &sl);
-    if (rc != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    if (img.h.is_reversed) {
-        HIP_TRY(hipFuncSetAttribute((const void*)dfa_walk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dfa_walk_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,
-                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
-    } else {
-        HIP_TRY(hipFuncSetAttribute((const void*)dfa_walk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dfa_walk_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept,
-                           ds.d_byte_class, img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_results, sl.args);
-    }
-    HIP_TRY(hipGetLastError());
-    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s);
-    if (rc != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-    return MFA_OK;
+    // 128 to 254 state sets (a table of 64 to 128 KiB): mfa_match_batch has always refused them; mfa_match_batch_resume walks them, one
+    // workgroup per CU (its 160 KiB hold the table)
+    if (!RESUME && table > 64 * 1024) return MFA_ERR_UNSUPPORTED;
+    return launch_lds(dfa_walk_kernel<REV, RESUME>, table, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s);
+}
+
+// d_states == NULL: mfa_match_batch; else mfa_match_batch_resume
+static int launch_dfa_any(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                          uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
+    if (d_states != nullptr)
+        return img.h.is_reversed ? launch_dfa<true, true>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s)
+                                 : launch_dfa<false, true>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s);
+    return img.h.is_reversed ? launch_dfa<true, false>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s)
+                             : launch_dfa<false, false>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s);
+}
+
+int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                    uint64_t n, uint8_t* d_results, void* stream) {
+    return launch_dfa_any(img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, (hipStream_t)stream);
+}
+
+int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint32_t* d_states, uint8_t* d_results, void* stream) {
+    return launch_dfa_any(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, (hipStream_t)stream);
 }
 
 }  // namespace mfa

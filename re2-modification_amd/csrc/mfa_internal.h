@@ -118,6 +118,14 @@ namespace mfa {
 // launchers (kernels.hip); all asynchronous on `stream`
 int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
                     uint64_t n, uint8_t* d_results, void* stream);
+// the same walk with every string's state read from and written to d_states (mfa_match_batch_resume); d_results may be NULL
+int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint32_t* d_states, uint8_t* d_results, void* stream);
+// workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
+inline uint64_t lds_blocks_per_cu(size_t lds) {
+    const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);
+    return per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;
+}
 // dfa_split.hip: split_begin in front of the main kernel (its `args` go to that kernel), split_tail behind it
 struct SplitLaunch {
     SplitArgs args{};
@@ -133,18 +141,15 @@ int  split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream);
 // d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                 uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
-// dfa_spec.hip: the same three steps for tables in L2 (128 state sets and more).  spec_begin leaves out->args.split_min == 0 when the path is
-// off (the caller then launches the kernel it always has); otherwise spec_main launches the main kernel that queues long strings -- d_states
-// != NULL: the one of mfa_match_batch_resume -- and spec_tail the kernels behind it (none when out->args.hdr == NULL).
+// dfa_spec.hip: the same three steps for tables in L2 (255 state sets and more).  spec_main launches the one main kernel of such tables --
+// d_states != NULL: its instantiation for mfa_match_batch_resume -- which queues long strings unless spec_begin has left
+// out->args.split_min == 0 (the path is off); spec_tail launches the kernels behind it (none when out->args.hdr == NULL).
 bool spec_applies(const HostImage& img);
 int  spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
 int  spec_main(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                uint8_t* d_results, void* stream, uint32_t* d_states, unsigned blocks);
 int  spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
-// dfa_resume.hip: the walk of launch_dfa_walk with every string's state read from and written to d_states; d_results may be NULL
-int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
-                      uint32_t* d_states, uint8_t* d_results, void* stream);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE ONLY: the host-compilable core of the multi-table launch for the memory-less segments of a mixed call
-// (csrc/dfa_mixed_core.h: the upload, the fused table, a lane's place in its string, the staged line, the walk of a line) run one lane
+// (csrc/dfa_mixed_core.h and, for the fused table, dfa_fill_table of csrc/dfa_split_core.h: the upload, the fused table, a lane's place in its
+// string, the staged line, the walk of a line) run one lane
 // at a time over an item list, in the order dfa_mixed_kernel (csrc/dfa_mixed.hip) uses it: slice by slice, the table filled only when
 // the automaton changes.
 //   dfa_mixed_emul BATCH.bin IMAGE0.blob IMAGE1.blob ...
@@ -94,7 +95,7 @@ int main(int argc, char** argv) {
         for (uint64_t s = 0; s < dfa_slices_of(count); s++, slices++) {
             if (image != held) {
                 if ((size_t)d.n_states * kDfaRow > s_next.size()) { fprintf(stderr, "table beyond the LDS\n"); return 3; }
-                mix_fill_table(s_next.data(), reinterpret_cast<const uint16_t*>(tables.data() + d.trans_at), tables.data() + d.class_at, d.n_states, d.n_classes, 0u, 1u);
+                dfa_fill_table(s_next.data(), reinterpret_cast<const uint16_t*>(tables.data() + d.trans_at), tables.data() + d.class_at, d.n_states, d.n_classes, 0u, 1u);
                 held = image; fills++;
             }
             for (uint64_t t = 0; t < kDfaSliceStrings && s * kDfaSliceStrings + t < count; t++) {

@@ -1,12 +1,12 @@
 // TEST INFRASTRUCTURE ONLY: the host-compilable core of the resume path for memory-less automata (csrc/dfa_resume_core.h: the state a
 // piece is entered with, the error state, the walk of a piece from a given state, the answer of a state) run one lane at a time, as
-// the kernels of dfa_resume.hip and dfa_fold_resume_kernel use it.
+// the resume instantiations of the kernels (kernels.hip, dfa_spec.hip) and of dfa_fold_kernel use it.
 //   dfa_resume_emul pieces IMAGE.blob ROUNDS.bin lds|big
 //       ROUNDS.bin: u64 n, u64 rounds, u32 state_in[n], rounds * n pairs (u64 b, u64 e) -- the piece of string k in round r, in place
 //       in the buffer --, u64 total, then `total` bytes.  stdout: one line per round, "state:result" per string.
 //   dfa_resume_emul fold IMAGE.blob BATCH.bin CHUNK TILE_BYTES
 //       BATCH.bin: u64 n, u64 offsets[n + 1], then offsets[n] bytes.  Every string is cut into chunks of CHUNK bytes, the chunks' maps
-//       are composed as dfa_fold_resume_kernel composes them FROM EVERY START STATE, and the state reached is compared with a plain walk of the
+//       are composed as dfa_fold_kernel<RESUME> composes them FROM EVERY START STATE, and the state reached is compared with a plain walk of the
 //       image's table from that state (and with resume_piece).  stdout: "ok STATES CHECKS"; a difference is exit code 5.
 #include <cstdio>
 #include <cstdlib>
@@ -90,7 +90,7 @@ static int run_fold(const HostImage& img, const std::vector<uint16_t>& next, con
             for (uint32_t j = 0; j < lanes; j++)
                 maps[c * lanes + j] = j + 1u < S ? (uint8_t)(split_chunk_walk<REV>(next.data(), bytes, lo, hi, (j + 1u) * kDfaRow) / kDfaRow) : 0;
         }
-        for (uint32_t s_in = 0; s_in < S; s_in++) {                       // dfa_fold_resume_kernel: lane (r, j), then lane 0, from s_in
+        for (uint32_t s_in = 0; s_in < S; s_in++) {                       // dfa_fold_kernel<RESUME>: lane (r, j), then lane 0, from s_in
             uint32_t st = s_in;
             for (uint64_t t0 = 0; t0 < nc; t0 += tile_maps) {
                 const uint32_t cnt = (uint32_t)(nc - t0 < tile_maps ? nc - t0 : tile_maps), per = split_fold_per(cnt, runs);

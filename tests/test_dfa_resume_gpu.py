@@ -1,4 +1,4 @@
-"""Memory-less automata on strings given in pieces, on the GPU: mfa_match_batch_resume (csrc/dfa_resume.hip, and the fold of
+"""Memory-less automata on strings given in pieces, on the GPU: mfa_match_batch_resume (the resume instantiations of csrc/kernels.hip, and the fold of
 csrc/dfa_split.hip started from a given state) against the CPU restatement and against the plain batch call, on the corpus of
 tests/test_dfa_resume_cpu.py; every table form; strings beyond MFA_MAX_STRING_BYTES; the sticky error; streams and capture; the host
 mirror and the command line on top of it."""
@@ -116,6 +116,34 @@ def test_every_table_form(form, rev, tmp_path, monkeypatch):
     pieces_against_whole(img, blob, strings, rng, form)
     want = oracle_lib.OracleImage(blob).match(strings)
     assert 0 < want.sum() < len(strings)
+
+
+@pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
+def test_table_between_lds_and_l2(rev, tmp_path):
+    """130 state sets, a fused table of 67 080 bytes: beyond the 64 KiB of mfa_match_batch's LDS kernels (which refuses such an image, as it
+    always has) and below the L2 kernel's 255 -- the resume call walks it with the untiled kernel, one workgroup per CU.  Pieces against
+    the oracle on the whole strings and against one resume call on the whole strings."""
+    k = 6
+    blob = front_end_blob("(a|b)*a" + "(a|b)" * k, tmp_path, rev)
+    rng = np.random.default_rng(130 + rev)
+    strings = [rnd(b"ab", int(ln), rng) for ln in [0, 1, 15, 16, 17, 4096] + [int(x) for x in rng.integers(0, 1500, size=600)]]
+    strings += [b"a" + b"b" * k, b"b" * (k + 1), b"ab" * 300 + b"a" + b"b" * k, b"ab" * 300 + b"b" + b"a" * k, b"abc" + b"a" * 30]
+    if rev:
+        strings = [s[::-1] for s in strings]
+    n = len(strings)
+    img = capi.Image(blob)
+    assert img.info()["dfa_states"] == 130
+    rounds = rounds_of(strings, cuts_for(strings, rng), rev)
+    d_states = new_states(n)
+    for r in range(ROUNDS):
+        got = feed(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states)
+    want = oracle_lib.OracleImage(blob).match(strings)
+    assert 0 < want.sum() < n and np.array_equal(got, want)
+    d_whole = new_states(n)
+    assert np.array_equal(feed(img, strings, d_whole), want) and np.array_equal(states_of(d_states, n), states_of(d_whole, n))
+    with pytest.raises(capi.MfaError) as err:
+        plain(img, strings)
+    assert err.value.code == capi.ERR_UNSUPPORTED
 
 
 LONG = (40 << 20) + 12345

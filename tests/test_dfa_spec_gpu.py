@@ -154,9 +154,83 @@ def test_resume_pieces_through_the_path(rev, tmp_path, monkeypatch):
     assert list(got) == [0, 2, whole[0], 2] and list(st[:2]) == [DEAD, INVALID] and st[2] == states_of(whole_states, n)[0] and st[3] == INVALID
 
 
+def path_off_corpus(rev, seed):
+    """the 514-state image, about 60 strings of 0 to 3 000 bytes and the edge strings of test_small_knob_parity"""
+    k = 8
+    rng = np.random.default_rng(seed + rev)
+    strings = [rnd(b"ab", int(ln), rng) for ln in rng.integers(0, 3001, size=60)]
+    strings += [b"", b"a" + b"b" * k, b"b" * (k + 1), b"ab" * 300 + b"a" + b"b" * k, b"ab" * 300 + b"b" + b"a" * k, b"abc" + b"a" * 30]
+    if rev:
+        strings = [s[::-1] for s in strings]
+    return strings, rng
+
+
+@pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
+def test_resume_with_the_path_off(rev, tmp_path, monkeypatch):
+    """MFA_DFA_SPEC=0 on a resume call: the same main kernel with the queue off.  Every string in three pieces (scan order), once with the
+    path and once without: final states and result bytes are equal, the results are the oracle's on the whole strings, the second run
+    reports no cut string.  A word that enters dead and an invalid word, both in front of long pieces, leave as they came (results 0 and 2)."""
+    import torch
+    small_knobs(monkeypatch)
+    blob = front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path, rev)
+    strings, rng = path_off_corpus(rev, 41)
+    want = oracle_lib.OracleImage(blob).match(strings)
+    assert 0 < want.sum() < len(strings)
+    strings += [rnd(b"ab", 2000, rng), rnd(b"ab", 2500, rng)]              # entered dead, entered invalid
+    n = len(strings)
+    rounds = [[], [], []]
+    for s in strings:
+        a, b = sorted(int(x) for x in rng.integers(0, len(s) + 1, size=2))
+        parts = [s[:a], s[a:b], s[b:]]
+        for r, part in enumerate(parts[::-1] if rev else parts):
+            rounds[r].append(part)
+    words = np.full(n, START, dtype=np.uint32)
+    words[-2:] = (DEAD, INVALID)
+    img = capi.Image(blob)
+    assert img.info()["dfa_states"] == 514 and img.info()["is_reversed"] == rev
+    prime(img)
+    runs = []
+    for off in (False, True):
+        if off:
+            monkeypatch.setenv("MFA_DFA_SPEC", "0")
+        d_states = torch.from_numpy(words.view(np.int32).copy()).cuda()
+        cut = 0
+        for r in range(3):
+            got = feed(img, rounds[r], d_states)
+            cut += img.last_dfa_split()[0]
+            if off:
+                assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
+            assert list(got[-2:]) == [0, 2] and list(states_of(d_states, n)[-2:]) == [DEAD, INVALID]
+        assert (cut == 0) == off                               # with the path, pieces of 256 bytes and more were cut
+        runs.append((states_of(d_states, n), got))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+    check(runs[1][1][:-2], want, strings, "three pieces without the path, rev %d" % rev)
+    whole_states = new_states(n - 2)
+    feed(img, strings[:-2], whole_states)
+    assert np.array_equal(runs[1][0][:-2], states_of(whole_states, n - 2))
+
+
+@pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
+def test_plain_call_with_the_split_off(rev, tmp_path, monkeypatch):
+    """MFA_DFA_SPLIT=0 on mfa_match_batch, on a workspace that would cut otherwise: the same main kernel with the queue off"""
+    small_knobs(monkeypatch)
+    blob = front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path, rev)
+    strings, _ = path_off_corpus(rev, 43)
+    want = oracle_lib.OracleImage(blob).match(strings)
+    assert 0 < want.sum() < len(strings)
+    img = capi.Image(blob)
+    assert img.info()["dfa_states"] == 514
+    prime(img)
+    monkeypatch.setenv("MFA_DFA_SPLIT", "0")
+    got, off = gpu_match(img, strings)
+    check(got, want, strings, "MFA_DFA_SPLIT=0, rev %d" % rev)
+    assert expected_split(off, SMALL_MIN, SMALL_CHUNK)[0] > 0
+    assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
+
+
 def test_quiet_workspace_hands_long_strings_over(tmp_path):
     """the cycle of test_dfa_split_gpu.py::test_quiet_workspace_hands_long_strings_over on the 514-state image: quiet calls drop the extra
-    launches, the first long batch after that is walked whole by the twin main kernel and still right, then the tail comes back for good"""
+    launches, the first long batch after that is walked whole by the main kernel and still right, then the tail comes back for good"""
     blob = front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path, 0)
     rng = np.random.default_rng(31)
     ora = oracle_lib.OracleImage(blob)

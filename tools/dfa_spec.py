@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Long strings of memory-less automata whose table lives in L2 (csrc/dfa_spec.hip) against the one-lane walk, (a|b)*a(a|b)^8 (514 state
 sets) unless said otherwise.  Kernel time from mfa_last_kernel_ms, two uncounted calls, then the median of REPS calls (default 5); the sides
-of a comparison alternate call by call in one process.  "walk" is the same library with MFA_DFA_SPEC=0, which launches dfa_big_kernel, the
-kernel a build without the path launches; MFA_LIB_PATH=<other build> runs any mode against another library for a process-level A/B.
+of a comparison alternate call by call in one process.  "walk" is the same library with MFA_DFA_SPEC=0, which launches the same
+main kernel (dfa_spec_big_kernel) with the queue off; MFA_LIB_PATH=<other build> runs any mode against another library for a process-level A/B.
+The two sides of "short" therefore run one kernel and differ by a test of split_min alone: that mode is meaningful only with MFA_LIB_PATH pointing
+at a build from before the kernels were merged, whose "walk" side is the separate kernel without a queue.
 The long-string modes set MFA_DFA_SPLIT=2 on the spec side, so that the workspace's first call is cut like the others (by default it is walked whole).
 One JSON line per measurement, appended to OUT (default profiles/r09_dfa_spec.jsonl).
 
   dfa_spec.py long  [REPS] [OUT]   (a) 8 x 1 MiB, spec against walk; then spec alone: 8 x (16 MiB - 1), and 8 x 1 MiB on 32 770 and 131 074 state sets
-  dfa_spec.py short [REPS] [OUT]   (b) 1 Mi x 1 KiB, spec (the twin main kernel alone: a workspace that has met no long string has no tail) against walk
+  dfa_spec.py short [REPS] [OUT]   (b) 1 Mi x 1 KiB, spec (the main kernel alone: a workspace that has met no long string has no tail) against walk
   dfa_spec.py sweep [REPS] [OUT]   (c) MFA_DFA_SPEC_LOOKBACK 0 / 64 / 256 / 1024 and MFA_DFA_SPEC_ROUNDS 0 / 1 / 3 on (a)
 """
 import json

@@ -47,8 +47,11 @@ extern "C" {
 /* limits of the device kernels (violations -> MFA_ERR_UNSUPPORTED at image creation) */
 #define MFA_MAX_NODES        1024u     /* MFA kind: nodes (any out-degree)                 */
 #define MFA_MAX_KERNEL_CELLS 9u        /* MFA kind: distinct memory cells ("1".."9", mfa.cpp:148) */
-#define MFA_MAX_DFA_STATES   (1u << 20) /* NFA kind: reachable state sets after tabulation  */
+#define MFA_MAX_DFA_STATES   (1u << 20) /* NFA kind: reachable state sets after tabulation; beyond them the image is a set-walk image (below) */
 #define MFA_MAX_STRING_BYTES 0x00ffffffu /* 16 MiB - 1 per string                          */
+/* NFA kind, EVERY image, tabulated or not: a cycle of epsilon edges among the nodes that can be reached from `start` over edges of any
+ * kind is MFA_ERR_UNSUPPORTED.  The reference's evaluateState (automata.cpp:98-117) marks a node only after its scan and does not return
+ * once it enters such a cycle; the check is made on the graph, so it also refuses a cycle that no input would make it enter. */
 
 typedef struct mfa_image mfa_image_t;
 
@@ -56,7 +59,7 @@ typedef struct mfa_image_info {
     uint32_t kind;         /* MFA_KIND_NFA / MFA_KIND_MFA                                   */
     uint32_t is_reversed;
     uint32_t n_nodes, n_edges, n_cells;
-    uint32_t dfa_states;   /* NFA kind: number of tabulated state sets (incl. the dead set) */
+    uint32_t dfa_states;   /* NFA kind: number of tabulated state sets (incl. the dead set); 0: a set-walk image */
     uint32_t byte_classes; /* NFA kind: number of input byte classes                        */
     uint32_t last_kernel;  /* MFA_KERNEL_*: which kernel the last match call on this image launched */
 } mfa_image_info;
@@ -65,11 +68,23 @@ typedef struct mfa_image_info {
 #define MFA_KERNEL_WALK        1u /* walk_kernel: table-driven memory-automaton walk over a list of live states (any automaton, no compiler) */
 #define MFA_KERNEL_SPECIALISED 2u /* mfa_jit_kernel: the walk generated for one automaton, one slot per node in VGPRs */
 #define MFA_KERNEL_TABLE       3u /* dfa_walk_kernel: tabulated memory-less automaton                    */
+#define MFA_KERNEL_NODESET     4u /* nfa_set_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
 
 /* Build an image from a blob (include/mfa_image_format.h).  Host-only work: parse,
  * check the structural invariants the kernels rely on, and for MFA_KIND_NFA tabulate
  * the reference's step function (automata.cpp:98-128) into a transition table.
- * Needs no GPU.  Replaces: holding an `Automata*` / `MFA*` (automata.h:18-84). */
+ * Needs no GPU.  Replaces: holding an `Automata*` / `MFA*` (automata.h:18-84).
+ *
+ * Set-walk images.  A memory-less automaton whose reachable state sets pass MFA_MAX_DFA_STATES (or MFA_DFA_STATE_LIMIT=n, a lower limit
+ * from the environment) is not tabulated: the image keeps the automaton's nodes, dfa_states is 0, and the match calls walk the SET of
+ * live nodes, one string per lane, with the reference's own step per byte (last_kernel: MFA_KERNEL_NODESET).  MFA_NFA_SETWALK=1 makes
+ * every memory-less image such an image without tabulating, MFA_NFA_SETWALK=0 none (beyond the limit: MFA_ERR_UNSUPPORTED, as it used
+ * to be); both knobs are read here, at image creation.  Limits of such an image (MFA_ERR_UNSUPPORTED at creation): at most 256 nodes and
+ * 255 byte classes, no cycle of epsilon edges among the nodes reachable from the start (the reference's evaluateState would not return),
+ * epsilon chains of at most 49 nodes.  What it does not do: mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the
+ * device is touched (its state between two bytes is a set of nodes, not one 32-bit number); a string of any length is walked whole by its
+ * lane (no split path; mfa_last_dfa_split and mfa_last_dfa_spec answer zeros); in a mixed object its segment always gets a launch of
+ * its own.  mfa_last_kernel_ms covers the kernel.  A string beyond MFA_MAX_STRING_BYTES answers 2. */
 int  mfa_image_create(const void* blob, size_t n_bytes, mfa_image_t** out);
 void mfa_image_destroy(mfa_image_t* img);
 int  mfa_image_get_info(const mfa_image_t* img, mfa_image_info* out);
@@ -153,7 +168,8 @@ int  mfa_match_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d
  * takes the LDS table).  A piece of MFA_DFA_SPLIT_MIN bytes or more is cut across the GPU as described above, whatever the table's size --
  * on an LDS table the fold starts from the string's word, on an L2 table the piece's first chunk does -- with the same knobs, the same
  * quiet-workspace rule and the same report through the split-report calls below; a word that is dead or in error is never cut; the call is legal inside a stream capture under the same conditions and re-entrant per (image, device, stream).
- * MFA_ERR_UNSUPPORTED: a memory automaton (its state holds spans of the input; there is no number to hand over).
+ * MFA_ERR_UNSUPPORTED: a memory automaton (its state holds spans of the input; there is no number to hand over), or a set-walk image
+ * (dfa_states == 0: its state is a set of nodes).
  * MFA_ERR_INVALID_ARG: d_states is NULL.  Both are answered before the device is touched. */
 #define MFA_DFA_STATE_DEAD    0u           /* the empty set: absorbing, rejecting */
 #define MFA_DFA_STATE_START   1u           /* {start}: what a string's first piece is given */

@@ -92,6 +92,7 @@ void device_release(DeviceState& ds) {
     if (ds.d_dfa_trans) (void)hipFree(ds.d_dfa_trans);
     if (ds.d_dfa_accept) (void)hipFree(ds.d_dfa_accept);
     if (ds.d_byte_class) (void)hipFree(ds.d_byte_class);
+    if (ds.d_set_tables) (void)hipFree(ds.d_set_tables);
     if (ds.d_walk) (void)hipFree(ds.d_walk);
     for (LaunchCtx* cx : ds.ctxs) { ctx_free(*cx); delete cx; }
     jit_unload(ds);
@@ -118,6 +119,8 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
     };
     if (h.h.kind == MFA_KIND_MFA) {
         if (img->walk_ok) rc = up((void**)&ds.d_walk, img->walk.words.data(), img->walk.words.size() * 4);
+    } else if (h.set_walk) {
+        rc = up((void**)&ds.d_set_tables, h.set_tables.data(), h.set_tables.size() * 4);
     } else {
         if (h.dfa_states <= 0xffffu) {
             std::vector<uint16_t> t16(h.dfa_trans.begin(), h.dfa_trans.end());
@@ -178,7 +181,7 @@ int mfa_image_create(const void* blob, size_t n_bytes, mfa_image_t** out) {
     mfa_image* img = new (std::nothrow) mfa_image();
     if (!img) return MFA_ERR_NOMEM;
     int rc = parse_blob(blob, n_bytes, img->host);
-    if (rc == MFA_OK) rc = img->host.h.kind == MFA_KIND_MFA ? check_mfa_invariants(img->host) : tabulate_nfa(img->host);
+    if (rc == MFA_OK) rc = img->host.h.kind == MFA_KIND_MFA ? check_mfa_invariants(img->host) : nfa_image_build(img->host);
     if (rc != MFA_OK) { delete img; return rc; }
     if (spec_applies(img->host)) img->host.dfa_home = spec_home_state(img->host.dfa_trans.data(), img->host.dfa_states, img->host.n_classes);
     if (img->host.h.kind == MFA_KIND_MFA) {
@@ -256,7 +259,7 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
     // MFA_VERBOSE=1: which kernel walks, on stderr
     if (is_mfa && !jit) { const char* rq = getenv("MFA_REQUIRE_JIT"); if (rq && rq[0] == '1') return MFA_ERR_JIT; }
     if (const char* vb = getenv("MFA_VERBOSE"))
-        if (vb[0] == '1') fprintf(stderr, "mfa_hip: %s\n", !is_mfa ? "table walk of the tabulated automaton (dfa_*_kernel)" : jit ? "kernel generated for this automaton (mfa_jit_kernel)" : "table-driven walk (walk_kernel)");
+        if (vb[0] == '1') fprintf(stderr, "mfa_hip: %s\n", !is_mfa ? img->host.set_walk ? "set walk of the automaton's nodes (nfa_set_kernel)" : "table walk of the tabulated automaton (dfa_*_kernel)" : jit ? "kernel generated for this automaton (mfa_jit_kernel)" : "table-driven walk (walk_kernel)");
     LaunchCtx* cx = nullptr;
     rc = ctx_acquire(*ds, stream, &cx);
     if (rc != MFA_OK) return rc;
@@ -266,7 +269,7 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
         LaunchCtx* cx; void* stream;
         ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
     } done_guard{cx, stream};
-    img->last_kernel = table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : MFA_KERNEL_TABLE;
+    img->last_kernel = table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : img->host.set_walk ? MFA_KERNEL_NODESET : MFA_KERNEL_TABLE;
     if (is_mfa && own_regions && regions_enabled()) {
         rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
         if (rc != MFA_OK) return rc;
@@ -328,6 +331,7 @@ int mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint6
                            uint8_t* d_results, int device, void* stream) {
     if (!img || !d_offsets) return MFA_ERR_INVALID_ARG;
     if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;      // a memory automaton's state holds spans of the input: nothing to hand over
+    if (img->host.set_walk) return MFA_ERR_UNSUPPORTED;                    // a set-walk image's state is a set of nodes, not one 32-bit number
     if (!d_states) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
     std::lock_guard<std::mutex> lk(img->mu);
@@ -350,7 +354,7 @@ int mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint6
 int mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint32_t* states, uint8_t* results,
                                 int device) {
     if (!img || !offsets) return MFA_ERR_INVALID_ARG;
-    if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;
+    if (img->host.h.kind != MFA_KIND_NFA || img->host.set_walk) return MFA_ERR_UNSUPPORTED;
     if (!states) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
     for (uint64_t k = 0; k < n; k++)

@@ -115,9 +115,10 @@ inline std::vector<uint8_t> dfa_mixed_pack(const std::vector<const HostImage*>& 
     return out;
 }
 
-// exactly the images launch_dfa_walk gives dfa_tiled_kernel: 16-bit pre-multiplied states, table plus tile at most 64 KiB
+// exactly the images launch_dfa_walk gives dfa_tiled_kernel: 16-bit pre-multiplied states, table plus tile at most 64 KiB (a set-walk
+// image has no table and takes a launch of its own)
 inline bool dfa_mixed_eligible(const HostImage& img) {
-    return img.h.kind == MFA_KIND_NFA && (size_t)img.dfa_states * kDfaRow <= 0xffffu && (size_t)img.dfa_states * kDfaRow * 2u + kMixTileBytes <= kMixLdsMax;
+    return img.h.kind == MFA_KIND_NFA && !img.set_walk && (size_t)img.dfa_states * kDfaRow <= 0xffffu && (size_t)img.dfa_states * kDfaRow * 2u + kMixTileBytes <= kMixLdsMax;
 }
 inline uint32_t dfa_mixed_table_bytes(const HostImage& img) { return img.dfa_states * kDfaRow * 2u; }
 

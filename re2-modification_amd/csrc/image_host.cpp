@@ -1,12 +1,15 @@
 // Host side of an automaton image: blob parsing, the structural checks the MFA kernel
-// relies on, and tabulation of the memory-less step function for the table-walk kernel.
+// relies on, tabulation of the memory-less step function for the table-walk kernel, and the tables of the set walk
+// for automata whose tabulation passes the limit.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <unordered_map>
 
 #include "mfa_internal.h"
+#include "nfa_set_core.h"
 
 namespace mfa {
 
@@ -103,12 +106,11 @@ struct Stepper {
 
 }  // namespace
 
-int tabulate_nfa(HostImage& img) {
-    const uint32_t n = img.h.n_nodes;
-    // byte classes: one per distinct literal label, one for every other byte ('.' edges match all)
+// byte classes: one per distinct literal label, one for every other byte ('.' edges match all); rep: a representative byte per class
+static int nfa_byte_classes(HostImage& img, std::vector<int>& rep) {
     int cls_of[256];
     for (int b = 0; b < 256; b++) cls_of[b] = -1;
-    std::vector<int> rep;           // representative byte per class
+    rep.clear();
     int other_rep = -1;
     for (const auto& e : img.edges)
         if (!(e.flags & MFA_EDGE_EPS) && e.label != '.' && cls_of[e.label] < 0) {
@@ -120,10 +122,133 @@ int tabulate_nfa(HostImage& img) {
     int other_cls = (int)rep.size();
     rep.push_back(other_rep < 0 ? 0 : other_rep);
     for (int b = 0; b < 256; b++) img.byte_class[b] = (uint8_t)(cls_of[b] >= 0 ? cls_of[b] : other_cls);
-    // a '.' byte in the input only matches '.' labels, like any other unlabelled byte -- unless some
-    // edge carries the literal label '.', which the reference treats as the wildcard (automata.cpp:111)
+    // a '.' byte in the input only matches '.' labels, like any other unlabelled byte -- unless some edge carries the literal label '.',
+    // which the reference treats as the wildcard (automata.cpp:111)
     img.n_classes = (uint32_t)rep.size();
-    if (img.n_classes > 255) return MFA_ERR_UNSUPPORTED;
+    return img.n_classes > 255 ? MFA_ERR_UNSUPPORTED : MFA_OK;
+}
+
+// The epsilon edges among the nodes that can be reached from `start`: MFA_ERR_UNSUPPORTED if they close a cycle (the reference's
+// evaluateState marks a node after its scan, so it would recurse for ever, and so would Stepper); else *chain = the most nodes on one
+// path of epsilon edges (1 when there is none).
+int nfa_eps_chain(const HostImage& img, uint32_t* chain, std::vector<uint8_t>* reached) {
+    const uint32_t n = img.h.n_nodes;
+    std::vector<uint8_t> seen(n, 0);
+    std::vector<uint32_t> todo{img.h.start};
+    seen[img.h.start] = 1;
+    while (!todo.empty()) {
+        const uint32_t u = todo.back(); todo.pop_back();
+        for (uint32_t e = img.edge_begin[u]; e < img.edge_begin[u + 1]; e++)
+            if (!seen[img.edges[e].target]) { seen[img.edges[e].target] = 1; todo.push_back(img.edges[e].target); }
+    }
+    // depth-first over epsilon edges with an explicit stack: colour 1 = on the path, 2 = done (len = nodes on its longest path down)
+    std::vector<uint8_t> colour(n, 0);
+    std::vector<uint32_t> len(n, 1), at(n, 0), path;
+    uint32_t longest = 1;
+    for (uint32_t r = 0; r < n; r++) {
+        if (!seen[r] || colour[r]) continue;
+        path.assign(1, r); colour[r] = 1; at[r] = img.edge_begin[r];
+        while (!path.empty()) {
+            const uint32_t u = path.back();
+            if (at[u] < img.edge_begin[u + 1]) {
+                const mfa_blob_edge& ed = img.edges[at[u]++];
+                if (!(ed.flags & MFA_EDGE_EPS)) continue;
+                if (colour[ed.target] == 1) return MFA_ERR_UNSUPPORTED;
+                if (colour[ed.target] == 2) { len[u] = std::max(len[u], len[ed.target] + 1u); continue; }
+                colour[ed.target] = 1; at[ed.target] = img.edge_begin[ed.target]; path.push_back(ed.target);
+            } else {
+                colour[u] = 2; path.pop_back();
+                longest = std::max(longest, len[u]);
+                if (!path.empty()) len[path.back()] = std::max(len[path.back()], len[u] + 1u);
+            }
+        }
+    }
+    if (chain) *chain = longest;
+    if (reached) *reached = seen;
+    return MFA_OK;
+}
+
+// The tables of the set walk (nfa_set_core.h has the layout and the rule).  MFA_ERR_UNSUPPORTED: more nodes, classes, items or a
+// longer epsilon chain than the kernel holds, or a cycle of epsilon edges.
+int nfa_set_build(HostImage& img) {
+    const uint32_t n = img.h.n_nodes;
+    std::vector<int> rep;
+    int rc = nfa_byte_classes(img, rep);
+    if (rc != MFA_OK) return rc;
+    uint32_t chain = 1;
+    std::vector<uint8_t> reached;
+    rc = nfa_eps_chain(img, &chain, &reached);
+    if (rc != MFA_OK) return rc;
+    if (n > kSetMaxNodes || chain - 1u > kSetMaxDepth) return MFA_ERR_UNSUPPORTED;
+    const uint32_t W = n <= 32 ? 1u : n <= 64 ? 2u : n <= 128 ? 4u : 8u, C = img.n_classes;
+    std::vector<uint32_t> item_begin(n + 1, 0), items, masks;
+    uint32_t runs = 0;
+    for (uint32_t u = 0; u < n; u++) {
+        item_begin[u] = (uint32_t)items.size();
+        bool in_run = false;
+        for (uint32_t e = img.edge_begin[u]; reached[u] && e < img.edge_begin[u + 1]; e++) {
+            const mfa_blob_edge& ed = img.edges[e];
+            if (ed.flags & MFA_EDGE_EPS) { items.push_back(kSetItemEps | ed.target); in_run = false; continue; }
+            if (!in_run) { items.push_back(runs++); masks.resize((size_t)runs * C * W, 0u); in_run = true; }
+            for (uint32_t c = 0; c < C; c++)
+                if (ed.label == '.' || ed.label == (uint8_t)rep[c]) masks[((size_t)(runs - 1u) * C + c) * W + (ed.target >> 5)] |= 1u << (ed.target & 31u);
+        }
+    }
+    item_begin[n] = (uint32_t)items.size();
+    if (items.size() >= (1u << kSetPosBits) || masks.size() >= (1u << 26)) return MFA_ERR_UNSUPPORTED;
+    // accept: the nodes from which `finish` is reached over epsilon edges alone (finish itself among them)
+    std::vector<uint32_t> accept(W, 0u);
+    for (uint32_t u = 0; u < n; u++) {
+        std::vector<uint8_t> seen(n, 0);
+        std::vector<uint32_t> todo{u};
+        seen[u] = 1;
+        bool hit = false;
+        while (!todo.empty() && !hit) {
+            const uint32_t v = todo.back(); todo.pop_back();
+            if (v == img.h.finish) { hit = true; break; }
+            for (uint32_t e = img.edge_begin[v]; e < img.edge_begin[v + 1]; e++)
+                if ((img.edges[e].flags & MFA_EDGE_EPS) && !seen[img.edges[e].target]) { seen[img.edges[e].target] = 1; todo.push_back(img.edges[e].target); }
+        }
+        if (hit) accept[u >> 5] |= 1u << (u & 31u);
+    }
+    std::vector<uint32_t>& out = img.set_tables;
+    out.assign(SET_H_SIZE, 0u);
+    out[SET_H_NODES] = n; out[SET_H_WORDS] = W; out[SET_H_CLASSES] = C; out[SET_H_DEPTH] = chain - 1u;
+    out[SET_H_START] = img.h.start; out[SET_H_REVERSED] = img.h.is_reversed ? 1u : 0u;
+    out[SET_H_ITEM_BEGIN] = (uint32_t)out.size(); out.insert(out.end(), item_begin.begin(), item_begin.end());
+    out[SET_H_ITEMS] = (uint32_t)out.size();      out.insert(out.end(), items.begin(), items.end());
+    out[SET_H_MASKS] = (uint32_t)out.size();      out.insert(out.end(), masks.begin(), masks.end());
+    out[SET_H_ACCEPT] = (uint32_t)out.size();     out.insert(out.end(), accept.begin(), accept.end());
+    out[SET_H_BYTE_CLASS] = (uint32_t)out.size(); out.resize(out.size() + 64u, 0u);
+    std::memcpy(out.data() + out[SET_H_BYTE_CLASS], img.byte_class, 256);
+    out[SET_H_TOTAL] = (uint32_t)out.size();
+    img.set_walk = true;
+    img.dfa_states = 0; img.dfa_trans.clear(); img.dfa_accept.clear();
+    return MFA_OK;
+}
+
+// What mfa_image_create does with a memory-less automaton: tabulate it, and when the state sets pass the limit (MFA_DFA_STATE_LIMIT,
+// at most MFA_MAX_DFA_STATES) build the tables of the set walk instead.  MFA_NFA_SETWALK=1: the set walk without tabulating;
+// MFA_NFA_SETWALK=0: no set walk, the refusal of old.  Both are read here, once per image.
+int nfa_image_build(HostImage& img) {
+    int rc = nfa_eps_chain(img, nullptr, nullptr);
+    if (rc != MFA_OK) return rc;
+    const char* sw = getenv("MFA_NFA_SETWALK");
+    if (sw && sw[0] == '1') return nfa_set_build(img);
+    uint64_t limit = MFA_MAX_DFA_STATES;
+    if (const char* e = getenv("MFA_DFA_STATE_LIMIT")) {
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v >= 2 && v < limit) limit = v;
+    }
+    rc = tabulate_nfa(img, (uint32_t)limit);
+    if (rc != MFA_ERR_UNSUPPORTED || img.n_classes > 255 || (sw && sw[0] == '0')) return rc;
+    return nfa_set_build(img);
+}
+
+int tabulate_nfa(HostImage& img, uint32_t max_states, std::vector<std::string>* sets_out) {
+    const uint32_t n = img.h.n_nodes;
+    std::vector<int> rep;
+    if (nfa_byte_classes(img, rep) != MFA_OK) return MFA_ERR_UNSUPPORTED;
 
     // state sets as packed bit strings (up to MFA_MAX_DFA_STATES of them: determinisation can be exponential, e.g.
     // (a|b)*a(a|b)^k has 2^(k+1) sets)
@@ -153,7 +278,7 @@ int tabulate_nfa(HostImage& img) {
             uint32_t id;
             if (it == ids.end()) {
                 id = (uint32_t)sets.size();
-                if (id >= MFA_MAX_DFA_STATES) return MFA_ERR_UNSUPPORTED;
+                if (id >= max_states) { img.dfa_trans.clear(); return MFA_ERR_UNSUPPORTED; }
                 ids.emplace(t, id); sets.push_back(t);
             } else id = it->second;
             img.dfa_trans.push_back(id);
@@ -166,6 +291,7 @@ int tabulate_nfa(HostImage& img) {
         std::vector<uint8_t> f = st.step(cur, -1);            // automata.cpp:201-202
         img.dfa_accept[s] = f[img.h.finish];                  // automata.cpp:204-208
     }
+    if (sets_out) *sets_out = std::move(sets);                // (tests: state number -> its node set, bit v & 7 of byte v >> 3)
     return MFA_OK;
 }
 

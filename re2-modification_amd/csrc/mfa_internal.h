@@ -40,12 +40,17 @@ struct HostImage {
     uint8_t               byte_class[256] = {0};
     std::vector<uint32_t> dfa_trans;   // [dfa_states][n_classes]
     std::vector<uint8_t>  dfa_accept;  // [dfa_states]: finish is in the set after the final pass
+    // MFA_KIND_NFA whose tabulation passed the limit: the tables of the set walk (nfa_set_core.h); dfa_states is then 0
+    bool                  set_walk = false;
+    std::vector<uint32_t> set_tables;
     mutable int           jit_source_ok = -1;      // MFA kind: the generated kernel's source is of a size a compiler finishes (jit.hip; -1 = not looked at)
 };
 
 int parse_blob(const void* blob, size_t n_bytes, HostImage& out);   // MFA_OK / MFA_ERR_*
 int check_mfa_invariants(const HostImage& img);                      // MFA_OK / MFA_ERR_UNSUPPORTED
-int tabulate_nfa(HostImage& img);                                    // fills the dfa_* members
+int tabulate_nfa(HostImage& img, uint32_t max_states = MFA_MAX_DFA_STATES, std::vector<std::string>* sets_out = nullptr);   // fills the dfa_* members; MFA_ERR_UNSUPPORTED beyond max_states state sets
+int nfa_set_build(HostImage& img);                                   // fills set_tables instead (MFA_ERR_UNSUPPORTED: outside the set walk's limits)
+int nfa_image_build(HostImage& img);                                 // MFA_KIND_NFA at image creation: one or the other
 
 // ---- per-device state -----------------------------------------------------------------------
 
@@ -86,6 +91,7 @@ struct DeviceState {
     void*     d_dfa_trans  = nullptr;   // [dfa_states][n_classes], 16-bit entries up to 65535 state sets, 32-bit beyond
     uint8_t*  d_dfa_accept = nullptr;
     uint8_t*  d_byte_class = nullptr;
+    uint32_t* d_set_tables = nullptr;   // a set-walk image: HostImage::set_tables
     // launch workspaces
     std::vector<LaunchCtx*> ctxs;
     LaunchCtx*              last = nullptr;    // context of the most recent launch (mfa_last_kernel_ms)
@@ -121,6 +127,9 @@ int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const 
 // the same walk with every string's state read from and written to d_states (mfa_match_batch_resume); d_results may be NULL
 int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint32_t* d_states, uint8_t* d_results, void* stream);
+// nfa_set.hip: the set walk of an image whose tabulation passed the limit (HostImage::set_walk)
+int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                   uint8_t* d_results, void* stream);
 // workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
 inline uint64_t lds_blocks_per_cu(size_t lds) {
     const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);

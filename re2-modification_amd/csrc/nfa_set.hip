@@ -1,0 +1,83 @@
+// The set walk of memory-less automata, written for gfx950 (MI355X): Automata::match (reference automata.cpp:177-210) for an automaton
+// whose determinisation passes the tabulation limit (image_host.cpp: nfa_image_build).  One input string per lane; the lane's state is
+// the set of live nodes, W words of bit mask in registers, and every byte runs the reference's step on it (nfa_set_core.h).
+//   LDS: the stacks of the 256 lanes, [slot][lane] -- a slot's 256 words are consecutive, so the lanes of a wave that push or pop at the
+//   same depth hit 64 different banks, and the stack pointer stays a register (a private array indexed by it would live in scratch
+//   memory) -- and behind them the automaton's tables when both fit 64 KiB; else the tables are read through L2.
+//   Input: 16 bytes per lane per load, in aligned blocks that hold a byte of the string: nothing beyond offsets[n] rounded up to 16.
+//   Grid: persistent, capped by what the CUs keep resident (lds_blocks_per_cu), strings dealt out by lane number.
+// Supported: up to 256 nodes (W = 1, 2, 4, 8 words for up to 32, 64, 128, 256), 255 byte classes, epsilon chains of up to 49 nodes.
+// A long string is walked whole by its lane: the state is a set, not a number, and the split paths compose maps of numbers.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "mfa_internal.h"
+#include "nfa_set_core.h"
+
+namespace mfa {
+
+static constexpr size_t kSetLdsMax = 64u * 1024u;
+
+template <bool REV, int W>
+__global__ void __launch_bounds__(256)
+nfa_set_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t stack_words, uint32_t tables_in_lds,
+               const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results) {
+    extern __shared__ uint32_t lds[];
+    uint32_t* stack = lds + threadIdx.x;                               // slot s of this lane: stack[s * 256]
+    const uint32_t* base = tables;
+    if (tables_in_lds) {
+        uint32_t* copy = lds + stack_words;
+        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
+        __syncthreads();
+        base = copy;
+    }
+    const NfaSetView t = nfa_set_view(tables, base);
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t sid = (uint64_t)blockIdx.x * 256u + threadIdx.x; sid < n; sid += stride)
+        results[sid] = nfa_set_walk<REV, W>(t, stack, 256u, bytes, offsets[sid], offsets[sid + 1]);
+}
+
+template <bool REV, int W>
+static int launch_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint8_t* d_results, hipStream_t s) {
+    const uint32_t words = (uint32_t)img.set_tables.size(), stack_words = img.set_tables[SET_H_DEPTH] * 256u;
+    static_assert((size_t)kSetMaxDepth * 256u * 4u <= kSetLdsMax, "the stacks alone fit (nfa_set_build holds an image to kSetMaxDepth)");
+    const bool in_lds = ((size_t)stack_words + words) * 4u <= kSetLdsMax;
+    const size_t lds = ((size_t)stack_words + (in_lds ? words : 0u)) * 4u;
+    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(lds);
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    auto kern = nfa_set_kernel<REV, W>;
+    // per instantiation and device, once; images hold different locks, so the flags are atomic (two first launches at once both set it)
+    static std::atomic<bool> lds_allowed[64];
+    const bool tracked = ds.device >= 0 && ds.device < 64;
+    if (!tracked || !lds_allowed[ds.device].load(std::memory_order_acquire)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSetLdsMax));
+        if (tracked) lds_allowed[ds.device].store(true, std::memory_order_release);
+    }
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words, in_lds ? 1u : 0u,
+                       d_bytes, d_offsets, n, d_results);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
+    return MFA_OK;
+}
+
+int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                   uint8_t* d_results, void* stream) {
+    if (!img.set_walk || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+#define MFA_SET_LAUNCH(W) (img.h.is_reversed ? launch_set<true, W>(img, ds, cx, d_bytes, d_offsets, n, d_results, s) \
+                                             : launch_set<false, W>(img, ds, cx, d_bytes, d_offsets, n, d_results, s))
+    switch (img.set_tables[SET_H_WORDS]) {
+        case 1: return MFA_SET_LAUNCH(1);
+        case 2: return MFA_SET_LAUNCH(2);
+        case 4: return MFA_SET_LAUNCH(4);
+        case 8: return MFA_SET_LAUNCH(8);
+    }
+#undef MFA_SET_LAUNCH
+    return MFA_ERR_UNSUPPORTED;
+}
+
+}  // namespace mfa

@@ -216,7 +216,8 @@ void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const 
 void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     mfa_image* img = image_for_match();
     mfa_image_info info;
-    if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA) {
+    // (a set-walk image -- dfa_states == 0 -- hands no state from call to call: a string beyond the limit is refused as a memory automaton's is)
+    if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA && info.dfa_states != 0) {
         vector<uint64_t> longs;
         for (uint64_t k = 0; k < n; k++)
             if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) longs.push_back(k);
@@ -296,6 +297,8 @@ void Automata::Stream::feed(const string& block) {
     mfa_image_info info;
     int rc = mfa_image_get_info(img, &info);
     if (rc != MFA_OK) fail("mfa_image_get_info", rc);
+    if (info.kind == MFA_KIND_NFA && info.dfa_states == 0)
+        throw std::runtime_error("Automata::Stream: the automaton's state sets pass the tabulation limit; it is walked as a set of nodes, which is not carried from block to block");
     const uint8_t* bytes = reinterpret_cast<const uint8_t*>(block.data());
     vector<uint8_t> stage;
     for (uint64_t r = 0; r == 0 || r * kPieceBytes < block.size(); r++) {
@@ -393,7 +396,7 @@ vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector
     vector<Automata*> long_owner;
     for (size_t k = 0; k < strs.size(); k++) {
         mfa_image_info info;
-        const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA;
+        const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA && info.dfa_states != 0;      // (tabulated: its strings may go in pieces)
         for (const string& s : strs[k]) {
             if (memory_less && s.size() > MFA_MAX_STRING_BYTES) { longs.push_back({off.size() - 1, &s}); long_owner.push_back(automata[k]); }
             else bytes.insert(bytes.end(), s.begin(), s.end());

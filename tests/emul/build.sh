@@ -1,7 +1,22 @@
 #!/bin/sh
-# TEST INFRASTRUCTURE ONLY: builds the one-lane host emulation of the walk kernel's source (see walk_emul.cpp)
+# TEST INFRASTRUCTURE ONLY: builds one of the host harnesses of this folder (see NAME_emul.cpp).
+#   build.sh NAME [OUT]       OUT: where the program goes (default: NAME_emul in this folder)
+#   EMUL_FLAGS: more compiler flags, e.g. -DWALK_NODE_MAP=1 or -fsanitize=address,undefined
 set -e
+name=${1:?usage: build.sh NAME [OUT]}
 here=$(cd "$(dirname "$0")" && pwd)
-out=${1:-$here/walk_emul}
-g++ -O1 -g -std=c++17 $EMUL_FLAGS -Wall -Wno-unknown-pragmas -Wno-unused-function -Wno-unused-variable -Wno-maybe-uninitialized -I"$here/shim" -I"$here/../../re2-modification_amd/csrc" -I"$here/../../include" \
-    -o "$out" "$here/walk_emul.cpp" "$here/../../re2-modification_amd/csrc/walk_tables.cpp" "$here/../../re2-modification_amd/csrc/image_host.cpp"
+case ${2:-} in "") out=$here/${name}_emul ;; /*) out=$2 ;; *) out=$PWD/$2 ;; esac
+cd "$here"
+csrc=../../re2-modification_amd/csrc
+# the harnesses that compile the kernels' own headers do so through the HIP shim, and hear the warnings those headers raise under g++
+shim="-Ishim -Wno-unknown-pragmas -Wno-unused-function -Wno-unused-variable"
+# NAME          optimisation   more flags                              sources beside NAME_emul.cpp
+case $name in
+walk)           opt=-O1        more="$shim -Wno-maybe-uninitialized"   src="$csrc/walk_tables.cpp $csrc/image_host.cpp" ;;
+plan|dfa_plan)  opt=-O1        more=                                   src= ;;
+dfa_split|dfa_resume|dfa_mixed|nfa_set)
+                opt=-O1        more=$shim                              src=$csrc/image_host.cpp ;;
+dfa_spec)       opt=-O2        more=$shim                              src=$csrc/image_host.cpp ;;
+*)              echo "build.sh: no harness named '$name'" >&2; exit 2 ;;
+esac
+g++ $opt -g -std=c++17 $EMUL_FLAGS -Wall $more -I$csrc -I../../include -o "$out" ${name}_emul.cpp $src

@@ -7,11 +7,7 @@
 //   dfa_mixed_emul --eligible STATES        prints "eligible table_bytes" for a memory-less automaton of STATES state sets
 //   BATCH.bin: u64 n, u64 n_items, u64 offsets[n + 1], n_items x (u64 first, u64 count, u64 image), then offsets[n] bytes.
 //   stdout: "fills F slices S", then one line per string: 0 / 1 / 2, or - for a string no item holds.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#include "emul_common.h"
 #include "dfa_mixed_core.h"
 #include "walk_plan.h"
 
@@ -52,29 +48,18 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc < 3) { fprintf(stderr, "usage: dfa_mixed_emul BATCH.bin IMAGE.blob...\n"); return 2; }
-    auto slurp = [](const char* path) {
-        std::vector<uint8_t> v;
-        FILE* f = fopen(path, "rb");
-        if (!f) { perror(path); exit(2); }
-        uint8_t buf[65536];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + got);
-        fclose(f);
-        return v;
-    };
     std::vector<HostImage> imgs(argc - 2);
     std::vector<const HostImage*> ptrs;
     std::vector<uint8_t> eligible;
     for (int k = 2; k < argc; k++) {
-        const std::vector<uint8_t> blob = slurp(argv[k]);
         HostImage& img = imgs[k - 2];
-        if (parse_blob(blob.data(), blob.size(), img) != MFA_OK || img.h.kind != MFA_KIND_NFA || tabulate_nfa(img) != MFA_OK) { fprintf(stderr, "%s: not a memory-less image\n", argv[k]); return 2; }
+        emul::load_memoryless(argv[k], img);
         ptrs.push_back(&img);
         eligible.push_back(dfa_mixed_eligible(img) ? 1 : 0);
     }
     const std::vector<uint8_t> tables = dfa_mixed_pack(ptrs, eligible);
     const MixDfaDesc* descs = reinterpret_cast<const MixDfaDesc*>(tables.data());
-    const std::vector<uint8_t> batch = slurp(argv[1]);
+    const std::vector<uint8_t> batch = emul::slurp(argv[1]);
     uint64_t n, n_items;
     memcpy(&n, batch.data(), 8);
     memcpy(&n_items, batch.data() + 8, 8);
@@ -82,9 +67,7 @@ int main(int argc, char** argv) {
     memcpy(off.data(), batch.data() + 16, (n + 1) * 8);
     memcpy(items.data(), batch.data() + 16 + (n + 1) * 8, 3 * n_items * 8);
     const uint64_t total16 = (off[n] + 15u) & ~(uint64_t)15;
-    uint8_t* bytes = (uint8_t*)aligned_alloc(16, total16 ? total16 : 16);      // exactly what the contract makes readable
-    memset(bytes, 0, total16 ? total16 : 16);
-    memcpy(bytes, batch.data() + 16 + (n + 1) * 8 + 3 * n_items * 8, (size_t)off[n]);
+    uint8_t* bytes = emul::padded(batch.data() + 16 + (n + 1) * 8 + 3 * n_items * 8, (size_t)off[n]);      // exactly what the contract makes readable
     std::vector<char> out(n, '-');
     std::vector<uint16_t> s_next((kMixLdsMax - kMixTileBytes) / 2u, 0);
     uint64_t fills = 0, slices = 0, held = ~0ull;

@@ -8,34 +8,12 @@
 //       BATCH.bin: u64 n, u64 offsets[n + 1], then offsets[n] bytes.  Every string is cut into chunks of CHUNK bytes, the chunks' maps
 //       are composed as dfa_fold_kernel<RESUME> composes them FROM EVERY START STATE, and the state reached is compared with a plain walk of the
 //       image's table from that state (and with resume_piece).  stdout: "ok STATES CHECKS"; a difference is exit code 5.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "mfa_internal.h"
+#include "emul_common.h"
 #include "dfa_resume_core.h"
 
 using namespace mfa;
-
-static std::vector<uint8_t> slurp(const char* path) {
-    std::vector<uint8_t> v;
-    FILE* f = fopen(path, "rb");
-    if (!f) { perror(path); exit(2); }
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + got);
-    fclose(f);
-    return v;
-}
-
-static uint8_t* padded(const uint8_t* src, size_t total) {
-    uint8_t* bytes = (uint8_t*)aligned_alloc(16, ((total + 15) & ~(size_t)15) + 16);
-    memset(bytes, 0, ((total + 15) & ~(size_t)15) + 16);
-    memcpy(bytes, src, total);
-    return bytes;
-}
 
 // the walk nobody shares: the image's table, byte by byte
 template <bool REV>
@@ -53,7 +31,7 @@ static int run_pieces(const HostImage& img, const std::vector<uint16_t>& next, c
     const uint8_t* pairs = in.data() + 16 + n * 4;
     uint64_t total;
     memcpy(&total, pairs + rounds * n * 16, 8);
-    uint8_t* bytes = padded(pairs + rounds * n * 16 + 8, total);
+    uint8_t* bytes = emul::padded(pairs + rounds * n * 16 + 8, total);
     for (uint64_t r = 0; r < rounds; r++) {
         for (uint64_t k = 0; k < n; k++) {
             uint64_t b, e;
@@ -72,12 +50,11 @@ static int run_pieces(const HostImage& img, const std::vector<uint16_t>& next, c
 }
 
 template <bool REV>
-static int run_fold(const HostImage& img, const std::vector<uint16_t>& next, const std::vector<uint8_t>& batch, uint64_t chunk, uint32_t tile_bytes) {
-    uint64_t n;
-    memcpy(&n, batch.data(), 8);
-    std::vector<uint64_t> off(n + 1);
-    memcpy(off.data(), batch.data() + 8, (n + 1) * 8);
-    uint8_t* bytes = padded(batch.data() + 8 + (n + 1) * 8, (size_t)off[n]);
+static int run_fold(const HostImage& img, const std::vector<uint16_t>& next, const std::vector<uint8_t>& file, uint64_t chunk, uint32_t tile_bytes) {
+    const emul::Batch batch = emul::read_batch(file);
+    const std::vector<uint64_t>& off = batch.off;
+    const uint8_t* bytes = batch.bytes;
+    const uint64_t n = off.size() - 1;
     const uint32_t S = img.dfa_states, ll2 = split_lanes_log2(S), lanes = 1u << ll2, runs = 256u >> ll2, tile_maps = tile_bytes >> ll2;
     std::vector<uint8_t> maps, tile_runs(256);
     uint64_t checks = 0;
@@ -111,24 +88,18 @@ static int run_fold(const HostImage& img, const std::vector<uint16_t>& next, con
         }
     }
     printf("ok %u %llu\n", S, (unsigned long long)checks);
-    free(bytes);
+    free(batch.bytes);
     return 0;
 }
 
 int main(int argc, char** argv) {
     if (argc < 5) { fprintf(stderr, "usage: dfa_resume_emul pieces IMAGE.blob ROUNDS.bin lds|big  |  fold IMAGE.blob BATCH.bin CHUNK TILE_BYTES\n"); return 2; }
     const std::string mode = argv[1];
-    const std::vector<uint8_t> blob = slurp(argv[2]), in = slurp(argv[3]);
     HostImage img;
-    if (parse_blob(blob.data(), blob.size(), img) != MFA_OK || img.h.kind != MFA_KIND_NFA || tabulate_nfa(img) != MFA_OK) { fprintf(stderr, "not a memory-less image\n"); return 2; }
+    emul::load_memoryless(argv[2], img);
+    const std::vector<uint8_t> in = emul::slurp(argv[3]);
     const bool big = mode == "pieces" && std::string(argv[4]) == "big";
-    std::vector<uint16_t> next;                                            // the fused table, as the kernels build it in LDS
-    if (!big) {
-        if (img.dfa_states > 127) { fprintf(stderr, "table does not fit LDS\n"); return 2; }
-        next.assign((size_t)img.dfa_states * kDfaRow, 0);
-        for (uint32_t s = 0; s < img.dfa_states; s++)
-            for (uint32_t b = 0; b < 256; b++) next[s * kDfaRow + b] = (uint16_t)(img.dfa_trans[s * img.n_classes + img.byte_class[b]] * kDfaRow);
-    }
+    const std::vector<uint16_t> next = big ? std::vector<uint16_t>() : emul::fused_table(img);
     if (mode == "pieces") return img.h.is_reversed ? run_pieces<true>(img, next, in, big) : run_pieces<false>(img, next, in, big);
     if (mode == "fold" && argc >= 6) {
         const uint64_t chunk = strtoull(argv[4], nullptr, 10);

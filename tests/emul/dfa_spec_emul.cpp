@@ -6,27 +6,12 @@
 //       one: every string from state 1; every: from every state set of the image but the dead one (the resume form).
 //       The state reached is compared with a plain byte-by-byte walk of the image's table from the same state; a difference is exit code 5.
 //       stdout: "ok STATES CHECKS REWALKED SERIAL_STRINGS SERIAL_BYTES HOME", then one line with the result byte of every string from state 1.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "mfa_internal.h"
+#include "emul_common.h"
 #include "dfa_spec_core.h"
 
 using namespace mfa;
-
-static std::vector<uint8_t> slurp(const char* path) {
-    std::vector<uint8_t> v;
-    FILE* f = fopen(path, "rb");
-    if (!f) { perror(path); exit(2); }
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + got);
-    fclose(f);
-    return v;
-}
 
 // the walk nobody shares: the image's table, byte by byte
 template <bool REV>
@@ -85,15 +70,11 @@ static uint32_t spec_string(const HostImage& img, const uint8_t* bytes, uint64_t
 }
 
 template <bool REV>
-static int run(const HostImage& img, const std::vector<uint8_t>& batch, uint64_t chunk, uint32_t lookback, uint32_t rounds, bool every) {
-    uint64_t n;
-    memcpy(&n, batch.data(), 8);
-    std::vector<uint64_t> off(n + 1);
-    memcpy(off.data(), batch.data() + 8, (n + 1) * 8);
-    const size_t total = (size_t)off[n], room = ((total + 15) & ~(size_t)15) + 16;
-    uint8_t* bytes = (uint8_t*)aligned_alloc(16, room);                    // exactly what the kernels may read: whole 16-byte blocks
-    memset(bytes, 0, room);
-    memcpy(bytes, batch.data() + 8 + (n + 1) * 8, total);
+static int run(const HostImage& img, const std::vector<uint8_t>& file, uint64_t chunk, uint32_t lookback, uint32_t rounds, bool every) {
+    const emul::Batch batch = emul::read_batch(file);                      // exactly what the kernels may read: whole 16-byte blocks
+    const std::vector<uint64_t>& off = batch.off;
+    const uint8_t* bytes = batch.bytes;
+    const uint64_t n = off.size() - 1;
     const uint32_t home = spec_home_state(img.dfa_trans.data(), img.dfa_states, img.n_classes);
     if (home == 0u || home >= img.dfa_states) { fprintf(stderr, "home state %u\n", home); return 5; }
     Counts cnt;
@@ -114,15 +95,15 @@ static int run(const HostImage& img, const std::vector<uint8_t>& batch, uint64_t
     }
     printf("ok %u %llu %llu %llu %llu %u\n%s\n", img.dfa_states, (unsigned long long)checks, (unsigned long long)cnt.rewalked,
            (unsigned long long)cnt.serial_strings, (unsigned long long)cnt.serial_bytes, home, results.c_str());
-    free(bytes);
+    free(batch.bytes);
     return 0;
 }
 
 int main(int argc, char** argv) {
     if (argc < 7) { fprintf(stderr, "usage: dfa_spec_emul IMAGE.blob BATCH.bin CHUNK LOOKBACK ROUNDS one|every\n"); return 2; }
-    const std::vector<uint8_t> blob = slurp(argv[1]), batch = slurp(argv[2]);
     HostImage img;
-    if (parse_blob(blob.data(), blob.size(), img) != MFA_OK || img.h.kind != MFA_KIND_NFA || tabulate_nfa(img) != MFA_OK) { fprintf(stderr, "not a memory-less image\n"); return 2; }
+    emul::load_memoryless(argv[1], img);
+    const std::vector<uint8_t> batch = emul::slurp(argv[2]);
     const uint64_t chunk = strtoull(argv[3], nullptr, 10);
     const uint32_t lookback = (uint32_t)strtoul(argv[4], nullptr, 10), rounds = (uint32_t)strtoul(argv[5], nullptr, 10);
     if (chunk < 16 || (chunk & 15u) || rounds > kSpecRoundsMax) { fprintf(stderr, "bad chunk or rounds\n"); return 2; }

@@ -3,12 +3,7 @@
 // order dfa_plan_kernel, dfa_chunk_kernel and dfa_fold_kernel use it.  Every non-empty string is cut.
 //   dfa_split_emul IMAGE.blob BATCH.bin CHUNK_MIN ARENA_CHUNKS TILE_BYTES
 //   BATCH.bin: u64 n, u64 offsets[n + 1], then offsets[n] bytes.  stdout: "chunk_bytes chunks", then one 0/1 line per string.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "mfa_internal.h"
+#include "emul_common.h"
 
 using namespace mfa;
 
@@ -59,35 +54,14 @@ static void run(const HostImage& img, const std::vector<uint16_t>& next, const u
 
 int main(int argc, char** argv) {
     if (argc < 6) { fprintf(stderr, "usage: dfa_split_emul IMAGE.blob BATCH.bin CHUNK_MIN ARENA_CHUNKS TILE_BYTES\n"); return 2; }
-    auto slurp = [](const char* path) {
-        std::vector<uint8_t> v;
-        FILE* f = fopen(path, "rb");
-        if (!f) { perror(path); exit(2); }
-        uint8_t buf[65536];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + got);
-        fclose(f);
-        return v;
-    };
-    const std::vector<uint8_t> blob = slurp(argv[1]), batch = slurp(argv[2]);
     HostImage img;
-    if (parse_blob(blob.data(), blob.size(), img) != MFA_OK || img.h.kind != MFA_KIND_NFA || tabulate_nfa(img) != MFA_OK) { fprintf(stderr, "not a memory-less image\n"); return 2; }
-    if (img.dfa_states > 127) { fprintf(stderr, "table does not fit LDS\n"); return 2; }
-    std::vector<uint16_t> next((size_t)img.dfa_states * kDfaRow, 0);      // the fused table, as the kernels build it in LDS
-    for (uint32_t s = 0; s < img.dfa_states; s++)
-        for (uint32_t b = 0; b < 256; b++) next[s * kDfaRow + b] = (uint16_t)(img.dfa_trans[s * img.n_classes + img.byte_class[b]] * kDfaRow);
-    uint64_t n;
-    memcpy(&n, batch.data(), 8);
-    std::vector<uint64_t> off(n + 1);
-    memcpy(off.data(), batch.data() + 8, (n + 1) * 8);
-    const size_t total = (size_t)off[n];
-    uint8_t* bytes = (uint8_t*)aligned_alloc(16, ((total + 15) & ~(size_t)15) + 16);
-    memset(bytes, 0, ((total + 15) & ~(size_t)15) + 16);
-    memcpy(bytes, batch.data() + 8 + (n + 1) * 8, total);
+    emul::load_memoryless(argv[1], img);
+    const std::vector<uint16_t> next = emul::fused_table(img);
+    const emul::Batch batch = emul::read_batch(emul::slurp(argv[2]));
     const uint64_t chunk_min = strtoull(argv[3], nullptr, 10), arena = strtoull(argv[4], nullptr, 10);
     const uint32_t tile_bytes = (uint32_t)strtoul(argv[5], nullptr, 10);
-    if (img.h.is_reversed) run<true>(img, next, bytes, off, chunk_min, arena, tile_bytes);
-    else run<false>(img, next, bytes, off, chunk_min, arena, tile_bytes);
-    free(bytes);
+    if (img.h.is_reversed) run<true>(img, next, batch.bytes, batch.off, chunk_min, arena, tile_bytes);
+    else run<false>(img, next, batch.bytes, batch.off, chunk_min, arena, tile_bytes);
+    free(batch.bytes);
     return 0;
 }

@@ -8,27 +8,12 @@
 //       stdout: "ok STATES CLASSES W DEPTH"; a difference is exit code 5.
 //   nfa_set_emul match IMAGE.blob BATCH.bin
 //       BATCH.bin: u64 n, u64 offsets[n + 1], then offsets[n] bytes.  stdout: one result digit per string, then a newline.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "mfa_internal.h"
+#include "emul_common.h"
 #include "nfa_set_core.h"
 
 using namespace mfa;
-
-static std::vector<uint8_t> slurp(const char* path) {
-    std::vector<uint8_t> v;
-    FILE* f = fopen(path, "rb");
-    if (!f) { perror(path); exit(2); }
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + got);
-    fclose(f);
-    return v;
-}
 
 template <int W>
 static int run_step(const HostImage& tab, const HostImage& set, const std::vector<std::string>& sets) {
@@ -65,28 +50,21 @@ static int run_step(const HostImage& tab, const HostImage& set, const std::vecto
 }
 
 template <bool REV, int W>
-static int run_match(const HostImage& set, const std::vector<uint8_t>& batch) {
+static int run_match(const HostImage& set, const std::vector<uint8_t>& file) {
     const NfaSetView t = nfa_set_view(set.set_tables.data(), set.set_tables.data());
     std::vector<uint32_t> stack(t.depth + 1u);
-    uint64_t n;
-    memcpy(&n, batch.data(), 8);
-    std::vector<uint64_t> off(n + 1);
-    memcpy(off.data(), batch.data() + 8, (n + 1) * 8);
-    const size_t total = (size_t)off[n], room = (total + 15) & ~(size_t)15;       // exactly the library's read rule: ASan sees a byte beyond it
-    uint8_t* bytes = (uint8_t*)aligned_alloc(16, room ? room : 16);
-    memset(bytes, 0, room ? room : 16);
-    memcpy(bytes, batch.data() + 8 + (n + 1) * 8, total);
+    const emul::Batch batch = emul::read_batch(file);                            // exactly the library's read rule: ASan sees a byte beyond it
     std::string out;
-    for (uint64_t k = 0; k < n; k++) out.push_back((char)('0' + nfa_set_walk<REV, W>(t, stack.data(), 1u, bytes, off[k], off[k + 1])));
+    for (size_t k = 0; k + 1 < batch.off.size(); k++) out.push_back((char)('0' + nfa_set_walk<REV, W>(t, stack.data(), 1u, batch.bytes, batch.off[k], batch.off[k + 1])));
     puts(out.c_str());
-    free(bytes);
+    free(batch.bytes);
     return 0;
 }
 
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: nfa_set_emul step IMAGE.blob | match IMAGE.blob BATCH.bin\n"); return 2; }
     const std::string mode = argv[1];
-    const std::vector<uint8_t> blob = slurp(argv[2]);
+    const std::vector<uint8_t> blob = emul::slurp(argv[2]);
     HostImage tab, set;
     if (parse_blob(blob.data(), blob.size(), tab) != MFA_OK || tab.h.kind != MFA_KIND_NFA) { fprintf(stderr, "not a memory-less image\n"); return 2; }
     set = tab;
@@ -101,7 +79,7 @@ int main(int argc, char** argv) {
         return BY_W(run_step<1>(tab, set, sets), run_step<2>(tab, set, sets), run_step<4>(tab, set, sets), run_step<8>(tab, set, sets));
     }
     if (mode == "match" && argc >= 4) {
-        const std::vector<uint8_t> batch = slurp(argv[3]);
+        const std::vector<uint8_t> batch = emul::slurp(argv[3]);
         if (rev) return BY_W((run_match<true, 1>(set, batch)), (run_match<true, 2>(set, batch)), (run_match<true, 4>(set, batch)), (run_match<true, 8>(set, batch)));
         return BY_W((run_match<false, 1>(set, batch)), (run_match<false, 2>(set, batch)), (run_match<false, 4>(set, batch)), (run_match<false, 8>(set, batch)));
     }

@@ -15,21 +15,10 @@
 #define WALK_DEV inline
 #include "walk_core.h"
 #include "walk_tables.h"
-#include "mfa_internal.h"
+#include "emul_common.h"
 
 using namespace mfa;
 using namespace mfa_walk;
-
-static std::vector<uint8_t> slurp(const char* path) {
-    std::vector<uint8_t> v;
-    FILE* f = fopen(path, "rb");
-    if (!f) { perror(path); exit(2); }
-    uint8_t buf[65536];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + n);
-    fclose(f);
-    return v;
-}
 
 // region table of one string, from the definition: maximal q-periodic regions (q <= 8) of at least MFA_REGION_MIN_LEN bytes, those
 // covered by a region of a proper divisor period dropped, the 15 longest kept, sorted by start
@@ -116,13 +105,13 @@ int main(int argc, char** argv) {
     uint32_t K = 1, CM = 1;
     bool rev = false;
     for (int a = 1; a < argc; a += (a == 1 ? 3 : 2)) {          // the launch's cell count: the largest of its automata's
-        std::vector<uint8_t> blob = slurp(argv[a]);
+        std::vector<uint8_t> blob = emul::slurp(argv[a]);
         HostImage img;
         if (parse_blob(blob.data(), blob.size(), img) != MFA_OK) { fprintf(stderr, "bad image %s\n", argv[a]); return 2; }
         K = std::max(K, (uint32_t)(img.h.n_cells ? img.h.n_cells : 1));
     }
     for (int a = 1; a < argc; a += (a == 1 ? 3 : 2)) {
-        std::vector<uint8_t> blob = slurp(argv[a]);
+        std::vector<uint8_t> blob = emul::slurp(argv[a]);
         HostImage img;
         if (parse_blob(blob.data(), blob.size(), img) != MFA_OK || check_mfa_invariants(img) != MFA_OK) { fprintf(stderr, "bad image %s\n", argv[a]); return 2; }
         WalkTables wt;

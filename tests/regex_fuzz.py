@@ -11,10 +11,9 @@ import random
 import subprocess
 import tempfile
 
-import oracle_lib
 from mfa_amd import image
+from testlib import DIPLOMA
 
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
 FLAGS = ("-mfa", "-bnf", "-reverse")
 PUMPS = (20, 64, 70, 130, 300, 1000)      # around the region pass's 64-byte minimum, and long enough for chained jumps
 MAX_SAMPLE = 20000                        # a sample that grows beyond this is dropped (nested pumped stars)

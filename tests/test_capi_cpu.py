@@ -1,6 +1,5 @@
 """CPU-side checks of the C-ABI library: it loads, exports every declared symbol, builds images
 (host-only work) and refuses to match without a device.  No compute here."""
-import json
 import os
 import re
 
@@ -9,10 +8,9 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
+from testlib import MANIFEST
 
 ROOT = oracle_lib.ROOT
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
 
 
 def test_exports_match_header():

@@ -1,7 +1,7 @@
 """Memory-less automata on strings given in pieces (mfa_match_batch_resume), the part that can be wrong without a GPU
 (csrc/dfa_resume_core.h: the state a piece is entered with, the sticky error, the walk of a piece and the fold of chunk maps from a given
 state), compiled for the host (tests/emul/dfa_resume_emul.cpp) and run against the CPU restatement; and what the C-ABI answers before it
-touches a device.  The kernels around it are checked by tests/test_dfa_resume_gpu.py, which uses this file's corpus."""
+touches a device.  The kernels around it are checked by tests/test_dfa_resume_gpu.py, on the same corpus (tests/testlib.py)."""
 import ctypes
 import os
 import re
@@ -13,72 +13,12 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from test_dfa_split_cpu import NFA_NAMES, blob_of, out_offsets, strings_for
-
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-ROUNDS = 4
-MAX_BYTES = 0x00ffffff
+from testlib import MAX_BYTES, NFA_NAMES, ROUNDS, blob_of, corpus, cuts_for, emul_exe, out_offsets, rounds_of, seen_so_far, table_66, table_127, write_batch
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dfa_resume_emul") / "dfa_resume_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_dfa_resume.sh"), exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return exe
-
-
-def corpus(name, rev):
-    """the strings of test_dfa_split_cpu.py (0 to 20 000 bytes, packed back to back: a start at every offset mod 16), mirrored for the
-    reversed scan, with their image and the direction that image scans in (rev = 0 leaves a fixture the direction it was compiled with:
-    nfa_abb_plain scans from the end either way)"""
-    rng = np.random.default_rng(len(name) * 131 + rev)
-    strings = strings_for(name, rng)
-    if rev:
-        strings = [s[::-1] for s in strings]
-    blob = blob_of(name, rev)
-    return blob, strings, image.blob_info(blob)["reversed"]
-
-
-def cuts_for(strings, rng):
-    """string k -> its cut points [0, c1, .., len]: 1 to 4 pieces at seeded random points; empty pieces (at either end and in the
-    middle) and, in the packed buffer, a cut at every residue mod 16"""
-    off = out_offsets(strings)
-    cuts = []
-    for k, s in enumerate(strings):
-        inner = sorted(int(x) for x in rng.integers(0, len(s) + 1, size=k % ROUNDS))
-        if inner and len(s) >= 32:                         # the first cut lands on residue k mod 16 of the buffer
-            inner[0] = (k % 16 - off[k]) % 16 + 16 * int(rng.integers(0, (len(s) - 16) // 16))
-            inner.sort()
-        if inner and k % 5 == 0:
-            inner[0] = 0                                   # an empty first piece
-        if inner and k % 7 == 0:
-            inner[-1] = len(s)                             # an empty last piece
-        if len(inner) >= 2 and k % 3 == 0:
-            inner[1] = inner[0]                            # an empty piece in the middle
-        cuts.append([0] + sorted(inner) + [len(s)])
-    return cuts
-
-
-def rounds_of(strings, cuts, rev):
-    """ROUNDS lists of (begin, end) per string, relative to the string, IN SCAN ORDER: a reversed automaton is given the last piece
-    first.  A string with fewer pieces gets empty ones behind its last"""
-    out = []
-    for r in range(ROUNDS):
-        row = []
-        for s, c in zip(strings, cuts):
-            pieces = list(zip(c[:-1], c[1:]))
-            if rev:
-                pieces = pieces[::-1]
-            done = 0 if rev else len(s)
-            row.append(pieces[r] if r < len(pieces) else (done, done))
-        out.append(row)
-    return out
-
-
-def seen_so_far(strings, rounds, r, rev):
-    """what string k has been given up to and including round r: a prefix, or for the reversed scan a suffix"""
-    return [s[rounds[r][k][0]:] if rev else s[:rounds[r][k][1]] for k, s in enumerate(strings)]
+def emul():
+    return emul_exe("dfa_resume")
 
 
 def run_pieces(emul, tmp_path, blob, data, total, states_in, pairs, form):
@@ -148,27 +88,6 @@ def test_sticky_error_and_dead_state(emul, tmp_path):
         assert (int(st[0][0]), int(res[0][0])) == (capi.DFA_STATE_DEAD, 0)
 
 
-def front_end_blob(regex, tmp_path, rev=0, flag="-thompson"):
-    """the host front-end's automaton for `regex`; rev = 1 forces the reversed scan on it, as blob_of does for a fixture"""
-    p = subprocess.run([DIPLOMA, "-dump", flag], input=regex + "\n", capture_output=True, text=True, cwd=tmp_path)
-    assert p.returncode == 0, p.stderr
-    d = image.parse_dump(p.stdout)
-    if rev:
-        d["reversed"] = 1
-    return image.to_blob(d)
-
-
-def table_66(tmp_path, rev=0):
-    """(a|b)*a(a|b)^5: 66 state sets (tests/test_dfa_split_gpu.py)"""
-    return front_end_blob("(a|b)*a" + "(a|b)" * 5, tmp_path, rev)
-
-
-def table_127(tmp_path, rev=0):
-    """127 state sets, the most an LDS table holds (tests/test_dfa_split_gpu.py)"""
-    ab = "(a|b)"
-    return front_end_blob("(a|b)*(a" + ab * 5 + "|b" + ab * 4 + "a)" + "(c|d)" * 7 + "c*", tmp_path, rev)
-
-
 @pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
 @pytest.mark.parametrize("states", [66, 127])
 def test_fold_from_every_start_state(emul, states, rev, tmp_path):
@@ -182,9 +101,8 @@ def test_fold_from_every_start_state(emul, states, rev, tmp_path):
     strings += [alpha[rng.integers(0, 2, size=900)].tobytes() + b"abbbbbcdcdcdcccc", b"ab" * 700 + b"abbbbb"]
     if rev:
         strings = [s[::-1] for s in strings]
-    data, off = oracle_lib.pack(strings)
     (tmp_path / "a.blob").write_bytes(blob)
-    (tmp_path / "batch.bin").write_bytes(struct.pack("<Q", len(strings)) + off.astype("<u8").tobytes() + data.tobytes()[:int(off[-1])])
+    write_batch(tmp_path / "batch.bin", strings)
     for chunk, tile in ((16, 2048), (48, 512), (256, 32768), (4096, 32768)):
         p = subprocess.run([emul, "fold", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin"), str(chunk), str(tile)], capture_output=True)
         assert p.returncode == 0, p.stderr.decode()[-400:]
@@ -229,4 +147,4 @@ def test_constants_equal_the_header():
     got = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+MFA_DFA_STATE_(\w+)\s+(0x[0-9a-fA-F]+|\d+)u", hdr)}
     assert got == {"DEAD": capi.DFA_STATE_DEAD, "START": capi.DFA_STATE_START, "INVALID": capi.DFA_STATE_INVALID}
     assert (capi.DFA_STATE_DEAD, capi.DFA_STATE_START, capi.DFA_STATE_INVALID) == (0, 1, 0xffffffff)
-    assert int(re.search(r"#define\s+MFA_MAX_STRING_BYTES\s+(0x[0-9a-fA-F]+)u", hdr).group(1), 16) == MAX_BYTES
+    assert int(re.search(r"#define\s+MFA_MAX_STRING_BYTES\s+(0x[0-9a-fA-F]+)u", hdr).group(1), 16) == MAX_BYTES == 0x00ffffff

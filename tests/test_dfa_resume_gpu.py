@@ -1,8 +1,7 @@
 """Memory-less automata on strings given in pieces, on the GPU: mfa_match_batch_resume (the resume instantiations of csrc/kernels.hip, and the fold of
 csrc/dfa_split.hip started from a given state) against the CPU restatement and against the plain batch call, on the corpus of
-tests/test_dfa_resume_cpu.py; every table form; strings beyond MFA_MAX_STRING_BYTES; the sticky error; streams and capture; the host
+tests/test_dfa_resume_cpu.py (tests/testlib.py); every table form; strings beyond MFA_MAX_STRING_BYTES; the sticky error; streams and capture; the host
 mirror and the command line on top of it."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,54 +9,14 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from test_dfa_resume_cpu import MAX_BYTES, ROUNDS, corpus, cuts_for, front_end_blob, rounds_of, seen_so_far, table_66, table_127
-from test_dfa_split_cpu import NFA_NAMES, blob_of
-from test_dfa_split_gpu import rnd, scan_poke
+from testlib import (DEAD, DIPLOMA, INVALID, MAX_BYTES, NFA_NAMES, ROUNDS, START, accepted_long, blob_of, corpus, cuts_for, feed, filled, front_end_blob,
+                     manifest_entry, match_on_gpu, new_states, rnd, rounds_of, scan_poke, seen_so_far, states_of, table_66, table_127, upload)
 
 pytestmark = pytest.mark.gpu
 
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-START, DEAD, INVALID = capi.DFA_STATE_START, capi.DFA_STATE_DEAD, capi.DFA_STATE_INVALID
-
-
-def upload(strings):
-    import torch
-    data, off = oracle_lib.pack(strings)
-    d_bytes = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
-    d_bytes[:len(data)] = torch.from_numpy(data.copy())
-    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda()
-
-
-def new_states(n, value=START):
-    import torch
-    return torch.from_numpy(np.full(max(n, 1), value, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def states_of(d_states, n):
-    return d_states.cpu().numpy().view(np.uint32)[:n].copy()
-
-
-def feed(img, pieces, d_states, results=True, stream=None):
-    """one round: the pieces of all strings through mfa_match_batch_resume; returns the result bytes (None without results)"""
-    import torch
-    d_bytes, d_off = upload(pieces)
-    res = torch.full((max(len(pieces), 1),), 7, dtype=torch.uint8, device="cuda") if results else None
-    img.match_tensors_resume(d_bytes, d_off, d_states, res, stream=stream)
-    torch.cuda.synchronize()
-    return res[:len(pieces)].cpu().numpy() if results else None
-
-
-def plain(img, strings):
-    import torch
-    d_bytes, d_off = upload(strings)
-    res = torch.full((max(len(strings), 1),), 7, dtype=torch.uint8, device="cuda")
-    img.match_tensors(d_bytes, d_off, res)
-    torch.cuda.synchronize()
-    return res[:len(strings)].cpu().numpy()
-
 
 def pieces_against_whole(img, blob, strings, rng, what, oracle_rounds=True):
-    """the strings cut as tests/test_dfa_resume_cpu.py cuts them, fed in ROUNDS rounds in scan order (a string with fewer pieces gets
+    """the strings cut as tests/test_dfa_resume_cpu.py cuts them (testlib.cuts_for), fed in ROUNDS rounds in scan order (a string with fewer pieces gets
     empty ones): every round's results against the oracle on what has been given so far; final states against ONE call on the whole
     strings; that call's results against mfa_match_batch and the oracle"""
     is_rev = image.blob_info(blob)["reversed"]
@@ -75,7 +34,7 @@ def pieces_against_whole(img, blob, strings, rng, what, oracle_rounds=True):
     d_whole = new_states(n)
     whole = feed(img, strings, d_whole)
     assert np.array_equal(states_of(d_states, n), states_of(d_whole, n)), what
-    assert np.array_equal(whole, plain(img, strings)) and np.array_equal(whole, got), what
+    assert np.array_equal(whole, match_on_gpu(img, strings)[0]) and np.array_equal(whole, got), what
     assert int(states_of(d_whole, n).max()) < img.info()["dfa_states"]
     assert img.info()["last_kernel"] == capi.KERNEL_TABLE
 
@@ -142,7 +101,7 @@ def test_table_between_lds_and_l2(rev, tmp_path):
     d_whole = new_states(n)
     assert np.array_equal(feed(img, strings, d_whole), want) and np.array_equal(states_of(d_states, n), states_of(d_whole, n))
     with pytest.raises(capi.MfaError) as err:
-        plain(img, strings)
+        match_on_gpu(img, strings)
     assert err.value.code == capi.ERR_UNSUPPORTED
 
 
@@ -203,7 +162,7 @@ def test_sticky_errors_and_dead_on_entry():
     off = torch.tensor([0, 4, 8, e, e + 3, e + 5, e + 8], dtype=torch.int64, device="cuda")
     st_in = np.array([n_states, INVALID, START, START, DEAD, START], dtype=np.uint32)
     d_states = torch.from_numpy(st_in.view(np.int32)).cuda()
-    res = torch.full((6,), 7, dtype=torch.uint8, device="cuda")
+    res = filled(6)
     img.match_tensors_resume(big, off, d_states, res)
     torch.cuda.synchronize()
     st = states_of(d_states, 6)
@@ -248,7 +207,7 @@ def test_two_streams_one_image():
         strings = [rnd(b"ab", ln, rng) for ln in lens]
         strings = [s[:-3] + b"abb" if (k + v) % 2 and len(s) >= 3 else s for k, s in enumerate(strings)]
         rounds = [upload([s[r * len(s) // 3:(r + 1) * len(s) // 3] for s in strings]) for r in range(3)]
-        work.append((rounds, new_states(len(lens)), torch.full((len(lens),), 7, dtype=torch.uint8, device="cuda"), ora.match(strings)))
+        work.append((rounds, new_states(len(lens)), filled(len(lens)), ora.match(strings)))
     assert not np.array_equal(work[0][3], work[1][3])
     torch.cuda.synchronize()
     for r in range(3):
@@ -272,9 +231,9 @@ def test_resume_call_is_capturable():
     second[3] = b"bab"
     whole = [a + b for a, b in zip(first, second)]
     want_first, want_whole = oracle_lib.OracleImage(blob).match(first), oracle_lib.OracleImage(blob).match(whole)
-    d_bytes, d_off = upload(first)
+    d_bytes, d_off, _ = upload(first)
     d_states = new_states(len(first))
-    res = torch.full((len(first),), 7, dtype=torch.uint8, device="cuda")
+    res = filled(len(first))
     img = capi.Image(blob)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -311,19 +270,12 @@ def test_host_entry_point():
 
 
 # ---- the host mirror and the command line ----------------------------------------------------------------------------------------------
-def _manifest(name):
-    import json
-    with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-        return next(a for a in json.load(f)["automata"] if a["name"] == name)
-
-
 @pytest.mark.parametrize("name", ["nfa_abb_plain", "nfa_alt3_plain"])
 def test_cli_tokens_beyond_the_limit(name, tmp_path):
     """`diploma -match` with tokens of 20 MiB + 5 -- one accepted, one rejected by its last byte -- between two short ones: 0/1 lines as
     for any token, the header unchanged.  (a|b)*abb compiles to an automaton that scans from the END (the pieces go last first), the
     other regex to one that scans from the front.  `diploma -match-blocks` (an Automata::Stream fed 1 MiB at a time) agrees."""
-    from test_dfa_split_gpu import accepted_long
-    auto = _manifest(name)
+    auto = manifest_entry(name)
     blob = blob_of(name, 0)
     assert image.blob_info(blob)["reversed"] == (1 if name == "nfa_abb_plain" else 0)
     rng = np.random.default_rng(20)
@@ -344,7 +296,7 @@ def test_cli_tokens_beyond_the_limit(name, tmp_path):
 
 def test_cli_memory_regex_still_refuses_a_long_token(tmp_path):
     """a regex with memory: a token beyond the limit fails as it always has (MFA_ERR_TOO_LONG from the host entry point), a short one is matched"""
-    auto = _manifest("ex1_plain")
+    auto = manifest_entry("ex1_plain")
     text = auto["regex"].encode() + b"\n" + b"aa\n" + b"a" * (MAX_BYTES + 1) + b"\nexit\n"
     p = subprocess.run([DIPLOMA, "-match"], input=text, capture_output=True, cwd=tmp_path)
     assert p.returncode != 0 and b"MFA_MAX_STRING_BYTES" in p.stderr

@@ -2,40 +2,19 @@
 (csrc/dfa_spec_core.h: the lookback range, the guess from two seeds, when a chunk is walked again, the resolve loop over the chunks'
 records, the home state), compiled for the host (tests/emul/dfa_spec_emul.cpp) and run one lane at a time -- round 0, the repair rounds,
 resolve -- against a plain walk of the table (inside the harness) and against the CPU restatement.  The kernels around it are checked by
-tests/test_dfa_spec_gpu.py, which uses this file's tables."""
-import os
-import struct
+tests/test_dfa_spec_gpu.py, on the same tables (tests/testlib.py: TABLES)."""
 import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib
-from mfa_amd import capi, image
+from mfa_amd import capi
+from testlib import TABLES, emul_exe, table_blob, write_batch
 
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
 CHUNKS = (16, 48, 4096)
 LOOKBACKS = (0, 16, 256)
 ROUNDS = (0, 1, 3)
-
-# name -> (regex, state sets).  t514: the state is the last nine bytes, every guess with nine bytes of lookback is right.  counter: (a^300)*,
-# the state is a position modulo 300 and never converges.  prefix: a literal in front of t514, so a walk from {start} dies in mid-text.
-TABLES = {
-    "t514": ("(a|b)*a" + "(a|b)" * 8, 514),
-    "counter": ("(" + "a" * 300 + ")*", None),
-    "prefix": ("xyz(a|b)*a" + "(a|b)" * 8, None),
-}
-
-
-def table_blob(name, tmp_path, rev=0):
-    """the host front-end's automaton; rev = 1 makes the same automaton scan from the end (the mirrored language)"""
-    p = subprocess.run([DIPLOMA, "-dump", "-thompson"], input=TABLES[name][0] + "\n", capture_output=True, text=True, cwd=tmp_path)
-    assert p.returncode == 0, p.stderr
-    d = image.parse_dump(p.stdout)
-    if rev:
-        d["reversed"] = 1
-    return image.to_blob(d)
 
 
 def text_for(name, ln, rng, k=0):
@@ -76,10 +55,8 @@ def batch_for(name, chunk, rev, rng):
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dfa_spec_emul") / "dfa_spec_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_dfa_spec.sh"), exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return exe
+def emul():
+    return emul_exe("dfa_spec")
 
 
 def run_emul(emul, tmp_path, chunk, lookback, rounds, mode):
@@ -93,9 +70,8 @@ def run_emul(emul, tmp_path, chunk, lookback, rounds, mode):
 
 
 def write_case(tmp_path, blob, strings):
-    data, off = oracle_lib.pack(strings)
     (tmp_path / "a.blob").write_bytes(blob)
-    (tmp_path / "batch.bin").write_bytes(struct.pack("<Q", len(strings)) + off.astype("<u8").tobytes() + data.tobytes()[:int(off[-1])])
+    write_batch(tmp_path / "batch.bin", strings)
 
 
 @pytest.mark.parametrize("chunk", CHUNKS)

@@ -1,16 +1,14 @@
 """Long strings of memory-less automata whose table lives in L2 (255 state sets and more) on the GPU: csrc/dfa_spec.hip cuts a string of
 MFA_DFA_SPLIT_MIN bytes or more into chunks, walks every chunk from a guessed state, repairs wrong guesses in a fixed number of rounds and
 resolves the rest exactly.  Answers against the CPU restatement and against the same call with MFA_DFA_SPEC=0; what the path did through
-mfa_last_dfa_split and mfa_last_dfa_spec.  Tables and knobs of tests/test_dfa_spec_cpu.py."""
+mfa_last_dfa_split and mfa_last_dfa_spec.  Tables of tests/test_dfa_spec_cpu.py (tests/testlib.py: TABLES)."""
 import numpy as np
 import pytest
 
 import oracle_lib
-from mfa_amd import capi, image
-from test_dfa_resume_cpu import front_end_blob
-from test_dfa_resume_gpu import DEAD, INVALID, START, feed, new_states, states_of
-from test_dfa_spec_cpu import table_blob
-from test_dfa_split_gpu import CHUNK_MIN, SPLIT_MIN, check, expected_split, fixture_blob, gpu_match, rnd, short_strings, upload
+from mfa_amd import capi
+from testlib import (CHUNK_MIN, DEAD, INVALID, SPLIT_MIN, START, check, expected_split, feed, filled, fixture_blob, front_end_blob, match_on_gpu, mixed_match,
+                     new_states, rnd, short_strings, states_of, table_blob, upload)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +18,7 @@ SMALL_MIN, SMALL_CHUNK = 256, 64
 def prime(img):
     """A launch workspace of an L2-table image starts quiet: its first batch with a long string is walked whole by the main kernel, which tells
     the workspace, and from the next call on (same stream) long strings are cut.  One such batch, checked to have been walked whole."""
-    got, _ = gpu_match(img, [b"ab" * 40000, b"ab"])
+    got, _ = match_on_gpu(img, [b"ab" * 40000, b"ab"])
     assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
     return got
 
@@ -48,7 +46,7 @@ def test_small_knob_parity(states, rev, tmp_path, monkeypatch):
     want = oracle_lib.OracleImage(blob).match(strings)
     assert 0 < want.sum() < len(strings)
     prime(img)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "%d state sets, rev %d" % (states, rev))
     n_long, chunks, chunk = img.last_dfa_split()
     print("split", (n_long, chunks, chunk), "spec", img.last_dfa_spec())
@@ -56,7 +54,7 @@ def test_small_knob_parity(states, rev, tmp_path, monkeypatch):
     assert (n_long, chunks, chunk) == expected_split(off, SMALL_MIN, SMALL_CHUNK)
     assert img.last_dfa_spec()[1:] == (0, 0)                  # the state is the last k + 1 bytes: 256 bytes of lookback make every guess right
     monkeypatch.setenv("MFA_DFA_SPEC", "0")
-    plain, _ = gpu_match(img, strings)
+    plain, _ = match_on_gpu(img, strings)
     assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
     check(got, plain, strings, "against the same call without the path")
 
@@ -73,10 +71,10 @@ def test_default_knobs(tmp_path):
     assert (want[1], want[4]) == (1, 0)
     img = capi.Image(blob)
     assert img.info()["dfa_states"] == 514
-    got, off = gpu_match(img, strings)                         # a fresh workspace: walked whole this once, and right
+    got, off = match_on_gpu(img, strings)                         # a fresh workspace: walked whole this once, and right
     check(got, want, strings, "default knobs, first call")
     assert img.last_dfa_split() == (0, 0, 0)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "default knobs")
     print("split", img.last_dfa_split(), "spec", img.last_dfa_spec())
     assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN) and img.last_dfa_split()[0] == 2
@@ -105,7 +103,7 @@ def test_tables_that_guess_badly(name, rev, rounds, tmp_path, monkeypatch):
     img = capi.Image(blob)
     assert img.info()["dfa_states"] >= 255
     prime(img)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "%s rev %d rounds %d" % (name, rev, rounds))
     assert img.last_dfa_split() == expected_split(off, SMALL_MIN, SMALL_CHUNK)
     rewalked, serial_strings, serial_bytes = img.last_dfa_spec()
@@ -222,7 +220,7 @@ def test_plain_call_with_the_split_off(rev, tmp_path, monkeypatch):
     assert img.info()["dfa_states"] == 514
     prime(img)
     monkeypatch.setenv("MFA_DFA_SPLIT", "0")
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "MFA_DFA_SPLIT=0, rev %d" % rev)
     assert expected_split(off, SMALL_MIN, SMALL_CHUNK)[0] > 0
     assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
@@ -239,20 +237,20 @@ def test_quiet_workspace_hands_long_strings_over(tmp_path):
     want_short, want_long = ora.match(short), ora.match(longs)
     img = capi.Image(blob)
     for call in range(8):                                      # quiet after four calls that reported no long string
-        got, _ = gpu_match(img, short)
+        got, _ = match_on_gpu(img, short)
         check(got, want_short, short, "short batch, call %d" % call)
         assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
-    got, off = gpu_match(img, longs)
+    got, off = match_on_gpu(img, longs)
     check(got, want_long, longs, "long strings in a call without the tail")
     assert img.last_dfa_split() == (0, 0, 0)                   # walked whole, this once
     cut = expected_split(off, SPLIT_MIN, CHUNK_MIN)
     assert cut[0] == 2
     for round_ in range(2):
-        got, _ = gpu_match(img, longs)
+        got, _ = match_on_gpu(img, longs)
         check(got, want_long, longs, "long strings again")
         assert img.last_dfa_split() == cut
         for call in range(6):
-            got, _ = gpu_match(img, short)
+            got, _ = match_on_gpu(img, short)
             check(got, want_short, short, "short batch after long ones")
             assert img.last_dfa_split() == (0, 0, 0)
 
@@ -271,7 +269,7 @@ def test_call_is_capturable(tmp_path):
     ora = oracle_lib.OracleImage(blob)
     want_first, want_second = ora.match(first), ora.match(second)
     d_bytes, d_off, off = upload(first)
-    res = torch.full((len(lens),), 7, dtype=torch.uint8, device="cuda")
+    res = filled(len(lens))
     img = capi.Image(blob)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -297,7 +295,6 @@ def test_call_is_capturable(tmp_path):
 
 def test_in_a_mixed_batch(tmp_path, monkeypatch):
     """a mixed object with the 514-state image beside nfa_abb_plain and ex1_plain: the L2 segment gets a launch of its own, its long string is cut"""
-    from test_mixed_dfa_gpu import mixed_match
     small_knobs(monkeypatch)
     blobs = [fixture_blob("nfa_abb_plain"), front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path, 0), fixture_blob("ex1_plain")]
     imgs = [capi.Image(b) for b in blobs]

@@ -1,9 +1,6 @@
 """Long strings of memory-less automata on the GPU: the split path (csrc/dfa_split.hip) cuts a string of MFA_DFA_SPLIT_MIN bytes or
 more into chunks, walks the chunks side by side for every start state and composes their maps.  Answers against the CPU
 restatement and against the same call with MFA_DFA_SPLIT=0; what the path did through mfa_last_dfa_split."""
-import json
-import os
-import random
 import subprocess
 
 import numpy as np
@@ -11,107 +8,10 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
+from testlib import (CHUNK_MIN, DIPLOMA, MAX_BYTES, NFA_NAMES, SPLIT_MIN, accepted_long, check, expected_split, filled, fixture_blob, front_end_blob,
+                     manifest_entry, match_on_gpu, rnd, scan_poke, short_strings, upload)
 
 pytestmark = pytest.mark.gpu
-
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
-NFA_NAMES = [a["name"] for a in MANIFEST["automata"] if a["name"].startswith("nfa_")]
-MAX_BYTES = 0x00ffffff
-SPLIT_MIN, CHUNK_MIN, ARENA = 65536, 4096, 131072           # the library's defaults (include/mfa_hip.h)
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-
-
-def upload(strings):
-    import torch
-    data, off = oracle_lib.pack(strings)
-    d_bytes = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
-    d_bytes[:len(data)] = torch.from_numpy(data.copy())
-    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda(), off
-
-
-def gpu_match(img, strings):
-    import torch
-    d_bytes, d_off, off = upload(strings)
-    res = torch.full((max(len(strings), 1),), 7, dtype=torch.uint8, device="cuda")
-    img.match_tensors(d_bytes, d_off, res)
-    torch.cuda.synchronize()
-    return res[:len(strings)].cpu().numpy(), off
-
-
-def expected_split(off, split_min, chunk_min, arena=ARENA):
-    """what mfa_last_dfa_split must report for a batch with these offsets (the formulas of the header)"""
-    spans = [(int(b), int(e)) for b, e in zip(off[:-1], off[1:]) if int(e) - int(b) >= split_min]
-    if not spans:
-        return (0, 0, 0)
-    long_bytes = sum(e - b for b, e in spans)
-    chunk = max(chunk_min, (long_bytes // arena + 15) // 16 * 16)
-    return (len(spans), sum((e - (b & ~15) + chunk - 1) // chunk for b, e in spans), chunk)
-
-
-def rnd(alpha, n, rng):
-    return (np.frombuffer(alpha, dtype=np.uint8)[rng.integers(0, len(alpha), size=n)]).tobytes()
-
-
-def accepted_long(name, n, rng):
-    """a string of exactly n bytes (n >= 6000) that the fixture accepts -- all but the four nfa_dot_*, which die on every input tried"""
-    if name.startswith(("nfa_abb", "nfa_third")):
-        return rnd(b"ab", n - 3, rng) + b"abb"
-    if name.startswith("nfa_enum"):
-        return rnd(b"abc", n - 3, rng) + b"abc"
-    if name.startswith("nfa_star1"):
-        return rnd(b"ab", n - 2, rng) + b"ab"
-    if name.startswith("nfa_star2"):
-        return rnd(b"ab", n - 1, rng) + b"a"
-    if name.startswith("nfa_alt3"):
-        tail = 5000 + (n & 1)
-        words = np.array([[97, 98], [98, 97]], dtype=np.uint8)[rng.integers(0, 2, size=(n - 2 - tail) // 2)]
-        return b"ab" + words.tobytes() + b"c" * tail
-    if name.startswith("nfa_star4"):
-        words = [b"ab", b"c", b"cc", b"abab"]
-        idx = rng.integers(0, 4, size=n)
-        cum = np.cumsum(np.array([2, 1, 2, 4])[idx])
-        m = int(np.searchsorted(cum, n - 1, side="right"))
-        body = b"".join(words[i] for i in idx[:m].tolist())
-        return body + b"c" * (n - 1 - len(body)) + b"a"
-    return rnd(b"ab", n, rng)
-
-
-def scan_poke(s, k, is_rev):
-    """s with the k-th byte IN SCAN ORDER replaced by z (k < 0: from the end of the scan)"""
-    i = k if k >= 0 else len(s) + k
-    if is_rev:
-        i = len(s) - 1 - i
-    return s[:i] + b"z" + s[i + 1:]
-
-
-def short_strings(rng, count=300):
-    """the ragged batch of test_gpu_parity.py: test_table_walk_whole_lines"""
-    out = []
-    for k, ln in enumerate(int(x) for x in rng.integers(0, 700, size=count)):
-        t = bytes(rng.choice(list(b"ab" if k % 4 else b"abc."), size=ln).tolist())
-        if k % 3 == 0 and ln >= 3:
-            t = t[:-3] + b"abb"
-        out.append(t)
-    return out
-
-
-def fixture_blob(name, rev=None):
-    d = image.parse_dump(oracle_lib.load_dump(name))
-    if rev is not None:
-        d["reversed"] = rev
-    return image.to_blob(d)
-
-
-def front_end_blob(regex, tmp_path, flag):
-    p = subprocess.run([DIPLOMA, "-dump", flag], input=regex + "\n", capture_output=True, text=True, cwd=tmp_path)
-    assert p.returncode == 0, p.stderr
-    return image.blob_from_dump(p.stdout)
-
-
-def check(got, want, strings, what):
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, "%s: %d mismatches, first string %d (len %d) want %d got %d" % (what, bad.size, bad[0], len(strings[bad[0]]), want[bad[0]], got[bad[0]])
 
 
 @pytest.mark.parametrize("name", NFA_NAMES)
@@ -127,7 +27,7 @@ def test_parity_at_real_size(name):
     strings.insert(200, b"")
     want = oracle_lib.OracleImage(blob).match(strings)
     img = capi.Image(blob)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, name)
     assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN) and img.last_dfa_split()[0] == 4
     assert img.info()["last_kernel"] == capi.KERNEL_TABLE
@@ -159,11 +59,11 @@ def test_parity_at_every_border(name, rev, chunk, monkeypatch):
     assert {int(o) % 16 for o, ln in zip(off[:-1], lens) if ln >= 256} == set(range(16))
     want = oracle_lib.OracleImage(blob).match(strings)
     img = capi.Image(blob)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "%s rev %d chunk %d" % (name, rev, chunk))
     assert img.last_dfa_split() == expected_split(off, 256, chunk) and img.last_dfa_split()[2] == chunk
     monkeypatch.setenv("MFA_DFA_SPLIT", "0")
-    plain, _ = gpu_match(img, strings)
+    plain, _ = match_on_gpu(img, strings)
     assert img.last_dfa_split() == (0, 0, 0)
     check(got, plain, strings, "against the same call without the split path")
 
@@ -172,7 +72,7 @@ def test_largest_table_in_lds(tmp_path):
     """127 state sets, the most the path takes: the chunk kernel's table is 65 532 bytes of LDS, 128 lanes per chunk"""
     ab = "(a|b)"
     regex = "(a|b)*(a" + ab * 5 + "|b" + ab * 4 + "a)" + "(c|d)" * 7 + "c*"
-    blob = front_end_blob(regex, tmp_path, "-thompson")
+    blob = front_end_blob(regex, tmp_path)
     img = capi.Image(blob)
     assert img.info()["dfa_states"] == 127
     rng = np.random.default_rng(127)
@@ -181,7 +81,7 @@ def test_largest_table_in_lds(tmp_path):
     strings = [body + b"abbbbb" + tail + b"ccc", body + b"babbba" + tail, body + b"bbbbbb" + tail, body + b"abbbbb" + tail + b"d", b"", body[:500] + b"aaaaaa" + tail,
                body[:70000] + b"aaaaaa" + tail + b"c" * 300000]
     want = oracle_lib.OracleImage(blob).match(strings)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "127 state sets")
     assert list(want[:4]) == [1, 1, 0, 0]
     assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN) and img.last_dfa_split()[0] == 5
@@ -203,20 +103,20 @@ def test_quiet_workspace_hands_long_strings_over(kernel, monkeypatch):
     assert want_long[40] == 1 and want_long[41] == 0 and want_long[43] == 1
     img = capi.Image(blob)
     for call in range(8):                                      # quiet after four calls that reported no long string
-        got, _ = gpu_match(img, short)
+        got, _ = match_on_gpu(img, short)
         check(got, want_short, short, "short batch, call %d" % call)
         assert img.last_dfa_split() == (0, 0, 0)
-    got, off = gpu_match(img, longs)
+    got, off = match_on_gpu(img, longs)
     check(got, want_long, longs, "long strings in a call without split kernels")
     assert img.last_dfa_split() == (0, 0, 0)                   # walked whole, this once
     cut = expected_split(off, SPLIT_MIN, CHUNK_MIN)
     assert cut[0] == 3
     for round_ in range(2):
-        got, _ = gpu_match(img, longs)
+        got, _ = match_on_gpu(img, longs)
         check(got, want_long, longs, "long strings again")
         assert img.last_dfa_split() == cut
         for call in range(8):
-            got, _ = gpu_match(img, short)
+            got, _ = match_on_gpu(img, short)
             check(got, want_short, short, "short batch after long ones")
             assert img.last_dfa_split() == (0, 0, 0)
 
@@ -225,14 +125,14 @@ def test_more_state_sets_than_a_wave_and_the_limit(tmp_path):
     """(a|b)*a(a|b)^k: 66 state sets at k = 5 (more than 64: a chunk's start states take two waves) are cut, a table beyond LDS (k = 8) is not"""
     rng = np.random.default_rng(58)
     for k, cut in ((5, True), (8, False)):
-        blob = front_end_blob("(a|b)*a" + "(a|b)" * k, tmp_path, "-thompson")
+        blob = front_end_blob("(a|b)*a" + "(a|b)" * k, tmp_path)
         img = capi.Image(blob)
         states = img.info()["dfa_states"]
         assert (65 <= states <= 127) if cut else states > 127
         body = rnd(b"ab", 2 << 20, rng)
         strings = [body[:-(k + 1)] + b"a" + b"b" * k, body[:-(k + 1)] + b"b" + b"a" * k, b"", body[:1000], b"a" + b"b" * k]
         want = oracle_lib.OracleImage(blob).match(strings)
-        got, off = gpu_match(img, strings)
+        got, off = match_on_gpu(img, strings)
         check(got, want, strings, "k = %d" % k)
         assert list(want[:2]) == [1, 0]
         assert img.last_dfa_split() == (expected_split(off, SPLIT_MIN, CHUNK_MIN) if cut else (0, 0, 0))
@@ -250,7 +150,7 @@ def test_death_and_survival(name):
     strings = [ok, scan_poke(ok, -1, is_rev), scan_poke(ok, 5, is_rev), scan_poke(ok, 70000, is_rev), b"ab"]
     want = oracle_lib.OracleImage(blob).match(strings)
     img = capi.Image(blob)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, name)
     assert img.last_dfa_split() == expected_split(off, SPLIT_MIN, CHUNK_MIN)
     if not name.startswith("nfa_dot"):
@@ -277,7 +177,7 @@ def test_one_image_two_streams_back_to_back():
     outs = []
     for call in range(20):
         d_bytes, d_off, want, off = batches[call % 2]
-        res = torch.full((len(lens),), 7, dtype=torch.uint8, device="cuda")
+        res = filled(len(lens))
         img.match_tensors(d_bytes, d_off, res, stream=streams[(call // 2) % 2])
         outs.append((res, want))
     torch.cuda.synchronize()
@@ -294,7 +194,7 @@ def test_arena_pressure(monkeypatch):
     strings = [rnd(b"ab", n, rng) for n in (1 << 20, 40, 3 << 20, 70000, 0, (1 << 20) + 13)]
     want = oracle_lib.OracleImage(blob).match(strings)
     img = capi.Image(blob)
-    got, off = gpu_match(img, strings)
+    got, off = match_on_gpu(img, strings)
     check(got, want, strings, "arena of 100 chunks")
     n_long, chunks, chunk = img.last_dfa_split()
     long_bytes = (1 << 20) + (3 << 20) + 70000 + (1 << 20) + 13
@@ -305,7 +205,7 @@ def test_arena_pressure(monkeypatch):
 
 def test_through_the_layers(tmp_path):
     """`./diploma -match` with one 4 MiB token (a large file without blanks is one string), and mfa_match_batch_host on the same string"""
-    auto = next(a for a in MANIFEST["automata"] if a["name"] == "nfa_abb_plain")
+    auto = manifest_entry("nfa_abb_plain")
     rng = np.random.default_rng(4)
     blob = fixture_blob("nfa_abb_plain")
     for token in (rnd(b"ab", (4 << 20) - 3, rng) + b"abb", rnd(b"ab", (4 << 20) - 3, rng) + b"abz"):
@@ -324,11 +224,11 @@ def test_memory_automata_untouched(monkeypatch):
     blob = fixture_blob("ex1_plain")
     strings = [b"aa", b"a" * (1 << 20), b"a" * (1 << 20) + b"b", b"", b"aaaaaab"]
     img = capi.Image(blob)
-    got, _ = gpu_match(img, strings)
+    got, _ = match_on_gpu(img, strings)
     assert img.last_dfa_split() == (0, 0, 0)
     assert list(got) == [1, 1, 0, 1, 0]          # the restatement's answers (it needs minutes for the long two; computed once)
     monkeypatch.setenv("MFA_DFA_SPLIT", "0")
-    again, _ = gpu_match(capi.Image(blob), strings)
+    again, _ = match_on_gpu(capi.Image(blob), strings)
     assert np.array_equal(got, again)
 
 
@@ -341,7 +241,7 @@ def test_call_is_capturable():
     strings = [rnd(b"ab", 500000, rng) + b"abb", b"ab", rnd(b"ab", 900001, rng), b"abb", b""]
     want = oracle_lib.OracleImage(blob).match(strings)
     d_bytes, d_off, off = upload(strings)
-    res = torch.full((len(strings),), 7, dtype=torch.uint8, device="cuda")
+    res = filled(len(strings))
     img = capi.Image(blob)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):

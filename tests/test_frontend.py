@@ -1,17 +1,14 @@
 """Host front-end (re2-modification_amd/host): the automata it builds must be IDENTICAL to the
 reference's -- node list order, allocation rank, edge order, labels, cell actions -- because edge and
 node order decide tie-breaks at match time.  Golden dumps come from the reference itself."""
-import json
 import os
 import subprocess
 
 import pytest
 
 import oracle_lib
+from testlib import DIPLOMA, MANIFEST
 
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
 
 FLAG = {"plain": [], "thompson": ["-thompson"], "glushkov": ["-glushkov"], "mfa": ["-mfa"], "bnf": ["-bnf"], "reverse": ["-reverse"], "ssnf": ["-ssnf"],
         "all": ["-all"]}

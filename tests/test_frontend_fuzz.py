@@ -7,35 +7,12 @@ import subprocess
 import pytest
 
 import oracle_lib
+from testlib import DIPLOMA, rand_regex
 
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
 HARNESS = os.path.join(oracle_lib.ROOT, "oracle", "_ref", "ref_harness")
 
 pytestmark = pytest.mark.skipif(not (os.path.exists(HARNESS) and os.path.exists(DIPLOMA)),
                                 reason="needs the reference harness (build container only)")
-
-
-def rand_regex(rng, depth, cells, allow_mem):
-    """A random regex of the README grammar (README.md:11-24): literals, '.', concatenation, alternation in
-    parentheses, star on a parenthesised group or a literal, and -- if allow_mem -- {r}:k and &k."""
-    if depth <= 0:
-        r = rng.random()
-        if allow_mem and cells and r < 0.25:
-            return "&" + rng.choice(cells)
-        return rng.choice("abc.") if r < 0.95 else rng.choice("ab")
-    kind = rng.random()
-    if kind < 0.35:
-        return "".join(rand_regex(rng, depth - 1, cells, allow_mem) for _ in range(rng.randint(2, 3)))
-    if kind < 0.55:
-        return "(" + "|".join(rand_regex(rng, depth - 1, cells, allow_mem) for _ in range(rng.randint(2, 3))) + ")"
-    if kind < 0.75:
-        return "(" + rand_regex(rng, depth - 1, cells, allow_mem) + ")*"
-    if kind < 0.85 and allow_mem:
-        k = rng.choice("12")
-        if k not in cells:
-            cells.append(k)
-        return "{" + rand_regex(rng, depth - 1, cells, False) + "}:" + k
-    return rng.choice("abc") + "*"
 
 
 def dump_pair(regex, flag, mode, tmp):

@@ -1,6 +1,5 @@
 """GPU parity: the HIP path (through the C-ABI) against the golden vectors produced by the
 reference and against the CPU restatement, bit-exact 0/1."""
-import json
 import os
 
 import numpy as np
@@ -8,11 +7,9 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
+from testlib import DIPLOMA, MANIFEST, MAX_BYTES, front_end_blob, rand_regex
 
 pytestmark = pytest.mark.gpu
-
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
 
 
 def gpu_match(img, strings):
@@ -69,7 +66,6 @@ def test_cli_match_contract(tmp_path):
     """`./diploma -match`: header lines, then one 0/1 line per token, byte-identical with the reference
     (main.cpp:42-44, matchers/match.cpp:21-31)."""
     import subprocess
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
     flags = {"plain": [], "bnf": ["-bnf"], "reverse": ["-reverse"], "ssnf": ["-ssnf"], "all": ["-all"]}
     for name in ("ex1_plain", "ex5_plain", "nfa_abb_plain", "nfa_third_plain", "ex3_reverse", "ex6_reverse", "ex2_bnf", "ex1_reverse", "nfa_abb_all",
                  "nfa_star1_ssnf", "ex14_reverse", "ex17_bnf"):
@@ -81,7 +77,7 @@ def test_cli_match_contract(tmp_path):
                 if s:                              # the empty string cannot be a token of `cin >> text`
                     strings.append(s); want.append(b)
         text = auto["regex"].encode() + b"\n" + b"\n".join(strings) + b"\nexit\nnot-read\n"
-        p = subprocess.run([diploma, "-match"] + flags[auto["mode"]], input=text, capture_output=True, cwd=tmp_path)
+        p = subprocess.run([DIPLOMA, "-match"] + flags[auto["mode"]], input=text, capture_output=True, cwd=tmp_path)
         assert p.returncode == 0, p.stderr
         expect = auto["header"].encode() + b"".join(b"%d\n" % b for b in want)
         assert p.stdout == expect, name
@@ -92,7 +88,6 @@ def test_match_file_drivers(tmp_path):
     batch time and then one 0/1 line per string (the reference prints `<seconds> <result>` per string); match_gt prints times
     only, like the reference, and leaves results.txt."""
     import subprocess
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
     for name in ("ex6_plain", "ex3_plain"):
         auto = next(a for a in MANIFEST["automata"] if a["name"] == name)
         strings, want = [], []
@@ -102,7 +97,7 @@ def test_match_file_drivers(tmp_path):
                     strings.append(st); want.append(int(b))
         path = tmp_path / (name + ".txt")
         path.write_bytes(b"".join(st + b"\n" for st in strings))
-        p = subprocess.run([diploma, "-match-file", "mfa", str(path)], input=auto["regex"].encode() + b"\n", capture_output=True, cwd=tmp_path)
+        p = subprocess.run([DIPLOMA, "-match-file", "mfa", str(path)], input=auto["regex"].encode() + b"\n", capture_output=True, cwd=tmp_path)
         assert p.returncode == 0, p.stderr
         lines = p.stdout.split()
         assert float(lines[0]) >= 0.0 and [int(x) for x in lines[1:]] == want, name
@@ -110,7 +105,7 @@ def test_match_file_drivers(tmp_path):
     auto = next(a for a in MANIFEST["automata"] if a["name"] == "nfa_abb_glushkov")
     path = tmp_path / "gt.txt"
     path.write_bytes(b"abb\naabb\nab\nbbbbabb\n")
-    p = subprocess.run([diploma, "-match-file", "gt", str(path)], input=auto["regex"].encode() + b"\n", capture_output=True, cwd=tmp_path)
+    p = subprocess.run([DIPLOMA, "-match-file", "gt", str(path)], input=auto["regex"].encode() + b"\n", capture_output=True, cwd=tmp_path)
     assert p.returncode == 0, p.stderr
     assert float(p.stdout.split()[0]) >= 0.0
     # results.txt: times only, `seconds,` like the reference's (match_mfa.cpp:40-41 writes one per string; a batch has one time), and
@@ -124,7 +119,6 @@ def test_cli_match_mixed(tmp_path):
     """`./diploma -match-mixed FILE...`: several regexes, each with its own strings, matched by ONE device call
     (host/automata_host.cpp: match_mixed -> mfa_match_mixed_host); the answers are the goldens'."""
     import subprocess
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
     files, want = [], []
     for name in ("ex1_plain", "ex5_plain", "ex9_plain", "x7_plain"):
         auto = next(a for a in MANIFEST["automata"] if a["name"] == name)
@@ -135,7 +129,7 @@ def test_cli_match_mixed(tmp_path):
         path = tmp_path / (name + ".txt")
         path.write_bytes(auto["regex"].encode() + b"\n" + b"".join(s + b"\n" for s in strings))
         files.append(str(path))
-    p = subprocess.run([diploma, "-match-mixed"] + files, capture_output=True, cwd=tmp_path)
+    p = subprocess.run([DIPLOMA, "-match-mixed"] + files, capture_output=True, cwd=tmp_path)
     assert p.returncode == 0, p.stderr
     assert [int(x) for x in p.stdout.split()] == want
 
@@ -144,12 +138,11 @@ def test_require_generated_kernel(tmp_path, monkeypatch):
     """MFA_REQUIRE_JIT=1: a caller that counts on the specialised kernel gets an error, not silently the other engine; MFA_VERBOSE=1
     says on stderr which kernel walks."""
     import subprocess
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
     env = dict(os.environ, MFA_REQUIRE_JIT="1", MFA_WALK="table")
-    p = subprocess.run([diploma, "-match"], input=b"({a*}:1&1)*\naa\nexit\n", capture_output=True, cwd=tmp_path, env=env)
+    p = subprocess.run([DIPLOMA, "-match"], input=b"({a*}:1&1)*\naa\nexit\n", capture_output=True, cwd=tmp_path, env=env)
     assert p.returncode != 0 and b"specialised kernel" in p.stderr
     env = dict(os.environ, MFA_VERBOSE="1", MFA_WALK="table")
-    p = subprocess.run([diploma, "-match"], input=b"({a*}:1&1)*\naa\nexit\n", capture_output=True, cwd=tmp_path, env=env)
+    p = subprocess.run([DIPLOMA, "-match"], input=b"({a*}:1&1)*\naa\nexit\n", capture_output=True, cwd=tmp_path, env=env)
     assert p.returncode == 0 and b"walk_kernel" in p.stderr and p.stdout.endswith(b"1\n")
 
 
@@ -159,14 +152,13 @@ def test_cli_example_runner(tmp_path):
     round and once more every tenth round, prefix accumulating the previous string)."""
     import subprocess
     from mfa_amd import corpus
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
     for ex in (1, 5):
         regex, pump, suffix, prefix = corpus.ALL_EXAMPLES[ex]
         d = tmp_path / "test" / ("example_%d" % ex)
         d.mkdir(parents=True)
         (d / "regexp.txt").write_text(regex + "\nunused-python-regex\n")
         (d / "pump.txt").write_text(",".join(pump) + "\n" + suffix + "\n" + prefix)
-        p = subprocess.run([diploma, "-match", str(ex)], capture_output=True, text=True, cwd=tmp_path, timeout=600)
+        p = subprocess.run([DIPLOMA, "-match", str(ex)], capture_output=True, text=True, cwd=tmp_path, timeout=600)
         assert p.returncode == 0, p.stderr
         assert p.stdout.splitlines()[0] == regex
         lines = (d / "diploma_results.txt").read_text().split("\n")
@@ -178,7 +170,7 @@ def test_cli_example_runner(tmp_path):
         while True:
             grown = grown + corpus.pumped_string(size, pump) + suffix
             size += size
-            if len(grown) > 0x00ffffff:
+            if len(grown) > MAX_BYTES:
                 break
             want.append(len(grown))
             rnd += 1
@@ -342,7 +334,7 @@ def test_edge_cases():
     s2 = [b"", b"abb", b"a" * 17 + b"abb", b"b" * 129 + b"abb", b"abb" + b"a" * 200] + [b"ab" * k + b"abb" for k in range(60)]
     assert list(gpu_match(capi.Image(nfa_blob), s2)) == list(oracle_lib.OracleImage(nfa_blob).match(s2))
     # exactly at the limit is matched, one byte more is flagged 2 by the device entry point and refused by the host one
-    limit = 0x00ffffff
+    limit = MAX_BYTES
     big = torch.full((limit + 1 + 64,), ord("a"), dtype=torch.uint8, device="cuda")
     off = torch.tensor([0, limit], dtype=torch.int64, device="cuda")
     r = img.match_tensors(big, off)
@@ -383,11 +375,7 @@ def test_streams_and_reuse():
 
 
 def _front_end_blob(regex, tmp_path, flag="-mfa"):
-    import subprocess
-    diploma = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-    p = subprocess.run([diploma, "-dump", flag], input=regex + "\n", capture_output=True, text=True, cwd=tmp_path)
-    assert p.returncode == 0, p.stderr
-    return image.blob_from_dump(p.stdout)
+    return front_end_blob(regex, tmp_path, flag=flag)
 
 
 @pytest.mark.parametrize("seed", range(3))
@@ -396,7 +384,6 @@ def test_random_regexes_on_gpu(seed, tmp_path, monkeypatch):
     the table-driven walk (all of them) and by a freshly generated specialised kernel (the first one per seed),
     against the CPU restatement."""
     import random
-    from test_frontend_fuzz import rand_regex
     rng = random.Random(9000 + seed)
     done = 0
     for _ in range(40):

@@ -1,7 +1,6 @@
 """INTEGRATION.md, binding B: integration/gpu_match.cpp compiled against the reference's own headers and objects (build
 container only: needs /root/reference and oracle/_ref/*.o), and the blob its freeze() makes from the reference's graphs
 compared with the committed golden images."""
-import json
 import os
 import subprocess
 
@@ -9,6 +8,7 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
+from testlib import MANIFEST
 
 REF = "/root/reference"
 OBJ = os.path.join(oracle_lib.ROOT, "oracle", "_ref")
@@ -17,9 +17,6 @@ OBJS = ["automata.o", "mfa.o", "bt_binary_tree.o", "bt_bt_thomson.o", "bt_bt_glu
 
 pytestmark = pytest.mark.skipif(not (os.path.isdir(REF) and all(os.path.exists(os.path.join(OBJ, o)) for o in OBJS)),
                                 reason="needs the reference sources and their objects (build container only)")
-
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
 
 
 @pytest.fixture(scope="module")

@@ -1,69 +1,25 @@
 """Memory-less automata inside mixed batches (mfa_match_mixed): the multi-table launch (csrc/dfa_mixed.hip), the launches of single
 segments, the clipped region pass, the scheduling around them and the command line, against the golden answers, the per-image calls and
 the CPU restatement."""
-import json
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib
-from mfa_amd import capi, image
+from mfa_amd import capi
+from testlib import DIPLOMA, MANIFEST, MAX_BYTES, filled, fixture_blob, front_end_blob, match_on_gpu, mixed_match, seg_first_of, upload
 
 pytestmark = pytest.mark.gpu
 
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
 NFA = [a for a in MANIFEST["automata"] if a["name"].startswith("nfa_")]
 MEM = [a for a in MANIFEST["automata"] if a["name"].endswith("_plain") and a["name"].startswith("ex")][:10]
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-MAX_BYTES = 0x00ffffff
 
 
 @pytest.fixture(autouse=True)
 def multi_table_launch(monkeypatch):
     """the multi-table launch is off by default until it has been measured (csrc/walk_plan.h: kDfaMultiDefault): these tests ask for it"""
     monkeypatch.setenv("MFA_MIXED_DFA", "1")
-
-
-def fixture_blob(name, rev=None):
-    d = image.parse_dump(oracle_lib.load_dump(name))
-    if rev is not None:
-        d["reversed"] = rev
-    return image.to_blob(d)
-
-
-def upload(strings):
-    import torch
-    data, off = oracle_lib.pack(strings)
-    d_bytes = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
-    d_bytes[:len(data)] = torch.from_numpy(data.copy())
-    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda()
-
-
-def seg_first_of(segments):
-    return [0] + [int(x) for x in np.cumsum([len(s) for s in segments])]
-
-
-def mixed_match(mixed, segments, stream=None):
-    import torch
-    strings = [s for seg in segments for s in seg]
-    d_bytes, d_off = upload(strings)
-    res = torch.full((max(len(strings), 1),), 7, dtype=torch.uint8, device="cuda")
-    mixed.match_tensors(d_bytes, d_off, seg_first_of(segments), res, stream=stream)
-    torch.cuda.synchronize()
-    return res[:len(strings)].cpu().numpy()
-
-
-def per_image(img, strings):
-    import torch
-    if not strings:
-        return np.zeros(0, dtype=np.uint8)
-    d_bytes, d_off = upload(strings)
-    res = img.match_tensors(d_bytes, d_off)
-    torch.cuda.synchronize()
-    return res.cpu().numpy()
 
 
 def golden(auto):
@@ -141,7 +97,7 @@ def test_memoryless_only_object():
     assert mixed.last_launches()["region_launches"] == 0 and mixed.last_launches()["walk_launches"] == 0
     assert mixed.last_ms()[0] == 0.0 and mixed.last_ms()[1] > 0.0
     assert mixed.last_dfa()["multi_launches"] == 1 and mixed.last_dfa()["own_launches"] == 0
-    want = np.concatenate([per_image(i, s) for i, s in zip(imgs, segments)])
+    want = np.concatenate([match_on_gpu(i, s)[0] for i, s in zip(imgs, segments)])
     assert np.array_equal(got, want) and np.array_equal(got, np.concatenate([golden(a)[1] for a in autos]))
     mixed.close()
 
@@ -156,7 +112,7 @@ def test_directions_mixed_in_one_object():
     mixed = capi.Mixed(imgs)
     got = mixed_match(mixed, segments)
     assert mixed.last_dfa()["multi_launches"] == 1 and mixed.last_dfa()["items"] == 4
-    want = np.concatenate([per_image(i, s) for i, s in zip(imgs, segments)])
+    want = np.concatenate([match_on_gpu(i, s)[0] for i, s in zip(imgs, segments)])
     assert np.array_equal(got, want)
     assert np.array_equal(got, np.concatenate([oracle_lib.OracleImage(b).match(s) for b, s in zip(blobs, segments)]))
     n = len(strings)
@@ -166,8 +122,7 @@ def test_directions_mixed_in_one_object():
 
 def test_ineligible_image_beside_eligible_ones(tmp_path):
     """a table that does not fit LDS (hundreds of state sets: the Thompson image of (a|b)*a(a|b)^8) gets a launch of its own"""
-    from test_gpu_parity import _front_end_blob          # the generator of test_large_tabulated_automaton
-    big = _front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path, "-thompson")
+    big = front_end_blob("(a|b)*a" + "(a|b)" * 8, tmp_path)
     blobs = [fixture_blob("nfa_abb_plain"), big, fixture_blob("nfa_enum_ssnf"), fixture_blob("ex1_plain")]
     imgs = [capi.Image(b) for b in blobs]
     assert imgs[1].info()["dfa_states"] > 127
@@ -213,7 +168,7 @@ def test_edge_cases():
     big[MAX_BYTES - 2:MAX_BYTES] = ord("b")                       # string 0 = a...abb, exactly at the limit
     d_off = torch.tensor([0, MAX_BYTES, 2 * MAX_BYTES + 1, 2 * MAX_BYTES + 4], dtype=torch.int64, device="cuda")
     big[2 * MAX_BYTES + 1:2 * MAX_BYTES + 4] = torch.tensor(list(b"abb"), dtype=torch.uint8, device="cuda")
-    res = torch.full((3,), 7, dtype=torch.uint8, device="cuda")
+    res = filled(3)
     mixed.match_tensors(big, d_off, [0, 3, 3, 3, 3, 3, 3], res)
     torch.cuda.synchronize()
     assert list(res[:3].cpu().numpy()) == [1, 2, 1]
@@ -244,10 +199,10 @@ def test_forty_alternating_calls_without_synchronising():
     dev = []
     for segments, want in batches:
         strings = [s for seg in segments for s in seg]
-        d_bytes, d_off = upload(strings)
+        d_bytes, d_off, _ = upload(strings)
         dev.append((d_bytes, d_off, seg_first_of(segments), len(strings)))
     for streams in ([torch.cuda.current_stream()], [torch.cuda.Stream(), torch.cuda.Stream()]):
-        results = [torch.full((dev[k % 2][3],), 7, dtype=torch.uint8, device="cuda") for k in range(40)]
+        results = [filled(dev[k % 2][3]) for k in range(40)]
         torch.cuda.synchronize()
         for k in range(40):
             d_bytes, d_off, sf, _ = dev[k % 2]
@@ -263,9 +218,9 @@ def test_capture_and_replay():
     blobs, batches = _two_batches()
     segments, want = batches[1]
     strings = [s for seg in segments for s in seg]
-    d_bytes, d_off = upload(strings)
+    d_bytes, d_off, _ = upload(strings)
     total = sum(len(s) for s in strings)
-    res = torch.full((len(strings),), 7, dtype=torch.uint8, device="cuda")
+    res = filled(len(strings))
     mixed = capi.Mixed([capi.Image(b) for b in blobs])
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):

@@ -2,7 +2,6 @@
 tests/emul/dfa_plan_emul.cpp) and the host build of the multi-table kernel's per-item walk (csrc/dfa_mixed_core.h, run one lane at a
 time by tests/emul/dfa_mixed_emul.cpp) against the golden answers.  The kernel around them is checked by tests/test_mixed_dfa_gpu.py."""
 import json
-import os
 import struct
 import subprocess
 
@@ -11,27 +10,21 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
+from testlib import MANIFEST, MAX_BYTES, emul_exe, fixture_blob
 
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
 SLICE, MAX_ITEMS, OWN_DEFAULT = 256, 96, 32768      # walk_plan.h: kDfaSliceStrings, kDfaMaxItems, kDfaOwnDefault
 ROW, TILE = 258, 4 * 64 * 144                       # dfa_split_core.h: kDfaRow; dfa_mixed_core.h: kMixTileBytes
-
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    NFA = [a for a in json.load(f)["automata"] if a["name"].startswith("nfa_")]
+NFA = [a for a in MANIFEST["automata"] if a["name"].startswith("nfa_")]
 
 
 @pytest.fixture(scope="module")
-def plan_emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dfa_plan_emul") / "dfa_plan_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_dfa_plan.sh"), exe])
-    return exe
+def plan_emul():
+    return emul_exe("dfa_plan")
 
 
 @pytest.fixture(scope="module")
-def walk_emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dfa_mixed_emul") / "dfa_mixed_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_dfa_mixed.sh"), exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return exe
+def walk_emul():
+    return emul_exe("dfa_mixed")
 
 
 def table_bytes(states):
@@ -144,11 +137,9 @@ def test_more_items_than_a_launch_takes(plan_emul):
     assert len(plan["items"]) == len(imgs) and plan["launches"] == 3
 
 
-def fixture_blob(name, rev=None, flip=0):
-    """the fixture's image; rev: with this scan direction; flip: with the other direction than its own (it then accepts the mirrored strings)"""
-    d = image.parse_dump(oracle_lib.load_dump(name))
-    d["reversed"] = (d["reversed"] ^ flip) if rev is None else rev
-    return image.to_blob(d)
+def other_direction(name):
+    """the fixture's image made to scan in the other direction than its own (it then accepts the mirrored strings)"""
+    return fixture_blob(name, 1 - image.blob_info(fixture_blob(name))["reversed"])
 
 
 def test_item_walk_on_every_fixture(walk_emul, tmp_path):
@@ -160,7 +151,7 @@ def test_item_walk_on_every_fixture(walk_emul, tmp_path):
     for rev in (0, 1):
         for a in NFA:
             assert sorted(a["sets"]) == ["abc7", "odd", "rnd"]
-            (tmp_path / ("%d.blob" % len(blobs))).write_bytes(fixture_blob(a["name"], flip=rev))
+            (tmp_path / ("%d.blob" % len(blobs))).write_bytes(other_direction(a["name"]) if rev else fixture_blob(a["name"]))
             first = len(strings)
             for sset in ("abc7", "odd", "rnd"):
                 ss = oracle_lib.load_set(sset)
@@ -202,7 +193,7 @@ def test_item_walk_lines_and_limits(walk_emul, tmp_path):
                 t = t[:-3] + b"abb" if k != 1 else b"bba" + t[3:]
             strings.append(t)
         items.append((first, len(strings) - first, k))
-    limit = 0x00ffffff
+    limit = MAX_BYTES
     first = len(strings)
     strings += [b"ab" * ((limit - 3) // 2) + b"abb", b"a" * (limit + 1), b"abb"]
     items.append((first, 3, 0))

@@ -1,13 +1,12 @@
 """The set walk of memory-less automata whose tabulation passes the limit, the part that can be wrong without a GPU (csrc/nfa_set_core.h:
 the reference's step on a bit mask of live nodes, the walk of one string; csrc/image_host.cpp: the tables, the fall-over at image
 creation), compiled for the host (tests/emul/nfa_set_emul.cpp) and run against the tabulated step function and the CPU restatement; and
-what the C-ABI answers before it touches a device.  The kernel around it is checked by tests/test_nfa_setwalk_gpu.py, which uses this
-file's corpus."""
+what the C-ABI answers before it touches a device.  The kernel around it is checked by tests/test_nfa_setwalk_gpu.py, on the same
+corpus (tests/testlib.py: setwalk_corpus)."""
 import ctypes
 import os
 import random
 import re
-import struct
 import subprocess
 
 import numpy as np
@@ -15,101 +14,18 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from test_dfa_resume_cpu import front_end_blob, table_127
-from test_dfa_split_cpu import NFA_NAMES, blob_of, out_offsets
-from test_frontend_fuzz import rand_regex
-
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
-LENGTHS = [0, 1, 15, 16, 17, 31, 32, 33, 255, 256, 257, 4096]
-AB = "(a|b)"
-
-
-def k_regex(k):
-    """(a|b)*a(a|b)^k: 2^(k+1) state sets in the Thompson compile"""
-    return "(a|b)*a" + AB * k
+from testlib import (DIPLOMA, LENGTHS, NFA_NAMES, blob_of, emul_exe, expected, front_end_blob, k_regex, out_offsets, rand_regex, setwalk_corpus, table_127, wide_images,
+                     wide_strings, write_batch)
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("nfa_set_emul") / "nfa_set_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_nfa_set.sh"), exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return exe
-
-
-# ---- the corpus (shared with the GPU test) ------------------------------------------------------------------------------------------
-def accepted_of(name, ln, rng):
-    """a string of (about) ln bytes that the fixture's regex accepts, where one of that length exists"""
-    pick = lambda alpha, k: bytes(rng.choice(list(alpha), size=max(k, 0)).tolist())
-    if name.startswith("nfa_abb"):
-        return pick(b"ab", ln - 3) + b"abb"
-    if name.startswith("nfa_third"):
-        return pick(b"ab", ln - 3) + b"a" + pick(b"ab", 2)
-    if name.startswith("nfa_enum"):
-        return pick(b"abc", ln - 3) + b"abc"
-    if name.startswith("nfa_star1"):
-        return pick(b"ab", ln - 2) + b"ab"
-    if name.startswith("nfa_star2"):
-        return pick(b"ab", ln - 1) + b"a"
-    if name.startswith("nfa_star4"):
-        body = b"".join(rng.choice([b"ab", b"c", b"cc", b"abab"]) for _ in range(ln // 2 + 1))[:max(ln - 1, 0)]
-        while body[-1:] == b"a":
-            body = body[:-1]
-        return b"c" * (ln - 1 - len(body)) + body + b"a"
-    if name.startswith("nfa_alt3"):                        # (ab|b)(ab|ba)*c*
-        pairs = max(ln - 2, 0) // 3
-        return b"ab" + b"".join(rng.choice([b"ab", b"ba"]) for _ in range(pairs)) + b"c" * max(ln - 2 - 2 * pairs, 0)
-    assert name.startswith("nfa_dot")                      # a.c*(b|.a)*
-    out = b"a" + pick(b"abcz.", 1) + b"c" * (max(ln - 2, 0) // 4)
-    while len(out) < ln:
-        out += b"b" if rng.random() < 0.4 or len(out) + 2 > ln else pick(b"abcz", 1) + b"a"
-    return out
-
-
-def corpus(name, rev, seed=0, n_golden=440):
-    """about 600 strings for a fixture: golden strings (the reference's own answers come with them) and generated ones of LENGTHS and of
-    random lengths up to 3000 -- accepted ones, ones rejected by their last byte only, ones that die early.  Packed back to back they
-    start at every offset mod 16.  rev: the image is made to scan from the end and the strings are mirrored.
-    Returns (blob, strings, golden): golden[k] = the reference's answer for string k, -1 where there is none."""
-    rng = np.random.default_rng(len(name) * 257 + rev + 1000 * seed)
-    gold_s, gold_b = [], []
-    for sset in ("abc7", "rnd", "odd"):
-        gold_s += oracle_lib.load_set(sset)
-        gold_b += [int(x) for x in oracle_lib.load_bits(name, sset)]
-    take = sorted(int(x) for x in rng.choice(len(gold_s), size=n_golden, replace=False))
-    strings, golden = [gold_s[k] for k in take], [gold_b[k] for k in take]
-    lens = LENGTHS + LENGTHS + [int(x) for x in rng.integers(0, 3001, size=40)] + [int(x) for x in rng.integers(0, 120, size=96)]
-    k = 0
-    while lens or len({o % 16 for o in out_offsets(strings)}) < 16:
-        ln = lens.pop(0) if lens else int(rng.integers(1, 300))
-        s = accepted_of(name, ln, rng)[-ln:] if ln else b""      # (shorter than the regex's shortest word: its tail)
-        assert len(s) == ln
-        if k % 4 == 1 and s:
-            s = s[:-1] + b"z"                              # rejected by the last byte only
-        if k % 9 == 5 and len(s) > 40:
-            s = s[:7] + b"\x00" + s[8:]                    # dies early
-        strings.append(s)
-        golden.append(-1)
-        k += 1
-    blob = blob_of(name, rev)
-    if rev and not image.blob_info(blob_of(name, 0))["reversed"]:
-        strings = [s[::-1] for s in strings]               # the flag makes the same automaton scan from the end: the mirrored language
-    return blob, strings, np.array(golden)
-
-
-def expected(blob, strings, golden):
-    """the CPU restatement's answers, held to the reference's own where the corpus has them; both answers must occur"""
-    want = oracle_lib.OracleImage(blob).match(strings)
-    have = golden >= 0
-    assert have.sum() > 300 and np.array_equal(want[have], golden[have].astype(np.uint8))
-    assert 0 < int(want.sum()) < len(strings)
-    return want
+def emul():
+    return emul_exe("nfa_set")
 
 
 def run_match(emul, tmp_path, blob, strings):
-    data, off = oracle_lib.pack(strings)
     (tmp_path / "a.blob").write_bytes(blob)
-    (tmp_path / "batch.bin").write_bytes(struct.pack("<Q", len(strings)) + off.astype("<u8").tobytes() + data.tobytes()[:int(off[-1])])
+    write_batch(tmp_path / "batch.bin", strings)
     p = subprocess.run([emul, "match", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin")], capture_output=True)
     if p.returncode == 3:
         return None                                        # outside the set walk's limits (an epsilon cycle, too many nodes)
@@ -147,29 +63,13 @@ def test_step_equals_the_table(emul, name, tmp_path):
 @pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
 @pytest.mark.parametrize("name", NFA_NAMES)
 def test_strings_against_oracle(emul, name, rev, tmp_path):
-    blob, strings, golden = corpus(name, rev)
+    blob, strings, golden = setwalk_corpus(name, rev)
     assert {o % 16 for o in out_offsets(strings)} == set(range(16)) and set(LENGTHS) <= {len(s) for s in strings}
     assert image.blob_info(blob)["reversed"] >= rev
     want = expected(blob, strings, golden)
     got = run_match(emul, tmp_path, blob, strings)
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, "%s: %d mismatches, first len %d want %d" % (name, bad.size, len(strings[bad[0]]), want[bad[0]])
-
-
-def wide_images(tmp_path):
-    """Thompson of nested alternations: more than 32 nodes, more than 64, more than 128, and deep epsilon chains"""
-    deep = "a"
-    for _ in range(6):
-        deep = "((" + deep + "|b)|c)"
-    return {"w2": front_end_blob("(a|b)*a" + AB * 4 + "(c|(a|b))*", tmp_path, 0, "-thompson"),
-            "w4": front_end_blob("((a|b)|(c|a))*" + "((a|b)|c)" * 6, tmp_path, 0, "-thompson"),
-            "w8": front_end_blob("((a|b)|(c|a))*" + "((a|(b|c))|(c|(a|b)))" * 8, tmp_path, 0, "-thompson"),
-            "deep": front_end_blob("(" + deep + ")*" + deep, tmp_path, 1, "-thompson")}
-
-
-def wide_strings(rng, n=300):
-    strings = [bytes(rng.choice(list(b"abc"), size=int(ln)).tolist()) for ln in LENGTHS + [int(x) for x in rng.integers(0, 200, size=n - len(LENGTHS))]]
-    return strings + [s[:-1] + b"z" for s in strings[3:40]]
 
 
 def test_wider_masks_and_deep_chains(emul, tmp_path):

@@ -1,6 +1,6 @@
 """The set walk of memory-less automata on the GPU (csrc/nfa_set.hip): every memory-less fixture forced onto it, the automatic fall-over
 of an automaton with 2^21 state sets, wider masks and deep epsilon chains, a mixed object that holds one, and the command line -- against
-the golden answers and the CPU restatement.  Corpus and images are those of tests/test_nfa_setwalk_cpu.py."""
+the golden answers and the CPU restatement.  Corpus and images are those of tests/test_nfa_setwalk_cpu.py (tests/testlib.py)."""
 import os
 import subprocess
 
@@ -9,13 +9,9 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from test_dfa_resume_cpu import front_end_blob
-from test_dfa_split_cpu import NFA_NAMES
-from test_nfa_setwalk_cpu import LENGTHS, corpus, expected, k_regex, wide_images, wide_strings
+from testlib import DIPLOMA, LENGTHS, NFA_NAMES, expected, filled, front_end_blob, k_regex, match_on_gpu, setwalk_corpus, upload, wide_images, wide_strings
 
 pytestmark = pytest.mark.gpu
-
-DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
 
 
 @pytest.fixture()
@@ -25,21 +21,9 @@ def env(monkeypatch):
     return monkeypatch
 
 
-def upload(strings):
-    import torch
-    data, off = oracle_lib.pack(strings)
-    d_bytes = torch.zeros((len(data) + 15) // 16 * 16, dtype=torch.uint8, device="cuda")      # exactly the read rule's room
-    d_bytes[:len(data)] = torch.from_numpy(data.copy())
-    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda()
-
-
 def match(img, strings):
-    import torch
-    d_bytes, d_off = upload(strings)
-    res = torch.full((max(len(strings), 1),), 7, dtype=torch.uint8, device="cuda")
-    img.match_tensors(d_bytes, d_off, res)
-    torch.cuda.synchronize()
-    return res[:len(strings)].cpu().numpy()
+    """with exactly the room the read rule asks for behind the strings"""
+    return match_on_gpu(img, strings, exact=True)[0]
 
 
 def check(img, strings, want, what):
@@ -55,7 +39,7 @@ def check(img, strings, want, what):
 def test_fixtures_forced(env, name, rev):
     """every memory-less fixture as a set-walk image, about 600 strings, against the reference's golden answers and the CPU restatement;
     the same image on fewer than 64 strings and on a count that is no multiple of 256"""
-    blob, strings, golden = corpus(name, rev)
+    blob, strings, golden = setwalk_corpus(name, rev)
     want = expected(blob, strings, golden)
     assert set(LENGTHS) <= {len(s) for s in strings} and len(strings) % 256 != 0 and len(strings) > 512
     env.setenv("MFA_NFA_SETWALK", "1")
@@ -130,8 +114,8 @@ def test_one_mixed_object(env, tmp_path):
     seg_set = [bytes(rng.choice(list(b"ab"), size=int(ln)).tolist()) for ln in rng.integers(0, 200, size=500)]
     segments = [base, base, seg_set]
     strings = [s for seg in segments for s in seg]
-    d_bytes, d_off = upload(strings)
-    res = torch.full((len(strings),), 7, dtype=torch.uint8, device="cuda")
+    d_bytes, d_off, _ = upload(strings, exact=True)
+    res = filled(len(strings))
     mixed = capi.Mixed([mem, tab, sw])
     mixed.match_tensors(d_bytes, d_off, [0, 700, 1400, 1900], res)
     torch.cuda.synchronize()

@@ -12,9 +12,7 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
-
-with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-    MANIFEST = json.load(f)
+from testlib import MANIFEST
 
 
 @pytest.mark.parametrize("auto", MANIFEST["automata"], ids=lambda a: a["name"])

@@ -11,31 +11,18 @@ import pytest
 
 import oracle_lib
 from mfa_amd import corpus, image
-
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
-
-
-_built = {}
-
-
-def build_emul(tmp_path_factory, flags=""):
-    """tests/emul/build.sh with EMUL_FLAGS=flags, once per session (tests/test_walk_fuzz_cpu.py walks with the same two builds)"""
-    if flags not in _built:
-        exe = str(tmp_path_factory.mktemp("emul") / "walk_emul")
-        subprocess.check_call([os.path.join(EMUL_DIR, "build.sh"), exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=dict(os.environ, EMUL_FLAGS=flags))
-        _built[flags] = exe
-    return _built[flags]
+from testlib import emul_exe
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    return build_emul(tmp_path_factory)
+def emul():
+    return emul_exe("walk")
 
 
 @pytest.fixture(scope="module")
-def emul_map(tmp_path_factory):
+def emul_map():
     """the same source as the kernel for long lists compiles it: WALK_NODE_MAP=1 (a node's entry found through a per-lane map, walk_core.h: insert)"""
-    return build_emul(tmp_path_factory, "-DWALK_NODE_MAP=1")
+    return emul_exe("walk", "-DWALK_NODE_MAP=1")
 
 
 def mfa_names():

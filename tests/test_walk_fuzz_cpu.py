@@ -12,7 +12,7 @@ import pytest
 import oracle_lib
 import regex_fuzz
 from mfa_amd import image
-from test_walk_emul import emul, emul_map  # noqa: F401  (fixtures: the plain and the WALK_NODE_MAP=1 build of tests/emul/build.sh)
+from testlib import emul_exe
 
 HARNESS = os.path.join(oracle_lib.ROOT, "oracle", "_ref", "ref_harness")
 N_REGEX = 44
@@ -23,6 +23,16 @@ _first = int(os.environ.get("MFA_FUZZ_FIRST", "0"))
 SEEDS = [(seed, ncell) for seed in range(_first, _first + 1 + int(os.environ.get("MFA_FUZZ_SEEDS", "0"))) for ncell in (3, 6, 9)]
 
 _corpora = {}
+
+
+@pytest.fixture(scope="module")
+def emul():
+    return emul_exe("walk")
+
+
+@pytest.fixture(scope="module")
+def emul_map():
+    return emul_exe("walk", "-DWALK_NODE_MAP=1")
 
 
 def corpus_of(seed, ncell):
@@ -48,7 +58,7 @@ def check(got, want, regex, flag, cap, accel, strings, build=""):
 
 
 @pytest.mark.parametrize("seed,ncell", SEEDS)
-def test_walk_source_on_random_automata(emul, emul_map, seed, ncell, tmp_path):  # noqa: F811
+def test_walk_source_on_random_automata(emul, emul_map, seed, ncell, tmp_path):
     walked = both = jumped = spilled = 0
     cell_counts = set()
     path = tmp_path / "a.blob"

@@ -10,6 +10,7 @@ import pytest
 
 import oracle_lib
 import regex_fuzz
+import testlib
 from mfa_amd import capi, image
 
 pytestmark = pytest.mark.gpu
@@ -32,11 +33,8 @@ def want_of(k):
 
 
 def upload(strings):
-    import torch
-    data, off = oracle_lib.pack(strings)
-    d_bytes = torch.zeros((len(data) + 15) // 16 * 16, dtype=torch.uint8, device="cuda")      # exactly the read rule's room
-    d_bytes[:len(data)] = torch.from_numpy(data.copy())
-    return d_bytes, torch.from_numpy(off.astype(np.int64)).cuda()
+    """with exactly the room the read rule asks for behind the strings"""
+    return testlib.upload(strings, exact=True)[:2]
 
 
 def guarded(n):

@@ -9,18 +9,16 @@ import subprocess
 import pytest
 
 import oracle_lib
+from testlib import emul_exe
 
-EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
 PLANS = os.path.join(oracle_lib.GOLDEN, "plans")
 LAUNCH_KEYS = ["g", "s0", "s1", "ml", "Kc", "w0", "w1", "a", "b", "k", "sf", "stb"]      # a recorded launch of a mixed call: these values, in this order
 LDS_LIMIT = 160 * 1024           # bytes of LDS of a CU (MI355X): a fact of the device, not read from the code under test
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("plan_emul") / "plan_emul")
-    subprocess.check_call([os.path.join(EMUL_DIR, "build_plan.sh"), exe])
-    return exe
+def emul():
+    return emul_exe("plan")
 
 
 def recorded(name):

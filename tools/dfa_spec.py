@@ -14,28 +14,26 @@ One JSON line per measurement, appended to OUT (default profiles/r09_dfa_spec.js
 """
 import json
 import os
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "re2-modification_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np
 import torch
 
-from mfa_amd import capi, image
+from mfa_amd import capi
+from testlib import front_end_blob, k_regex
 
 DEV = "cuda:0"
-DIPLOMA = os.path.join(ROOT, "re2-modification_amd", "host", "diploma")
 
 
 def table(k):
     """(a|b)*a(a|b)^k through the host front-end: 514 state sets at k = 8, 32 770 at 14, 131 074 at 16"""
     with tempfile.TemporaryDirectory() as tmp:
-        p = subprocess.run([DIPLOMA, "-dump", "-thompson"], input="(a|b)*a" + "(a|b)" * k + "\n", capture_output=True, text=True, cwd=tmp)
-    assert p.returncode == 0, p.stderr
-    return capi.Image(image.blob_from_dump(p.stdout))
+        return capi.Image(front_end_blob(k_regex(k), tmp))
 
 
 def batch(lens, seed):

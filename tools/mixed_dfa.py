@@ -19,6 +19,7 @@ import torch  # noqa: E402
 
 import oracle_lib  # noqa: E402
 from mfa_amd import capi, image  # noqa: E402
+from testlib import NFA_NAMES  # noqa: E402
 
 
 def corpus(n_seg, per_seg, max_len, rng, fixed=False):
@@ -56,8 +57,7 @@ def ab(forms, reps, stream):
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r07_mixed_dfa.jsonl")
-    with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
-        names = [a["name"] for a in json.load(f)["automata"] if a["name"].startswith("nfa_")]
+    names = NFA_NAMES
     images = [capi.Image(image.blob_from_dump(oracle_lib.load_dump(n))) for n in names]
     rng = np.random.default_rng(7)
     stream = torch.cuda.Stream()

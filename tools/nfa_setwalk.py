@@ -12,7 +12,6 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
 """
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -28,9 +27,9 @@ import oracle_lib
 from dfa_long import DEV, batch
 from dfa_resume import alternate
 from mfa_amd import capi, image
+from testlib import front_end_blob
 
 KERNELS = {capi.KERNEL_TABLE: "table kernel", capi.KERNEL_NODESET: "set walk"}      # what last_kernel says ran, in every output line
-DIPLOMA = os.path.join(ROOT, "re2-modification_amd", "host", "diploma")
 
 
 def created(blob, setwalk=None):
@@ -48,8 +47,7 @@ def created(blob, setwalk=None):
 
 
 def front_end(regex, flag):
-    p = subprocess.run([DIPLOMA, "-dump", flag], input=regex + "\n", capture_output=True, text=True, cwd="/tmp", check=True)
-    return image.blob_from_dump(p.stdout)
+    return front_end_blob(regex, "/tmp", flag=flag)
 
 
 SAMPLE = 1024      # strings per side whose answers are held to the CPU restatement of that side's own image

@@ -1,26 +1,23 @@
 #!/usr/bin/env python3
 """Development: the table-driven walk (MFA_WALK=table) against goldens and the oracle on every memory automaton, then its time
 beside the generated kernels' on the headline shard, example by example, and the mixed batch in one call."""
-import glob, json, os, sys, time
+import glob, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "re2-modification_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 import oracle_lib
 from mfa_amd import capi, image, corpus
+from testlib import MANIFEST, match_on_gpu
 
 dev = torch.device("cuda", 0)
 
 def gpu(img, strings):
-    data, off = oracle_lib.pack(strings)
-    d = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev); d[:len(data)] = torch.from_numpy(data.copy())
-    o = torch.from_numpy(off.astype(np.int64)).to(dev)
-    r = img.match_tensors(d, o); torch.cuda.synchronize()
-    return r.cpu().numpy()
+    return match_on_gpu(img, strings)[0]
 
 def parity():
     os.environ["MFA_WALK"] = "table"
-    man = json.load(open(os.path.join(oracle_lib.GOLDEN, "manifest.json")))
+    man = MANIFEST
     bad = tot = 0
     for auto in man["automata"]:
         blob = image.blob_from_dump(oracle_lib.load_dump(auto["name"]))

@@ -136,37 +136,66 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
 }
 
 // A batch given with HOST pointers: checks it, copies it to the device (offsets relative to the first string), runs `match` on the copies,
-// copies the results back and synchronises (throughput is then bounded by the host link).
-int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device,
-                      const std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes)>& match) {
-    if (!offsets || (!results && n)) return MFA_ERR_INVALID_ARG;
+// copies the results back and synchronises (throughput is then bounded by the host link).  states != NULL (mfa_match_batch_resume_host):
+// n words that travel to the device and back as well; `results` may then be NULL.  check_lengths: refuse strings beyond the limit.
+int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match, uint32_t* states, bool check_lengths) {
+    if (!offsets || (!results && !states && n)) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
     for (uint64_t k = 0; k < n; k++) {
         if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
-        if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) return MFA_ERR_TOO_LONG;
+        if (check_lengths && offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) return MFA_ERR_TOO_LONG;
     }
     int rc = check_device(device);
     if (rc != MFA_OK) return rc;
     const uint64_t total = offsets[n] - offsets[0];
-    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint8_t* d_res = nullptr;
+    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint32_t* d_st = nullptr; uint8_t* d_res = nullptr;
     std::vector<uint64_t> rel(n + 1);
     for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
     hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
     if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_res, n);
+    if (e == hipSuccess && states) e = hipMalloc((void**)&d_st, n * sizeof(uint32_t));
+    if (e == hipSuccess && results) e = hipMalloc((void**)&d_res, n);
     if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && states) e = hipMemcpy(d_st, states, n * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    if (rc == MFA_OK) rc = match(d_bytes, d_off, d_res, total);
+    if (rc == MFA_OK) rc = match(d_bytes, d_off, d_res, total, d_st);
     if (rc == MFA_OK) {
         e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && states) e = hipMemcpy(states, d_st, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && results) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
     }
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_off) (void)hipFree(d_off);
-    if (d_res) (void)hipFree(d_res);
+    for (void* p : {(void*)d_bytes, (void*)d_off, (void*)d_st, (void*)d_res})
+        if (p) (void)hipFree(p);
     return rc;
+}
+
+// Whatever happens to a launch once it holds a context, the context's `done` event is recorded behind what was enqueued: a launch on
+// another stream must not be handed this context (its counter, scratch area and table) while a kernel of this call may still be using it
+struct DoneGuard {
+    LaunchCtx* cx; void* stream;
+    ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
+};
+
+// the workspace of the image's last launch on `device`, or nullptr; the caller holds img->mu
+static LaunchCtx* last_ctx(mfa_image* img, int device) {
+    auto it = img->dev.find(device);
+    return it == img->dev.end() ? nullptr : it->second.last;
+}
+
+// the header words the split kernels of the image's last launch on `device` left (zeros when they did not run: `ran`)
+static int last_split_header(mfa_image* img, int device, bool LaunchCtx::*ran, uint32_t (&h)[SPLIT_H_WORDS]) {
+    if (!img) return MFA_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(img->mu);
+    LaunchCtx* cx = last_ctx(img, device);
+    if (!cx) return MFA_ERR_INVALID_ARG;
+    if (cx->*ran) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipEventSynchronize((hipEvent_t)cx->ev_done));
+        HIP_TRY(hipMemcpy(h, cx->d_split, sizeof h, hipMemcpyDeviceToHost));
+    }
+    return MFA_OK;
 }
 
 }  // namespace mfa
@@ -263,12 +292,7 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
     LaunchCtx* cx = nullptr;
     rc = ctx_acquire(*ds, stream, &cx);
     if (rc != MFA_OK) return rc;
-    // whatever happens below, the context's `done` event is recorded behind what was enqueued: a launch on another stream must not
-    // be handed this context (its counter, scratch area and table) while a kernel of this call may still be using it
-    struct DoneGuard {
-        LaunchCtx* cx; void* stream;
-        ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
-    } done_guard{cx, stream};
+    DoneGuard done_guard{cx, stream};
     img->last_kernel = table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : img->host.set_walk ? MFA_KERNEL_NODESET : MFA_KERNEL_TABLE;
     if (is_mfa && own_regions && regions_enabled()) {
         rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
@@ -323,7 +347,7 @@ int mfa_region_scan(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t 
 int mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results,
                          int device) {
     if (!img) return MFA_ERR_INVALID_ARG;
-    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t) {
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, uint32_t*) {
         return mfa_match_batch(img, d_bytes, d_off, n, d_res, device, nullptr); });
 }
 
@@ -341,10 +365,7 @@ int mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint6
     LaunchCtx* cx = nullptr;
     rc = ctx_acquire(*ds, stream, &cx);
     if (rc != MFA_OK) return rc;
-    struct DoneGuard {                                          // as in match_impl
-        LaunchCtx* cx; void* stream;
-        ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
-    } done_guard{cx, stream};
+    DoneGuard done_guard{cx, stream};
     img->last_kernel = MFA_KERNEL_TABLE;
     return launch_dfa_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, d_states, d_results, stream);
 }
@@ -356,59 +377,25 @@ int mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const ui
     if (!img || !offsets) return MFA_ERR_INVALID_ARG;
     if (img->host.h.kind != MFA_KIND_NFA || img->host.set_walk) return MFA_ERR_UNSUPPORTED;
     if (!states) return MFA_ERR_INVALID_ARG;
-    if (n == 0) return MFA_OK;
-    for (uint64_t k = 0; k < n; k++)
-        if (offsets[k + 1] < offsets[k]) return MFA_ERR_INVALID_ARG;
-    int rc = check_device(device);
-    if (rc != MFA_OK) return rc;
-    const uint64_t total = offsets[n] - offsets[0];
-    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint32_t* d_st = nullptr; uint8_t* d_res = nullptr;
-    std::vector<uint64_t> rel(n + 1);
-    for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
-    hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_st, n * sizeof(uint32_t));
-    if (e == hipSuccess && results) e = hipMalloc((void**)&d_res, n);
-    if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_st, states, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    if (rc == MFA_OK) rc = mfa_match_batch_resume(img, d_bytes, d_off, n, d_st, d_res, device, nullptr);
-    if (rc == MFA_OK) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(states, d_st, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && results) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
-    }
-    for (void* p : {(void*)d_bytes, (void*)d_off, (void*)d_st, (void*)d_res})
-        if (p) (void)hipFree(p);
-    return rc;
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, uint32_t* d_st) {
+        return mfa_match_batch_resume(img, d_bytes, d_off, n, d_st, d_res, device, nullptr); }, states, false);
 }
 
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {
     if (!img || !ms) return MFA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(img->mu);
-    auto it = img->dev.find(device);
-    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
-    LaunchCtx& cx = *it->second.last;
-    HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_stop));
-    HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)cx.ev_start, (hipEvent_t)cx.ev_stop));
-    jit_print_stats(cx, "last kernel");
+    LaunchCtx* cx = last_ctx(img, device);
+    if (!cx) return MFA_ERR_INVALID_ARG;
+    HIP_TRY(hipEventSynchronize((hipEvent_t)cx->ev_stop));
+    HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)cx->ev_start, (hipEvent_t)cx->ev_stop));
+    jit_print_stats(*cx, "last kernel");
     return MFA_OK;
 }
 
 int mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes) {
-    if (!img) return MFA_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(img->mu);
-    auto it = img->dev.find(device);
-    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
-    LaunchCtx& cx = *it->second.last;
     uint32_t h[SPLIT_H_WORDS] = {0};
-    if (cx.split_ran) {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_done));
-        HIP_TRY(hipMemcpy(h, cx.d_split, sizeof h, hipMemcpyDeviceToHost));
-    }
+    const int rc = last_split_header(img, device, &LaunchCtx::split_ran, h);
+    if (rc != MFA_OK) return rc;
     if (strings) *strings = h[SPLIT_H_STRINGS];
     if (chunks) *chunks = h[SPLIT_H_CHUNKS];
     if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
@@ -416,17 +403,9 @@ int mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t
 }
 
 int mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, uint64_t* serial_strings, uint64_t* serial_bytes) {
-    if (!img) return MFA_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(img->mu);
-    auto it = img->dev.find(device);
-    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
-    LaunchCtx& cx = *it->second.last;
     uint32_t h[SPLIT_H_WORDS] = {0};
-    if (cx.spec_ran) {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_done));
-        HIP_TRY(hipMemcpy(h, cx.d_split, sizeof h, hipMemcpyDeviceToHost));
-    }
+    const int rc = last_split_header(img, device, &LaunchCtx::spec_ran, h);
+    if (rc != MFA_OK) return rc;
     if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
     if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
     if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
@@ -436,13 +415,12 @@ int mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, u
 int mfa_last_region_ms(mfa_image_t* img, int device, float* ms) {
     if (!img || !ms) return MFA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(img->mu);
-    auto it = img->dev.find(device);
-    if (it == img->dev.end() || !it->second.last) return MFA_ERR_INVALID_ARG;
-    LaunchCtx& cx = *it->second.last;
+    LaunchCtx* cx = last_ctx(img, device);
+    if (!cx) return MFA_ERR_INVALID_ARG;
     *ms = 0.0f;
-    if (!cx.ran_regions) return MFA_OK;
-    HIP_TRY(hipEventSynchronize((hipEvent_t)cx.ev_r1));
-    HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)cx.ev_r0, (hipEvent_t)cx.ev_r1));
+    if (!cx->ran_regions) return MFA_OK;
+    HIP_TRY(hipEventSynchronize((hipEvent_t)cx->ev_r1));
+    HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)cx->ev_r0, (hipEvent_t)cx->ev_r1));
     return MFA_OK;
 }
 

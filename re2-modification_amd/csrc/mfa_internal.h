@@ -183,8 +183,10 @@ int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, con
                 uint8_t* d_results, const uint64_t* d_regions, uint32_t n_seg, const uint32_t* seg_first, const uint32_t* seg_table,
                 uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, LeanHint* lean = nullptr, void* wait_event = nullptr);
 void set_last_hip_error(int e);
-int  match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device,      // capi.hip
-                       const std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes)>& match);
+// capi.hip: `match` is given the device copies of the bytes, offsets, results, the batch's bytes, and the states (nullptr without)
+typedef std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes, uint32_t* d_states)> HostMatch;
+int  match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match,
+                       uint32_t* states = nullptr, bool check_lengths = true);
 int  check_device(int device);      // MFA_ERR_NO_DEVICE unless `device` exists; makes it the current one
 
 }  // namespace mfa

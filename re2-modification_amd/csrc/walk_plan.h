@@ -1,5 +1,5 @@
-// What a walk launch and a mixed call will do, decided by pure functions: no HIP, no allocation, no stream.  walk_launch.hip reads the
-// environment, calls these, and then only allocates, enqueues and launches what they say; tests/emul/plan_emul.cpp runs the same
+// What a walk launch and a mixed call will do, decided by pure functions: no HIP, no stream, no memory but std::vector's.  walk_launch.hip
+// calls these, and then only allocates, enqueues and launches what they say; tests/emul/plan_emul.cpp runs the same
 // functions on a machine without a GPU (tests/test_walk_plan_cpu.py).  The layout of a wave's memory is walk.h's WalkLayout.
 #ifndef MFA_WALK_PLAN_H
 #define MFA_WALK_PLAN_H
@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mfa_hip.h"
@@ -149,10 +150,6 @@ inline int plan_walk(const WalkPlanInput& p, const WalkKnobs& kn, uint64_t n, in
 // ---- a mixed call --------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t MIX_MAX_GROUPS = 12, MIX_MAX_STREAMS = 4, MIX_MAX_LAUNCHES = 24;
 
-inline int mixed_walk_streams(bool table) {
-    return std::max(1, std::min((int)MIX_MAX_STREAMS, env_int("MFA_MIXED_WALK_STREAMS", table ? 2 : 3)));
-}
-
 // Groups: ranges of strings, cut at fractions of the batch (a segment may straddle a cut).  Decreasing sizes: the walk of the last group
 // is what the call ends with.  spec: MFA_MIXED_CUTS (fractions, comma separated), or nullptr: by the batch's bytes.
 // How many groups pays depends on the batch's BYTES: a group's region launch should take about as long as a walk launch needs anyway
@@ -196,20 +193,27 @@ inline void segments_of(const uint64_t* seg_first, uint32_t ns, uint64_t lo, uin
     while (sb < ns && seg_first[sb] < hi) sb++;
 }
 
+// What planning needs to know of an automaton of the object (mfa_mixed_create fills one per image, once).  A memory automaton: cells,
+// longest list, and block_at, the word offset of its table block in the object's tables.  A memory-less one (walked by the table kernels:
+// plan_dfa_items below; no walk launch holds it, no region launch scans it): whether the multi-table launch takes it, its scan direction,
+// and table_bytes, its fused LDS table (n_states * kDfaRow * 2).
+struct MixImage { uint32_t K, max_live, block_at; bool memoryless, eligible, reversed; uint32_t table_bytes; };
+
 // Table engine: one launch per group and run of consecutive segments whose automata have the same number of cells (a launch's kernel and
 // its LDS footprint are those of its largest cell count; an object with an automaton of more than 6 cells walks all with that kernel: K);
-// groups alternate between the NW walk streams, so that a group's walk may start while the one before it drains.
-struct MixImage { uint32_t K, max_live, block_at; };      // block_at: word offset of the automaton's table block in the object's tables
+// groups alternate between the NW walk streams, so that a group's walk may start while the one before it drains.  A run ends in front
+// of a memory-less segment.  Per-segment engine: a launch is one segment's strings in one group, [s0, s1) = that segment, and nothing of
+// the table fields is used.
 struct MixLaunch {
     uint32_t g, s0, s1, ml, Kc, w0, w1;      // group, segments [s0, s1), longest list, cells, table words [w0, w1)
     uint64_t a, b;                           // strings [a, b)
     int k;                                   // walk stream
     uint32_t sf[WALK_MAX_SEG + 1], stb[WALK_MAX_SEG];      // launch_walk's seg_first / seg_table
+    uint32_t slot;                           // its place in the call's enqueue order: the spill area, counters and lean hint it uses
+    bool waits;                              // the first launch of its stream in its group: it waits for the group's event
 };
-// no_walk: per segment, 1 = a memory-less automaton's (walked by the table kernels: plan_dfa_items below): no walk launch holds it, and a
-// run of segments ends in front of it.  nullptr: every segment is a memory automaton's.
 inline std::vector<MixLaunch> plan_table_launches(const std::vector<uint64_t>& cut, const uint64_t* seg_first, const std::vector<MixImage>& img, uint32_t K,
-                                                  uint32_t total_words, int NW, const uint8_t* no_walk = nullptr) {
+                                                  uint32_t total_words, int NW) {
     const uint32_t ns = (uint32_t)img.size();
     std::vector<MixLaunch> plan;
     for (uint32_t g = 0; g + 1 < cut.size(); g++) {
@@ -217,10 +221,10 @@ inline std::vector<MixLaunch> plan_table_launches(const std::vector<uint64_t>& c
         uint32_t sa, sb;
         segments_of(seg_first, ns, lo, hi, sa, sb);
         for (uint32_t s0 = sa; s0 < sb;) {
-            if (no_walk && no_walk[s0]) { s0++; continue; }
+            if (img[s0].memoryless) { s0++; continue; }
             uint32_t s1 = s0 + 1;
             const uint32_t Kc = K > 6 ? K : img[s0].K;
-            while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (K > 6 || img[s1].K == Kc) && !(no_walk && no_walk[s1])) s1++;
+            while (s1 < sb && s1 - s0 < WALK_MAX_SEG && (K > 6 || img[s1].K == Kc) && !img[s1].memoryless) s1++;
             MixLaunch L{};
             L.a = std::max(seg_first[s0], lo); L.b = std::min(seg_first[s1], hi);
             if (L.b > L.a) {
@@ -275,7 +279,6 @@ constexpr uint64_t kDfaOwnDefault = 32768;      // MFA_MIXED_DFA_OWN
 constexpr uint64_t dfa_slices_of(uint64_t count) { return (count + kDfaSliceStrings - 1) / kDfaSliceStrings; }
 constexpr uint64_t dfa_slice_lo(uint64_t slices, uint64_t wg, uint64_t wgs) { return slices * wg / wgs; }
 
-struct DfaImage { bool memoryless, eligible, reversed; uint32_t table_bytes; };      // table_bytes: the fused LDS table (n_states * kDfaRow * 2)
 struct DfaItem { uint64_t first; uint32_t count, image; };                         // strings [first, first + count) of the batch, automaton `image`
 struct DfaKnobs { bool multi; uint64_t own_min; };
 inline DfaKnobs dfa_knobs() {
@@ -291,8 +294,10 @@ struct DfaPlan {
     uint32_t table_bytes = 0;        // the largest table of the items
     uint64_t strings = 0, slices = 0;      // of the items
 };
-// table_schedule: the call walks its memory automata with the table engine (else every memory-less segment gets its own launch)
-inline DfaPlan plan_dfa_items(const uint64_t* seg_first, const std::vector<DfaImage>& img, bool table_schedule, const DfaKnobs& kn) {
+// table_schedule: the call walks its memory automata with the table engine (else every memory-less segment gets its own launch).
+// Image: MixImage, or just the part of it that is read here
+struct DfaImage { bool memoryless, eligible, reversed; uint32_t table_bytes; };
+template <class Image> DfaPlan plan_dfa_items(const uint64_t* seg_first, const std::vector<Image>& img, bool table_schedule, const DfaKnobs& kn) {
     DfaPlan P;
     for (uint32_t s = 0; s < (uint32_t)img.size(); s++) {
         const uint64_t cnt = seg_first[s + 1] - seg_first[s];
@@ -303,6 +308,110 @@ inline DfaPlan plan_dfa_items(const uint64_t* seg_first, const std::vector<DfaIm
         P.strings += cnt;
         P.slices += dfa_slices_of(cnt);
     }
+    return P;
+}
+
+// ---- the whole schedule of a mixed call -------------------------------------------------------------------------------------------------
+// plan_mixed composes the pieces above into everything mfa_match_mixed puts on a stream, in that order: walk_launch.hip only makes buffers
+// and streams, records, waits and launches.  The region launches go to the caller's stream, group after group; a group's event says "its
+// regions are known"; what walks a group goes to the NW walk streams behind that event and runs beside the next group's region pass.
+struct MixObject { uint32_t K, total_words, n_mem, n_dfa; bool table_ok; };      // K: most cells of a memory automaton; the object's table words
+// every variable a mixed call's schedule depends on, read from the environment once per call
+struct MixKnobs {
+    int walk;                    // MFA_WALK (walk_mode): 2 = the per-segment engine (generated kernels)
+    bool regions;                // MFA_REGIONS / MFA_ACCEL
+    const char* cuts;            // MFA_MIXED_CUTS as it is given, or nullptr
+    bool single_direct;          // MFA_MIXED_SINGLE_DIRECT (default 1)
+    int walk_streams[2];         // MFA_MIXED_WALK_STREAMS for the per-segment engine (default 3) and for the table engine (default 2)
+    DfaKnobs dfa;                // MFA_MIXED_DFA, MFA_MIXED_DFA_OWN
+};
+inline int mixed_walk_streams(bool table) { return std::max(1, std::min((int)MIX_MAX_STREAMS, env_int("MFA_MIXED_WALK_STREAMS", table ? 2 : 3))); }
+inline MixKnobs mixed_knobs() {
+    return MixKnobs{walk_mode(), regions_enabled(), getenv("MFA_MIXED_CUTS"), env_int("MFA_MIXED_SINGLE_DIRECT", 1) != 0, {mixed_walk_streams(false), mixed_walk_streams(true)}, dfa_knobs()};
+}
+// what the object's first call on a device on the per-segment engine measured: ready[MIX_MAX_GROUPS], cost[one per image]
+struct MixCalib { bool calibrated; uint32_t ng_last; const float* ready; const float* cost; };
+
+// group, strings [a, b): a run of memory segments' strings inside the group; signals: its completion signal is the group's event (no packet of its own)
+struct MixRegion { uint32_t g; uint64_t a, b; uint32_t threads; bool signals; };
+struct MixPlan {
+    int rc = MFA_OK;                // MFA_ERR_UNSUPPORTED: more table launches than the object has slots (nothing may be started)
+    bool table = false;             // the table engine walks the memory automata (else one launch per segment)
+    bool direct = false;            // one automaton, one group: exactly mfa_match_batch on the caller's stream; the lists below stay empty
+    bool with_regions = false, calibrating = false;      // the call's own region launches fill a table; its walks are timed when it is over
+    int NW = 0, KD = -1, NS = 0;    // walk streams; the stream of the memory-less segments (-1: none); streams in all
+    std::vector<uint64_t> cut;
+    std::vector<int> where;         // per-segment engine: the walk stream of each segment
+    std::vector<MixRegion> regions; // in enqueue order
+    bool own_event[MIX_MAX_GROUPS] = {false};      // the group's event is recorded by itself behind the group's region launches
+    std::vector<MixLaunch> walks;   // in enqueue order: a group's follow its region launches and its event
+    DfaPlan dfa;
+    std::vector<std::pair<uint32_t, uint32_t>> dfa_multi;      // items [first, second) of each multi-table launch
+    uint32_t n_regions = 0, n_walks = 0, n_groups = 0, n_dfa_multi = 0, n_dfa_own = 0, n_dfa_items = 0;      // what mfa_mixed_last_launches and
+    uint64_t dfa_strings = 0;                                                                                 // mfa_mixed_last_dfa report
+    bool no_regions = false;        // the call had nothing to scan (mfa_mixed_timing: a region time of 0)
+};
+// bytes: of the batch, as the caller gave them or as they were read back (used only without kn.cuts)
+inline MixPlan plan_mixed(const std::vector<MixImage>& img, const MixObject& ob, const uint64_t* seg_first, uint64_t n, uint64_t bytes, const MixKnobs& kn, const MixCalib& cal) {
+    MixPlan P;
+    const uint32_t ns = (uint32_t)img.size();
+    const bool has_mem = ob.n_mem != 0;      // (without a memory automaton nothing is grouped)
+    P.table = kn.walk != 2 && ob.table_ok;   // the table engine unless the generated kernels are asked for
+    P.cut = plan_cuts(n, has_mem ? bytes : 1, P.table, has_mem ? kn.cuts : nullptr);
+    const uint32_t ng = P.n_groups = (uint32_t)P.cut.size() - 1;
+    const bool scans = kn.regions && has_mem;
+    P.NW = has_mem ? kn.walk_streams[P.table] : 0;
+    // One automaton, one group: exactly the single-automaton call (mfa_match_batch: region pass, then the walk, on the caller's stream, with the
+    // engine that call would choose) -- the hops to the internal streams and back cost such a batch 0.03-0.06 ms and buy it nothing.  (Cutting a
+    // 1.9 GB batch of ONE automaton into two or three groups was measured in round 4, configs[4]: 0.517 ms in one piece, 0.61 / 0.69 / 0.74
+    // ms in two / three / four groups: a walk launch is latency-bound, its 0.15 ms are paid per group and hide behind nothing that short.)
+    if (ns == 1 && ng == 1 && kn.single_direct) {
+        P.direct = true;
+        P.n_regions = scans ? 1u : 0u; P.n_walks = has_mem ? 1u : 0u; P.n_dfa_own = has_mem ? 0u : 1u;
+        P.no_regions = !has_mem;
+        return P;
+    }
+    P.with_regions = scans;
+    if (P.table) P.walks = plan_table_launches(P.cut, seg_first, img, ob.K, ob.total_words, P.NW);
+    if (P.walks.size() > MIX_MAX_LAUNCHES) { P.rc = MFA_ERR_UNSUPPORTED; return P; }      // (more runs of equal cell count than the object has launch slots)
+    // the memory-less segments: the items of the multi-table launches, and the segments with a launch of their own
+    if (ob.n_dfa) P.dfa = plan_dfa_items(seg_first, img, P.table, kn.dfa);
+    for (uint32_t i0 = 0; i0 < P.dfa.items.size(); i0 += kDfaMaxItems) P.dfa_multi.emplace_back(i0, std::min<uint32_t>((uint32_t)P.dfa.items.size(), i0 + kDfaMaxItems));
+    // their stream: one beyond the walk streams while the object may have one, else the last walk stream (they go first)
+    if (!P.dfa.items.empty() || !P.dfa.own.empty()) P.KD = std::min(P.NW, (int)MIX_MAX_STREAMS - 1);
+    P.NS = std::max(P.NW, P.KD + 1);
+    // which stream walks which segment (per-segment engine): the first call one after the other (timed), then by cost
+    P.calibrating = !P.table && !cal.calibrated && has_mem;
+    P.where = !P.table && cal.calibrated && cal.ng_last == ng ? assign_streams(P.cut, seg_first, ns, cal.ready, cal.cost, P.NW) : std::vector<int>(ns, 0);
+    size_t w = 0;
+    for (uint32_t g = 0; g < ng; g++) {
+        const uint64_t lo = P.cut[g], hi = P.cut[g + 1];
+        uint32_t sa, sb;
+        segments_of(seg_first, ns, lo, hi, sa, sb);
+        // one region launch per run of memory segments in the group (an object without memory-less automata: the group): the strings of
+        // memory-less segments are not scanned.  The table engine's group event is its last region launch's completion signal.
+        const size_t r0 = P.regions.size();
+        for (uint32_t s = sa; s < sb; s++) {
+            MixLaunch L{};                                     // (per-segment engine: the segment's strings in this group)
+            L.g = g; L.s0 = s; L.s1 = s + 1; L.k = P.where[s];
+            L.a = std::max(seg_first[s], lo); L.b = std::min(seg_first[s + 1], hi);
+            if (img[s].memoryless || L.b <= L.a) continue;
+            if (P.with_regions && P.regions.size() > r0 && P.regions.back().b == L.a) P.regions.back().b = L.b;
+            else if (P.with_regions) P.regions.push_back(MixRegion{g, L.a, L.b, P.table ? 128u : 256u, false});
+            if (!P.table) P.walks.push_back(L);
+        }
+        P.own_event[g] = !P.table || P.regions.size() == r0;
+        if (!P.own_event[g]) P.regions.back().signals = true;
+        bool waits[MIX_MAX_STREAMS] = {false};
+        for (; w < P.walks.size() && P.walks[w].g == g; w++) {
+            P.walks[w].slot = (uint32_t)w;
+            P.walks[w].waits = !waits[P.walks[w].k];
+            waits[P.walks[w].k] = true;
+        }
+    }
+    P.n_regions = (uint32_t)P.regions.size(); P.n_walks = (uint32_t)P.walks.size();
+    P.no_regions = P.regions.empty() && ob.n_dfa != 0;
+    P.n_dfa_multi = (uint32_t)P.dfa_multi.size(); P.n_dfa_own = (uint32_t)P.dfa.own.size(); P.n_dfa_items = (uint32_t)P.dfa.items.size(); P.dfa_strings = P.dfa.strings;
     return P;
 }
 }  // namespace mfa

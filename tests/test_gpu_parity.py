@@ -928,3 +928,65 @@ def test_lean_walk_of_text_without_stretches(name, monkeypatch):
         torch.cuda.synchronize()
         assert np.array_equal(res.cpu().numpy(), want), (name, lean, "mixed")
         mx.close(); img.close()
+
+
+def test_mixed_call_launches_what_the_planner_says(monkeypatch):
+    """What mfa_match_mixed puts on its streams is walk_plan.h's plan_mixed: an object of three memory automata and two memory-less ones,
+    2000 strings of at most 229 bytes, one cut inside a memory segment and one inside a memory-less segment, both engines, two calls in a
+    row without a synchronisation between them.  The answers are each image's own mfa_match_batch's and the oracle's, and the launches
+    the library reports are the counts tests/emul/plan_emul.cpp prints for the same case (the counts depend on none of the table
+    sizes the case line gives: the memory-less segments end every run of segments)."""
+    import json
+    import subprocess
+    import torch
+    from testlib import emul_exe, filled, fixture_blob, seg_first_of, upload
+    names = ["ex1_plain", "nfa_abb_thompson", "ex3_plain", "nfa_star4_plain", "ex6_plain"]
+    rng = np.random.default_rng(11)
+    pool = [oracle_lib.load_set("rnd"), oracle_lib.load_set("abc7")]
+    segments = [[pool[0][i] for i in rng.choice(len(pool[0]), size=250, replace=False)] + [pool[1][i] for i in rng.choice(len(pool[1]), size=150, replace=False)]
+                for _ in names]
+    strings = [s for seg in segments for s in seg]
+    seg = seg_first_of(segments)
+    assert seg[-1] == 2000 and max(len(s) for s in strings) <= 256
+    blobs = [fixture_blob(n) for n in names]
+    want = np.concatenate([oracle_lib.OracleImage(b).match(s) for b, s in zip(blobs, segments)])
+    assert 0 < int(want.sum()) < len(want)
+    d_bytes, d_off, off = upload(strings)
+    cuts = "0.1,0.3"                                               # strings 200 (segment 0, memory) and 600 (segment 1, memory-less)
+    monkeypatch.setenv("MFA_MIXED_CUTS", cuts)
+    monkeypatch.setenv("MFA_MIXED_DFA", "1")
+    fields = []
+    for b in blobs:
+        info = image.blob_info(b)
+        states = capi.Image(b).info()["dfa_states"]
+        dfa = info["kind"] != image.KIND_MFA
+        fields.append("%d,1,1,1,%d,%d,%d,%d" % (max(info["n_cells"], 1), dfa, dfa and states * 258 * 2 + 4 * 64 * 144 <= 65536, info["reversed"], states * 258 * 2))
+    for engine in ("table", "specialised"):
+        use_engine(monkeypatch, engine)
+        images = [capi.Image(b) for b in blobs]
+        mx = capi.Mixed(images)
+        first, second = filled(len(strings)), filled(len(strings))
+        mx.match_tensors(d_bytes, d_off, seg, first)
+        mx.match_tensors(d_bytes, d_off, seg, second)
+        torch.cuda.synchronize()
+        launches, dfa = mx.last_launches(), mx.last_dfa()
+        for res in (first, second):
+            assert np.array_equal(res.cpu().numpy(), want), engine
+        for k, img in enumerate(images):
+            alone = img.match_tensors(d_bytes, d_off[seg[k]:seg[k + 1] + 1])
+            torch.cuda.synchronize()
+            assert np.array_equal(alone.cpu().numpy(), want[seg[k]:seg[k + 1]]), (engine, names[k])
+        case = "mixed %s %s %d %d 0 %d - - MFA_WALK=%s MFA_MIXED_CUTS=%s MFA_MIXED_DFA=1" % (
+            ";".join(fields), ",".join(str(x) for x in seg), seg[-1], int(off[-1]), engine != "table", "table" if engine == "table" else "jit", cuts)
+        p = subprocess.run([emul_exe("plan")], input=case + "\n", capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-400:]
+        plan = json.loads(p.stdout)
+        c = plan["counts"]
+        assert plan["rc"] == 0 and plan["table"] == (engine == "table") and plan["cut"] == [0, 200, 600, 2000], case
+        assert launches == {"region_launches": c["region_launches"], "walk_launches": c["walk_launches"], "groups": c["groups"], "gated": False}, (engine, launches, c)
+        assert dfa == {"multi_launches": c["dfa_multi"], "own_launches": c["dfa_own"], "items": c["dfa_items"], "strings": c["dfa_strings"]}, (engine, dfa, c)
+        # three groups; the memory segments 0, 2 and 4 lie in groups 0+1, 2 and 2: four region launches, four walk launches
+        assert (c["groups"], c["region_launches"], c["walk_launches"]) == (3, 4, 4) and c["dfa_multi"] + c["dfa_own"] == (1 if engine == "table" else 2), c
+        mx.close()
+        for img in images:
+            img.close()

@@ -160,12 +160,14 @@ static void do_actions(mctx_t* c, const mfa_blob_edge* e, mstate_t* s, uint64_t 
 /* MFA::is_siffix_long_enough, mfa.cpp:116-133 */
 static int suffix_ok(const mctx_t* c, const mstate_t* s, int64_t i) {
     if (!c->reversed) return 1;
-    int64_t suffix = c->len - i, needed = 0;
+    int64_t suffix = c->len - i, needed = 0, unmarked = 0;   /* unmarked: what `needed` would be with no is_read mark set */
     for (int k = 1; k <= 9; k++)
         if (s->cell[k] >= 0) {
             const var_t* v = &c->pool[s->cell[k]];
             if (v->is_open || !v->is_read) needed += (int64_t)v->len;
+            unmarked += (int64_t)v->len;
         }
+    if (c->st && (needed <= suffix) != (unmarked <= suffix)) c->st->mark_decided++;
     return needed <= suffix;
 }
 
@@ -184,6 +186,7 @@ static void m_eval_state(mctx_t* c, mstate_t st, int64_t i, sset_t* out) {
             mstate_t ns = st; ns.node = e->target; copy_memory(c, &ns);
             unsigned act = MFA_EDGE_ACTION(*e, (unsigned)digit);
             ns.cell[digit] = var_new(c, act == MFA_ACT_OPEN, 0, (uint64_t)st.pos, 0);
+            if (c->st) { c->st->created[digit]++; c->st->created_open[digit] += act == MFA_ACT_OPEN; }
             m_eval_state(c, ns, i, out);
         } else if (i != c->len && i == st.pos) {                                 /* mfa.cpp:161-194 */
             uint8_t ch = scan_at(c, i);

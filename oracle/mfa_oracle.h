@@ -31,6 +31,9 @@ typedef struct mfa_oracle_stats {
     uint64_t compare_bytes;  /* sum of |value| over reads that reached the compare     */
     uint64_t max_states;     /* largest |states| seen on entry to a step               */
     uint64_t variables;      /* Variables allocated                                    */
+    uint64_t created[10];      /* cells a read of an absent cell created (mfa.cpp:148-160), by cell 1..9 ([0] unused) */
+    uint64_t created_open[10]; /* ... those of them created open: the same edge opens the cell                        */
+    uint64_t mark_decided;     /* is_siffix_long_enough calls whose answer would differ with every is_read mark cleared */
 } mfa_oracle_stats;
 
 /* returns 0 or a negative error */

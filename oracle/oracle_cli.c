@@ -44,9 +44,14 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[1], "match")) {
         for (size_t k = 0; k < nstr; k++) { putchar('0' + res[k]); putchar('\n'); }
     } else if (want_stats) {
-        printf("steps %llu evaluations %llu cell_reads %llu compare_bytes %llu max_states %llu variables %llu\n",
+        printf("steps %llu evaluations %llu cell_reads %llu compare_bytes %llu max_states %llu variables %llu",
                (unsigned long long)st.steps, (unsigned long long)st.evaluations, (unsigned long long)st.cell_reads,
                (unsigned long long)st.compare_bytes, (unsigned long long)st.max_states, (unsigned long long)st.variables);
+        printf(" created");                               /* per cell 1..9 */
+        for (int k = 1; k <= 9; k++) printf(" %llu", (unsigned long long)st.created[k]);
+        printf(" created_open");
+        for (int k = 1; k <= 9; k++) printf(" %llu", (unsigned long long)st.created_open[k]);
+        printf(" mark_decided %llu\n", (unsigned long long)st.mark_decided);
     } else {
         unsigned acc = 0; for (size_t k = 0; k < nstr; k++) acc += res[k];
         printf("%zu %zu %.6f %u\n", nstr, w, (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec), acc);

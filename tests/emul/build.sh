@@ -2,12 +2,15 @@
 # TEST INFRASTRUCTURE ONLY: builds one of the host harnesses of this folder (see NAME_emul.cpp).
 #   build.sh NAME [OUT]       OUT: where the program goes (default: NAME_emul in this folder)
 #   EMUL_FLAGS: more compiler flags, e.g. -DWALK_NODE_MAP=1 or -fsanitize=address,undefined
+#   EMUL_ROOT:  the tree whose include/ and re2-modification_amd/csrc/ are compiled (default: this repository); the harness itself,
+#               the shim and emul_common.h are always this folder's
 set -e
 name=${1:?usage: build.sh NAME [OUT]}
 here=$(cd "$(dirname "$0")" && pwd)
 case ${2:-} in "") out=$here/${name}_emul ;; /*) out=$2 ;; *) out=$PWD/$2 ;; esac
 cd "$here"
-csrc=../../re2-modification_amd/csrc
+root=${EMUL_ROOT:-../..}
+csrc=$root/re2-modification_amd/csrc
 # the harnesses that compile the kernels' own headers do so through the HIP shim, and hear the warnings those headers raise under g++
 shim="-Ishim -Wno-unknown-pragmas -Wno-unused-function -Wno-unused-variable"
 # NAME          optimisation   more flags                              sources beside NAME_emul.cpp
@@ -19,4 +22,4 @@ dfa_split|dfa_resume|dfa_mixed|nfa_set)
 dfa_spec)       opt=-O2        more=$shim                              src=$csrc/image_host.cpp ;;
 *)              echo "build.sh: no harness named '$name'" >&2; exit 2 ;;
 esac
-g++ $opt -g -std=c++17 $EMUL_FLAGS -Wall $more -I$csrc -I../../include -o "$out" ${name}_emul.cpp $src
+g++ $opt -g -std=c++17 $EMUL_FLAGS -Wall $more -I$csrc -I$root/include -o "$out" ${name}_emul.cpp $src

@@ -4,6 +4,9 @@
 //
 //   walk_emul <image.blob> <C> <accel 0|1> [<image2.blob> <first string of segment 2> ...]  < strings (one per line)  > 0/1 per line
 // With accel = 1 every string gets a region table computed here from the definition in include/mfa_hip.h (brute force).
+// EMUL_FIELDS set: one more line on stderr (before the counters), "fields: c-cm n1 .. n9 c-com .. c-rdm .. b-cm .. b-com .. b-rdm ..":
+// per cell 1..9, the effective edges of the FIRST image's tables that hold the cell in cm, com, rdm -- the vnodes' waiting lists (c) and
+// byte-class lists (b) counted apart, decoded from the table words as the launch has them (walk_tables.h).
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -72,6 +75,33 @@ struct SeqFeeder {
         return true;
     }
 };
+
+static void print_fields(const uint32_t* w) {
+    const uint32_t n_vids = w[0], NC = w[2], off_vinfo = w[6], off_vc = w[7], off_vb = w[8], off_ee = w[9], eew = w[11];
+    unsigned long long n[2][3][9] = {};
+    auto count = [&](uint32_t list, int which) {
+        for (uint32_t e = list >> 12; e < (list >> 12) + (list & 0xfffu); e++) {
+            const uint32_t e1 = w[off_ee + e * eew + 1], e2 = eew == 3 ? w[off_ee + e * eew + 2] : 0u;
+            const uint32_t f[3] = {eew == 2 ? (e1 >> 12) & 0x3fu : (e1 >> 18) & 0x1ffu, eew == 2 ? (e1 >> 18) & 0x3fu : e2 & 0x1ffu,
+                                   eew == 2 ? (e1 >> 24) & 0x3fu : (e2 >> 9) & 0x1ffu};
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 9; c++) n[which][k][c] += (f[k] >> c) & 1u;
+        }
+    };
+    for (uint32_t id = 0; id < n_vids; id++) {
+        if (!(w[off_vinfo + id] & 1u)) continue;
+        count(w[off_vc + id], 0);
+        for (uint32_t c = 0; c < NC; c++) count(w[off_vb + id * NC + c], 1);
+    }
+    static const char* const names[2][3] = {{"c-cm", "c-com", "c-rdm"}, {"b-cm", "b-com", "b-rdm"}};
+    fprintf(stderr, "fields:");
+    for (int which = 0; which < 2; which++)
+        for (int k = 0; k < 3; k++) {
+            fprintf(stderr, " %s", names[which][k]);
+            for (int c = 0; c < 9; c++) fprintf(stderr, " %llu", n[which][k][c]);
+        }
+    fprintf(stderr, "\n");
+}
 
 template <int K, bool REV>
 static void run(const Batch& b, const std::vector<uint32_t>& T, uint32_t C, uint32_t CM, WaveStats* ws) {
@@ -154,6 +184,7 @@ int main(int argc, char** argv) {
     }
     for (uint64_t k = 0; k < n; k++) { putchar('0' + res[k]); putchar('\n'); }
     fprintf(stderr, "emul: %u of the strings walked by the lean pass\n", lean_count);
+    if (getenv("EMUL_FIELDS")) print_fields(T.data());
     fprintf(stderr, "emul: %llu strings, steps %llu, dual %llu, probes %llu, hits %llu, skipped %llu, spill-steps %llu\n", (unsigned long long)n, ws.steps, ws.dual,
             ws.probes, ws.hits, ws.skipped, ws.spills);
     if (getenv("EMUL_HIST")) { fprintf(stderr, "events: entries %llu edge-evals %llu inserts %llu search-iters %llu c-items %llu\n", g_ev[0], g_ev[1], g_ev[2], g_ev[3], g_ev[6]); for (int k = 0; k < 80; k++) if (ws.hist[k]) fprintf(stderr, " n=%d:%llu", k, ws.hist[k]); fprintf(stderr, "\n"); }

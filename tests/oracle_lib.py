@@ -12,7 +12,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 class Stats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
-                ("steps", "evaluations", "cell_reads", "compare_bytes", "max_states", "variables")]
+                ("steps", "evaluations", "cell_reads", "compare_bytes", "max_states", "variables")] + [
+                ("created", ctypes.c_uint64 * 10), ("created_open", ctypes.c_uint64 * 10), ("mark_decided", ctypes.c_uint64)]
 
 
 _lib = None

@@ -52,6 +52,19 @@ def emul_exe(name, flags=""):
     return _built[(name, flags)]
 
 
+def walk_emul_run(exe, path, cap, accel, strings, more=()):
+    """walk_emul on one image (more: [image, first string, ...] of further segments): (answers, the counters of the emulation's last
+    stderr line; under "fields" what its EMUL_FIELDS line counts per cell, {"c-cm": [n1 .. n9], "c-com", "c-rdm", "b-cm", "b-com", "b-rdm"})"""
+    p = subprocess.run([exe, str(path), str(cap), str(accel)] + [str(m) for m in more], input=b"".join(s + b"\n" for s in strings),
+                       capture_output=True, env=dict(os.environ, EMUL_FIELDS="1"))
+    assert p.returncode == 0, p.stderr.decode()[-400:]
+    lines = p.stderr.decode().strip().split("\n")
+    stats = {k: int(v) for k, v in re.findall(r"([a-z-]+) (\d+)", lines[-1].split("strings,")[1])}
+    words = next(ln for ln in lines if ln.startswith("fields:")).split()[1:]
+    stats["fields"] = {words[k]: [int(x) for x in words[k + 1:k + 10]] for k in range(0, len(words), 10)}
+    return np.array([int(x) for x in p.stdout.split()], dtype=np.uint8), stats
+
+
 def write_batch(path, strings):
     """BATCH.bin of the harnesses: u64 n, u64 offsets[n + 1], then offsets[n] bytes; returns oracle_lib.pack(strings)"""
     data, off = oracle_lib.pack(strings)

@@ -68,7 +68,7 @@ typedef struct mfa_image_info {
 #define MFA_KERNEL_WALK        1u /* walk_kernel: table-driven memory-automaton walk over a list of live states (any automaton, no compiler) */
 #define MFA_KERNEL_SPECIALISED 2u /* mfa_jit_kernel: the walk generated for one automaton, one slot per node in VGPRs */
 #define MFA_KERNEL_TABLE       3u /* dfa_walk_kernel: tabulated memory-less automaton                    */
-#define MFA_KERNEL_NODESET     4u /* nfa_set_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
+#define MFA_KERNEL_NODESET     4u /* nfa_set_kernel, nfa_set_resume_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
 
 /* Build an image from a blob (include/mfa_image_format.h).  Host-only work: parse,
  * check the structural invariants the kernels rely on, and for MFA_KIND_NFA tabulate
@@ -81,8 +81,9 @@ typedef struct mfa_image_info {
  * every memory-less image such an image without tabulating, MFA_NFA_SETWALK=0 none (beyond the limit: MFA_ERR_UNSUPPORTED, as it used
  * to be); both knobs are read here, at image creation.  Limits of such an image (MFA_ERR_UNSUPPORTED at creation): at most 256 nodes and
  * 255 byte classes, no cycle of epsilon edges among the nodes reachable from the start (the reference's evaluateState would not return),
- * epsilon chains of at most 49 nodes.  What it does not do: mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the
- * device is touched (its state between two bytes is a set of nodes, not one 32-bit number); a string of any length is walked whole by its
+ * epsilon chains of at most 49 nodes.  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
+ * mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the device is touched, and mfa_match_batch_resume_set (below)
+ * is the call that carries such a set from piece to piece.  What it does not do: a string of any length is walked whole by its
  * lane (no split path; mfa_last_dfa_split and mfa_last_dfa_spec answer zeros); in a mixed object its segment always gets a launch of
  * its own.  mfa_last_kernel_ms covers the kernel.  A string beyond MFA_MAX_STRING_BYTES answers 2. */
 int  mfa_image_create(const void* blob, size_t n_bytes, mfa_image_t** out);
@@ -169,7 +170,7 @@ int  mfa_match_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d
  * on an LDS table the fold starts from the string's word, on an L2 table the piece's first chunk does -- with the same knobs, the same
  * quiet-workspace rule and the same report through the split-report calls below; a word that is dead or in error is never cut; the call is legal inside a stream capture under the same conditions and re-entrant per (image, device, stream).
  * MFA_ERR_UNSUPPORTED: a memory automaton (its state holds spans of the input; there is no number to hand over), or a set-walk image
- * (dfa_states == 0: its state is a set of nodes).
+ * (dfa_states == 0: its state is a set of nodes; the resume call for sets, further down, takes it).
  * MFA_ERR_INVALID_ARG: d_states is NULL.  Both are answered before the device is touched. */
 #define MFA_DFA_STATE_DEAD    0u           /* the empty set: absorbing, rejecting */
 #define MFA_DFA_STATE_START   1u           /* {start}: what a string's first piece is given */
@@ -180,6 +181,46 @@ int  mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint
  * error above, not MFA_ERR_TOO_LONG */
 int  mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
                                  uint32_t* states, uint8_t* results, int device);
+
+/* ---- strings in pieces (set-walk images) ------------------------------------------------------------
+ * The state of a set-walk image (dfa_states == 0) between two bytes is the SET of live nodes.  This resume call takes that set in and hands it
+ * out, in a record of 48 bytes per string, so a string may arrive in pieces exactly as with the call above -- one call per round of pieces.
+ * Pointers, batch layout, the 16-byte read rule and asynchrony are those of the plain batch call.  d_states: n records of device
+ * memory, 16-byte aligned, read and written in place: on entry record k says what string k has reached so far, on return what it has
+ * reached behind this piece.  tag MFA_SET_STATE_START: the string's first piece, `nodes` is ignored -- a zero-filled buffer is "every
+ * string at its start".  tag MFA_SET_STATE_LIVE: `nodes` is the set reached, node v being bit v & 31 of nodes[v >> 5]; the empty set is
+ * dead, absorbing and rejecting.  On return the tag is MFA_SET_STATE_LIVE or MFA_SET_STATE_INVALID, `reserved` is zero and the words of
+ * `nodes` beyond the image's mask width (1, 2, 4 or 8 words for up to 32, 64, 128, 256 nodes) are zero.  d_results may be NULL;
+ * otherwise results[k] is what the plain call would answer for the concatenation of the pieces given so far: 0 for the empty set, else 1
+ * if and only if the set holds a node from which `finish` is reached over epsilon edges alone.
+ * The records hold the image's own node numbers.  They mean something only to images made from the same blob by the same build
+ * of this library: DO NOT STORE THEM, and do not carry them from one automaton to another.
+ * SCAN ORDER: pieces are given in the order the automaton scans.  For an image with is_reversed that is from the END of the string:
+ * its LAST piece goes into the first call, its first piece into the last.
+ * Equivalence: cut a string into pieces anywhere, empty pieces included, and give them in scan order -- the final record and the final
+ * result byte are those of one call on the whole string from a zeroed record; such a call on whole strings answers byte for byte what
+ * the plain call answers.
+ * Errors on the device are sticky: a tag other than START or LIVE (INVALID among them), a `reserved` word that is not zero, a bit set for
+ * a node the image does not have (any word beyond its mask width included), a piece longer than MFA_MAX_STRING_BYTES, or a walk whose
+ * stack would overflow (the record names nodes no walk of this image reaches together) leaves tag MFA_SET_STATE_INVALID, `nodes` zero and
+ * result 2, and so does every later call on that record.  The SUM of a string's pieces has no limit.  A record that enters LIVE with the
+ * empty set leaves the same with result 0 and its bytes are not read.
+ * A piece of any length is walked whole by its lane (no split path: the two split-report calls below answer zeros); last_kernel becomes
+ * MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launch.  Re-entrant per (image, device, stream), and legal inside a stream capture
+ * once a first call has run (it allocates the workspace and raises the kernel's LDS limit).
+ * MFA_ERR_INVALID_ARG: img, d_offsets or d_states is NULL, or d_states is not 16-byte aligned.  MFA_ERR_UNSUPPORTED: a memory automaton,
+ * or a tabulated image (dfa_states != 0: its state is one number and the call above carries it).  All are answered before the device is
+ * touched; n == 0 is MFA_OK. */
+#define MFA_SET_STATE_START   0u           /* first piece; `nodes` is ignored.  A zero-filled buffer is "every string at its start" */
+#define MFA_SET_STATE_LIVE    1u           /* `nodes` is the set reached so far; the empty set is dead: absorbing, rejecting */
+#define MFA_SET_STATE_INVALID 0xffffffffu  /* sticky error */
+typedef struct mfa_set_state { uint32_t tag; uint32_t reserved[3]; uint32_t nodes[8]; } mfa_set_state;   /* 48 bytes */
+int  mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                                mfa_set_state* d_states, uint8_t* d_results, int device, void* stream);
+/* the same with HOST pointers (copy in, match, copy records and results out, synchronise; `states` needs no alignment beyond its type's);
+ * a piece beyond the limit is the sticky error above, not MFA_ERR_TOO_LONG */
+int  mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                                     mfa_set_state* states, uint8_t* results, int device);
 
 /* ---- region tables -------------------------------------------------------------------------------
  * Before a memory automaton walks a batch, one streaming pass over the batch (region_scan_kernel)

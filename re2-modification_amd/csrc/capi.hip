@@ -1,6 +1,7 @@
 // C-ABI of libmfa_hip.so (include/mfa_hip.h): glue between plain-C callers and the kernels.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -136,9 +137,11 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
 }
 
 // A batch given with HOST pointers: checks it, copies it to the device (offsets relative to the first string), runs `match` on the copies,
-// copies the results back and synchronises (throughput is then bounded by the host link).  states != NULL (mfa_match_batch_resume_host):
-// n words that travel to the device and back as well; `results` may then be NULL.  check_lengths: refuse strings beyond the limit.
-int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match, uint32_t* states, bool check_lengths) {
+// copies the results back and synchronises (throughput is then bounded by the host link).  states != NULL (the resume calls' host forms):
+// n records of state_bytes each (one word, or a mfa_set_state) that travel to the device and back as well; `results` may then be NULL.
+// check_lengths: refuse strings beyond the limit.
+int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match, void* states, size_t state_bytes,
+                      bool check_lengths) {
     if (!offsets || (!results && !states && n)) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
     for (uint64_t k = 0; k < n; k++) {
@@ -148,25 +151,25 @@ int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
     int rc = check_device(device);
     if (rc != MFA_OK) return rc;
     const uint64_t total = offsets[n] - offsets[0];
-    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; uint32_t* d_st = nullptr; uint8_t* d_res = nullptr;
+    uint8_t* d_bytes = nullptr; uint64_t* d_off = nullptr; void* d_st = nullptr; uint8_t* d_res = nullptr;
     std::vector<uint64_t> rel(n + 1);
     for (uint64_t k = 0; k <= n; k++) rel[k] = offsets[k] - offsets[0];
     hipError_t e = hipMalloc((void**)&d_bytes, total + 64);
     if (e == hipSuccess) e = hipMalloc((void**)&d_off, (n + 1) * sizeof(uint64_t));
-    if (e == hipSuccess && states) e = hipMalloc((void**)&d_st, n * sizeof(uint32_t));
+    if (e == hipSuccess && states) e = hipMalloc(&d_st, n * state_bytes);
     if (e == hipSuccess && results) e = hipMalloc((void**)&d_res, n);
     if (e == hipSuccess && total) e = hipMemcpy(d_bytes, bytes + offsets[0], total, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && states) e = hipMemcpy(d_st, states, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && states) e = hipMemcpy(d_st, states, n * state_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
     if (rc == MFA_OK) rc = match(d_bytes, d_off, d_res, total, d_st);
     if (rc == MFA_OK) {
         e = hipDeviceSynchronize();
-        if (e == hipSuccess && states) e = hipMemcpy(states, d_st, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && states) e = hipMemcpy(states, d_st, n * state_bytes, hipMemcpyDeviceToHost);
         if (e == hipSuccess && results) e = hipMemcpy(results, d_res, n, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
     }
-    for (void* p : {(void*)d_bytes, (void*)d_off, (void*)d_st, (void*)d_res})
+    for (void* p : {(void*)d_bytes, (void*)d_off, d_st, (void*)d_res})
         if (p) (void)hipFree(p);
     return rc;
 }
@@ -347,7 +350,7 @@ int mfa_region_scan(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t 
 int mfa_match_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results,
                          int device) {
     if (!img) return MFA_ERR_INVALID_ARG;
-    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, uint32_t*) {
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void*) {
         return mfa_match_batch(img, d_bytes, d_off, n, d_res, device, nullptr); });
 }
 
@@ -377,8 +380,39 @@ int mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const ui
     if (!img || !offsets) return MFA_ERR_INVALID_ARG;
     if (img->host.h.kind != MFA_KIND_NFA || img->host.set_walk) return MFA_ERR_UNSUPPORTED;
     if (!states) return MFA_ERR_INVALID_ARG;
-    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, uint32_t* d_st) {
-        return mfa_match_batch_resume(img, d_bytes, d_off, n, d_st, d_res, device, nullptr); }, states, false);
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void* d_st) {
+        return mfa_match_batch_resume(img, d_bytes, d_off, n, (uint32_t*)d_st, d_res, device, nullptr); }, states, sizeof(uint32_t), false);
+}
+
+static_assert(sizeof(mfa_set_state) == 48 && offsetof(mfa_set_state, nodes) == 16, "a record is three 16-byte quarters: tag and reserved, nodes[0..3], nodes[4..7]");
+
+int mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, mfa_set_state* d_states,
+                               uint8_t* d_results, int device, void* stream) {
+    if (!img || !d_offsets || !d_states) return MFA_ERR_INVALID_ARG;
+    if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;      // a memory automaton's state holds spans of the input: nothing to hand over
+    if (!img->host.set_walk) return MFA_ERR_UNSUPPORTED;                   // a tabulated image's state is one number: mfa_match_batch_resume
+    if ((uintptr_t)d_states & 15u) return MFA_ERR_INVALID_ARG;             // the kernel reads and writes a record as 16-byte quarters
+    if (n == 0) return MFA_OK;
+    std::lock_guard<std::mutex> lk(img->mu);
+    DeviceState* ds = nullptr;
+    int rc = device_prepare(img, device, &ds);
+    if (rc != MFA_OK) return rc;
+    LaunchCtx* cx = nullptr;
+    rc = ctx_acquire(*ds, stream, &cx);
+    if (rc != MFA_OK) return rc;
+    DoneGuard done_guard{cx, stream};
+    img->last_kernel = MFA_KERNEL_NODESET;
+    return launch_nfa_set_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
+}
+
+// host pointers: as mfa_match_batch_resume_host, with records of sizeof(mfa_set_state) (the staging buffer is 16-byte aligned whatever
+// `states` is)
+int mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, mfa_set_state* states, uint8_t* results,
+                                    int device) {
+    if (!img || !offsets || !states) return MFA_ERR_INVALID_ARG;
+    if (img->host.h.kind != MFA_KIND_NFA || !img->host.set_walk) return MFA_ERR_UNSUPPORTED;
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void* d_st) {
+        return mfa_match_batch_resume_set(img, d_bytes, d_off, n, (mfa_set_state*)d_st, d_res, device, nullptr); }, states, sizeof(mfa_set_state), false);
 }
 
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {

@@ -130,6 +130,10 @@ int launch_dfa_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, cons
 // nfa_set.hip: the set walk of an image whose tabulation passed the limit (HostImage::set_walk)
 int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                    uint8_t* d_results, void* stream);
+// the same walk with every string's set read from and written to its record of d_states (mfa_match_batch_resume_set: n records of twelve
+// words, 16-byte aligned); d_results may be NULL
+int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                          uint32_t* d_states, uint8_t* d_results, void* stream);
 // workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
 inline uint64_t lds_blocks_per_cu(size_t lds) {
     const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);
@@ -183,10 +187,10 @@ int launch_walk(const WalkPlanInput& p, const uint32_t* d_tables, int n_cus, con
                 uint8_t* d_results, const uint64_t* d_regions, uint32_t n_seg, const uint32_t* seg_first, const uint32_t* seg_table,
                 uint32_t** d_spill, size_t* spill_bytes, unsigned long long* d_counter, void* stream, LeanHint* lean = nullptr, void* wait_event = nullptr);
 void set_last_hip_error(int e);
-// capi.hip: `match` is given the device copies of the bytes, offsets, results, the batch's bytes, and the states (nullptr without)
-typedef std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes, uint32_t* d_states)> HostMatch;
+// capi.hip: `match` is given the device copies of the bytes, offsets, results, the batch's bytes, and the state records (nullptr without)
+typedef std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results, uint64_t total_bytes, void* d_states)> HostMatch;
 int  match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match,
-                       uint32_t* states = nullptr, bool check_lengths = true);
+                       void* states = nullptr, size_t state_bytes = 0, bool check_lengths = true);
 int  check_device(int device);      // MFA_ERR_NO_DEVICE unless `device` exists; makes it the current one
 
 }  // namespace mfa

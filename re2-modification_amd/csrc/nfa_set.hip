@@ -38,9 +38,39 @@ nfa_set_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32
         results[sid] = nfa_set_walk<REV, W>(t, stack, 256u, bytes, offsets[sid], offsets[sid + 1]);
 }
 
+// The same walk for strings in pieces (mfa_match_batch_resume_set): the lane's set comes from its record of `states` (twelve words, read as
+// three aligned 16-byte loads) instead of {start}, and goes back into it behind the piece (three 16-byte stores); `results` may be NULL.
+// Same grid, same LDS layout, same residency cap.  Record and rule: nfa_set_core.h.
 template <bool REV, int W>
+__global__ void __launch_bounds__(256)
+nfa_set_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t stack_words, uint32_t tables_in_lds,
+                      const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint4* __restrict__ states,
+                      uint8_t* __restrict__ results) {
+    extern __shared__ uint32_t lds[];
+    uint32_t* stack = lds + threadIdx.x;
+    const uint32_t* base = tables;
+    if (tables_in_lds) {
+        uint32_t* copy = lds + stack_words;
+        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
+        __syncthreads();
+        base = copy;
+    }
+    const NfaSetView t = nfa_set_view(tables, base);
+    const uint32_t n_nodes = tables[SET_H_NODES];
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t sid = (uint64_t)blockIdx.x * 256u + threadIdx.x; sid < n; sid += stride) {
+        uint4* rec = states + sid * 3u;
+        uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
+        const uint8_t r = nfa_set_resume_piece<REV, W>(t, n_nodes, stack, 256u, bytes, offsets[sid], offsets[sid + 1], q0, q1, q2);
+        rec[0] = q0; rec[1] = q1; rec[2] = q2;
+        if (results) results[sid] = r;
+    }
+}
+
+// d_states == nullptr: nfa_set_kernel; else nfa_set_resume_kernel on these records
+template <bool REV, int W, bool RESUME>
 static int launch_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
-                      uint8_t* d_results, hipStream_t s) {
+                      uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
     const uint32_t words = (uint32_t)img.set_tables.size(), stack_words = img.set_tables[SET_H_DEPTH] * 256u;
     static_assert((size_t)kSetMaxDepth * 256u * 4u <= kSetLdsMax, "the stacks alone fit (nfa_set_build holds an image to kSetMaxDepth)");
     const bool in_lds = ((size_t)stack_words + words) * 4u <= kSetLdsMax;
@@ -48,28 +78,33 @@ static int launch_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, cons
     uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(lds);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    auto kern = nfa_set_kernel<REV, W>;
+    const void* kern = RESUME ? (const void*)nfa_set_resume_kernel<REV, W> : (const void*)nfa_set_kernel<REV, W>;
     // per instantiation and device, once; images hold different locks, so the flags are atomic (two first launches at once both set it)
     static std::atomic<bool> lds_allowed[64];
     const bool tracked = ds.device >= 0 && ds.device < 64;
     if (!tracked || !lds_allowed[ds.device].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSetLdsMax));
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSetLdsMax));
         if (tracked) lds_allowed[ds.device].store(true, std::memory_order_release);
     }
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words, in_lds ? 1u : 0u,
-                       d_bytes, d_offsets, n, d_results);
+    if (RESUME)
+        hipLaunchKernelGGL((nfa_set_resume_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words,
+                           in_lds ? 1u : 0u, d_bytes, d_offsets, n, reinterpret_cast<uint4*>(d_states), d_results);
+    else
+        hipLaunchKernelGGL((nfa_set_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words,
+                           in_lds ? 1u : 0u, d_bytes, d_offsets, n, d_results);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }
 
-int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
-                   uint8_t* d_results, void* stream) {
+template <bool RESUME>
+static int launch_set_by_width(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                               uint32_t* d_states, uint8_t* d_results, void* stream) {
     if (!img.set_walk || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-#define MFA_SET_LAUNCH(W) (img.h.is_reversed ? launch_set<true, W>(img, ds, cx, d_bytes, d_offsets, n, d_results, s) \
-                                             : launch_set<false, W>(img, ds, cx, d_bytes, d_offsets, n, d_results, s))
+#define MFA_SET_LAUNCH(W) (img.h.is_reversed ? launch_set<true, W, RESUME>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s) \
+                                             : launch_set<false, W, RESUME>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s))
     switch (img.set_tables[SET_H_WORDS]) {
         case 1: return MFA_SET_LAUNCH(1);
         case 2: return MFA_SET_LAUNCH(2);
@@ -78,6 +113,16 @@ int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const u
     }
 #undef MFA_SET_LAUNCH
     return MFA_ERR_UNSUPPORTED;
+}
+
+int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                   uint8_t* d_results, void* stream) {
+    return launch_set_by_width<false>(img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, stream);
+}
+
+int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                          uint32_t* d_states, uint8_t* d_results, void* stream) {
+    return launch_set_by_width<true>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, stream);
 }
 
 }  // namespace mfa

@@ -1,6 +1,7 @@
 // The set walk of a memory-less automaton (nfa_set.hip), the part that can be wrong without a GPU: the tables of one automaton, the
-// reference's step (automata.cpp:98-128) on a bit mask of live nodes, and the walk of one string.  Included by the kernel and, with the
-// one-lane shim of tests/emul/, by the host harness tests/emul/nfa_set_emul.cpp.
+// reference's step (automata.cpp:98-128) on a bit mask of live nodes, the walk of one string, and the record that carries a string's set
+// from call to call.  Included by the kernel and, with the
+// one-lane shim of tests/emul/, by the host harnesses tests/emul/nfa_set_emul.cpp and nfa_set_resume_emul.cpp.
 //
 // The engine for automata whose determinisation passes the tabulation limit (image_host.cpp: tabulate_nfa): a lane's state is the SET of
 // live nodes, W 32-bit words of mask (node v = bit v & 31 of word v >> 5), and every input byte runs the reference's own step on it.
@@ -149,14 +150,12 @@ __host__ __device__ __forceinline__ uint8_t nfa_set_accepts(const NfaSetView& t,
     return hit ? (uint8_t)1 : (uint8_t)0;
 }
 
-// One lane, one string [b, e) of the batch, scanned upwards or (REV) downwards: its result byte.  The input is read in aligned 16-byte
-// blocks, and only blocks that hold a byte of the string.  An empty set ends the walk (the reference's `break`) with 0; a string beyond
-// MFA_MAX_STRING_BYTES is not walked and answers 2.
+// One lane, the bytes [b, e) of the batch, scanned upwards or (REV) downwards, from the set in cur: cur becomes the set reached.  Returns 1
+// if that set is not empty (also when there was no byte), 0 if it is -- an empty set ends the walk, the reference's `break` -- and 2 on a
+// stack overflow (cur is then not to be used).  The input is read in aligned 16-byte blocks, and only blocks that hold a byte of [b, e).
 template <bool REV, int W>
-__device__ inline uint8_t nfa_set_walk(const NfaSetView& t, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e) {
-    if (e - b > kSetMaxString) return 2;
-    uint32_t cur[W];
-    nfa_set_start<W>(t, cur);
+__device__ inline uint32_t nfa_set_walk_from(const NfaSetView& t, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e,
+                                             uint32_t (&cur)[W]) {
     uint64_t p = REV ? e : b;                                         // forward: next byte to consume; reverse: one past it
     while (REV ? p > b : p < e) {
         const uint64_t blk = (REV ? p - 1u : p) & ~(uint64_t)15;
@@ -172,11 +171,96 @@ __device__ inline uint8_t nfa_set_walk(const NfaSetView& t, uint32_t* stack, uin
             else { lo64 = lo64 >> 8 | hi64 << 56; hi64 >>= 8; }
             if (k < lo || k >= hi) continue;
             const uint32_t alive = nfa_set_step<W>(t, stack, stride, cur, t.byte_class[byte]);
-            if (alive != 1u) return alive == 0u ? (uint8_t)0 : (uint8_t)2;
+            if (alive != 1u) return alive;
         }
         p = REV ? blk : blk + 16u;
     }
+    return 1u;
+}
+
+// One lane, one string [b, e) of the batch, walked from {start}: its result byte.  A string beyond MFA_MAX_STRING_BYTES is not walked and
+// answers 2.
+template <bool REV, int W>
+__device__ inline uint8_t nfa_set_walk(const NfaSetView& t, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e) {
+    if (e - b > kSetMaxString) return 2;
+    uint32_t cur[W];
+    nfa_set_start<W>(t, cur);
+    const uint32_t alive = nfa_set_walk_from<REV, W>(t, stack, stride, bytes, b, e, cur);
+    if (alive != 1u) return alive == 0u ? (uint8_t)0 : (uint8_t)2;
     return nfa_set_accepts<W>(t, cur);
+}
+
+// ---- strings in pieces (mfa_match_batch_resume_set) -----------------------------------------------------------------------------------
+// The state of the set walk between two bytes is the set itself, so a string may be cut anywhere and its pieces walked one call after the
+// other: a record per string carries the set from call to call.  The record (mfa_set_state, include/mfa_hip.h) is twelve 32-bit words,
+// handled as three 16-byte quarters: q0 = tag, reserved[3]; q1 = nodes[0..3]; q2 = nodes[4..7].  Node v is bit v & 31 of nodes[v >> 5].
+static constexpr uint32_t kSetStateStart = 0u;                 // MFA_SET_STATE_START: {start}, `nodes` is not looked at
+static constexpr uint32_t kSetStateLive = 1u;                  // MFA_SET_STATE_LIVE: `nodes` is the set; the empty set is dead
+static constexpr uint32_t kSetStateInvalid = 0xffffffffu;      // MFA_SET_STATE_INVALID: sticky, answered 2
+static constexpr uint32_t kSetStateWords = 12u;
+static constexpr int kSetStateNodeWords = 8;
+
+// The set a piece of `len` bytes is entered with, unpacked into cur with compile-time indices only (the mask stays in registers): returns
+// kSetStateLive, or kSetStateInvalid for a record this image cannot have written -- a tag other than START or LIVE (INVALID among them,
+// so an error stays one), a reserved word that is not zero, a bit for a node the image lacks (any word beyond its W among them) -- and
+// for a piece beyond the limit.  n_nodes: the header's SET_H_NODES.
+template <int W>
+__host__ __device__ inline uint32_t nfa_set_state_decode(const NfaSetView& t, uint32_t n_nodes, const uint4& q0, const uint4& q1, const uint4& q2, uint64_t len,
+                                                         uint32_t (&cur)[W]) {
+    const uint32_t in[kSetStateNodeWords] = {q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+    bool ok = (q0.y | q0.z | q0.w) == 0u && len <= kSetMaxString;
+    if (q0.x == kSetStateStart) {
+        nfa_set_start<W>(t, cur);
+    } else {
+        ok = ok && q0.x == kSetStateLive;
+#pragma unroll
+        for (int k = 0; k < W; k++) {
+            const uint32_t first = (uint32_t)k * 32u;                // the nodes word k has: first .. min(first + 32, n_nodes)
+            const uint32_t have = n_nodes >= first + 32u ? 0xffffffffu : n_nodes > first ? (1u << (n_nodes - first)) - 1u : 0u;
+            ok = ok && (in[k] & ~have) == 0u;
+            cur[k] = in[k];
+        }
+#pragma unroll
+        for (int k = W; k < kSetStateNodeWords; k++) ok = ok && in[k] == 0u;
+    }
+    if (ok) return kSetStateLive;
+#pragma unroll
+    for (int k = 0; k < W; k++) cur[k] = 0;
+    return kSetStateInvalid;
+}
+
+// the record of a string that has reached cur (tag LIVE), or of one in error (tag INVALID: `nodes` is zero whatever cur holds)
+template <int W>
+__host__ __device__ inline void nfa_set_state_encode(uint32_t tag, const uint32_t (&cur)[W], uint4& q0, uint4& q1, uint4& q2) {
+    uint32_t out[kSetStateNodeWords];
+#pragma unroll
+    for (int k = 0; k < W; k++) out[k] = tag == kSetStateLive ? cur[k] : 0u;
+#pragma unroll
+    for (int k = W; k < kSetStateNodeWords; k++) out[k] = 0u;
+    q0 = make_uint4(tag, 0u, 0u, 0u);
+    q1 = make_uint4(out[0], out[1], out[2], out[3]);
+    q2 = make_uint4(out[4], out[5], out[6], out[7]);
+}
+
+// the result byte of a string whose record says (tag, cur): what mfa_match_batch answers for the concatenation of the pieces so far
+template <int W>
+__host__ __device__ __forceinline__ uint8_t nfa_set_state_result(const NfaSetView& t, uint32_t tag, const uint32_t (&cur)[W]) {
+    return tag == kSetStateLive ? nfa_set_accepts<W>(t, cur) : (uint8_t)2;      // (the empty set meets no mask: 0)
+}
+
+// One lane, one piece [b, e) of the batch: the record in q0, q1, q2 is replaced by the one behind the piece; returns the result byte.  A
+// string that enters dead (LIVE with the empty set) or in error leaves as it came and its bytes are not read.
+template <bool REV, int W>
+__device__ inline uint8_t nfa_set_resume_piece(const NfaSetView& t, uint32_t n_nodes, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e,
+                                               uint4& q0, uint4& q1, uint4& q2) {
+    uint32_t cur[W];
+    uint32_t tag = nfa_set_state_decode<W>(t, n_nodes, q0, q1, q2, e - b, cur);
+    uint32_t any = 0;
+#pragma unroll
+    for (int k = 0; k < W; k++) any |= cur[k];
+    if (tag == kSetStateLive && any != 0u && nfa_set_walk_from<REV, W>(t, stack, stride, bytes, b, e, cur) == 2u) tag = kSetStateInvalid;
+    nfa_set_state_encode<W>(tag, cur, q0, q1, q2);
+    return nfa_set_state_result<W>(t, tag, cur);
 }
 
 }  // namespace mfa

@@ -399,7 +399,7 @@ int mfa_mixed_last_dfa(mfa_mixed_t* mx, int device, uint32_t* multi_launches, ui
 // match_mixed and the `diploma -match-mixed` command line; throughput is then bounded by the host link).
 int mfa_match_mixed_host(mfa_mixed_t* mx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, const uint64_t* seg_first, uint8_t* results, int device) {
     if (!mx || !seg_first) return MFA_ERR_INVALID_ARG;
-    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t total, uint32_t*) {
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t total, void*) {
         return match_mixed_impl(mx, d_bytes, d_off, n, seg_first, d_res, device, nullptr, total); });
 }
 

@@ -368,6 +368,30 @@ def seen_so_far(strings, rounds, r, rev):
     return [s[rounds[r][k][0]:] if rev else s[:rounds[r][k][1]] for k, s in enumerate(strings)]
 
 
+def pieces_against_whole(img, blob, strings, rng, what, oracle_rounds=True):
+    """the strings cut as tests/test_dfa_resume_cpu.py cuts them (testlib.cuts_for), fed in ROUNDS rounds in scan order (a string with fewer pieces gets
+    empty ones): every round's results against the oracle on what has been given so far; final states against ONE call on the whole
+    strings; that call's results against mfa_match_batch and the oracle"""
+    is_rev = image.blob_info(blob)["reversed"]
+    cuts = cuts_for(strings, rng)
+    rounds = rounds_of(strings, cuts, is_rev)
+    ora = oracle_lib.OracleImage(blob)
+    n = len(strings)
+    d_states = new_states(n)
+    for r in range(ROUNDS):
+        got = feed(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states)
+        if oracle_rounds or r == ROUNDS - 1:
+            want = ora.match(seen_so_far(strings, rounds, r, is_rev))
+            bad = np.nonzero(got != want)[0]
+            assert bad.size == 0, "%s round %d: %d mismatches, first string %d (len %d) want %d got %d" % (what, r, bad.size, bad[0], len(strings[bad[0]]), want[bad[0]], got[bad[0]])
+    d_whole = new_states(n)
+    whole = feed(img, strings, d_whole)
+    assert np.array_equal(states_of(d_states, n), states_of(d_whole, n)), what
+    assert np.array_equal(whole, match_on_gpu(img, strings)[0]) and np.array_equal(whole, got), what
+    assert int(states_of(d_whole, n).max()) < img.info()["dfa_states"]
+    assert img.info()["last_kernel"] == capi.KERNEL_TABLE
+
+
 # ---- the set walk's corpus (tests/test_nfa_setwalk_*.py) --------------------------------------------------------------------------------
 LENGTHS = [0, 1, 15, 16, 17, 31, 32, 33, 255, 256, 257, 4096]
 

@@ -83,9 +83,20 @@ typedef struct mfa_image_info {
  * 255 byte classes, no cycle of epsilon edges among the nodes reachable from the start (the reference's evaluateState would not return),
  * epsilon chains of at most 49 nodes.  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
  * mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the device is touched, and mfa_match_batch_resume_set (below)
- * is the call that carries such a set from piece to piece.  What it does not do: a string of any length is walked whole by its
- * lane (no split path; mfa_last_dfa_split and mfa_last_dfa_spec answer zeros); in a mixed object its segment always gets a launch of
- * its own.  mfa_last_kernel_ms covers the kernel.  A string beyond MFA_MAX_STRING_BYTES answers 2. */
+ * is the call that carries such a set from piece to piece.  Long strings: a string of MFA_DFA_SPLIT_MIN bytes or more (default 65536) is
+ * cut into chunks inside the same call, as for a table in L2 (mfa_match_batch below has the scheme): every chunk is walked from ONE node
+ * set by a lane of its own -- the first chunk from the true set, the others from a guess, the set reached over the MFA_SET_SPLIT_LOOKBACK
+ * bytes (default 64) in front of the chunk from {start} or, if that walk dies, from a "home" set chosen per image -- then
+ * MFA_SET_SPLIT_ROUNDS launches (default 3, at most 8; fixed when the call is enqueued) walk again every chunk that was not started from
+ * what its predecessor ended in, and a last step follows each string's chunks from its true set and walks serially whatever still does
+ * not join up.  The answers are exact whatever the guesses were.  The chunk minimum of such an image is 256 bytes (MFA_DFA_CHUNK sets
+ * it); DESIGN.md section 4.9 has the sweep behind the three defaults.  Each chunk takes 144 bytes of the arena (about 25 MB
+ * per overlapping launch).  The extra launches are there from the first call on (no quiet workspace: one long string walked whole costs
+ * seconds).  MFA_SET_SPLIT=0 turns the path off for these images only, MFA_DFA_SPLIT=0 for all; MFA_DFA_SPLIT_MIN, MFA_DFA_CHUNK and
+ * MFA_DFA_ARENA are shared with the tabulated engines.  mfa_last_set_split tells what the last call did; mfa_last_dfa_split and
+ * mfa_last_dfa_spec answer zeros for such an image.  In a mixed object its segment always gets a launch of its own, which cuts long
+ * strings in the same way.  mfa_last_kernel_ms covers the kernel and the launches behind it.  A string beyond MFA_MAX_STRING_BYTES
+ * answers 2. */
 int  mfa_image_create(const void* blob, size_t n_bytes, mfa_image_t** out);
 void mfa_image_destroy(mfa_image_t* img);
 int  mfa_image_get_info(const mfa_image_t* img, mfa_image_info* out);
@@ -205,8 +216,11 @@ int  mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const u
  * stack would overflow (the record names nodes no walk of this image reaches together) leaves tag MFA_SET_STATE_INVALID, `nodes` zero and
  * result 2, and so does every later call on that record.  The SUM of a string's pieces has no limit.  A record that enters LIVE with the
  * empty set leaves the same with result 0 and its bytes are not read.
- * A piece of any length is walked whole by its lane (no split path: the two split-report calls below answer zeros); last_kernel becomes
- * MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launch.  Re-entrant per (image, device, stream), and legal inside a stream capture
+ * A piece of MFA_DFA_SPLIT_MIN bytes or more that enters with a live set is cut across the device as mfa_match_batch cuts a long string
+ * (mfa_image_create has the scheme and the knobs): its first chunk starts from the record's set, and the record and the result byte are
+ * written by the last launch.  Dead, invalid and over-long records are answered as before.  mfa_last_set_split tells what the call did
+ * (mfa_last_dfa_split and mfa_last_dfa_spec answer zeros); last_kernel becomes
+ * MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launches.  Re-entrant per (image, device, stream), and legal inside a stream capture
  * once a first call has run (it allocates the workspace and raises the kernel's LDS limit).
  * MFA_ERR_INVALID_ARG: img, d_offsets or d_states is NULL, or d_states is not 16-byte aligned.  MFA_ERR_UNSUPPORTED: a memory automaton,
  * or a tabulated image (dfa_states != 0: its state is one number and the call above carries it).  All are answered before the device is
@@ -337,6 +351,13 @@ int  mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_
  * bytes walked that way.  All 0 when that path did not run (see above; an LDS table has no guesses).  Same locking, synchronisation and
  * errors as mfa_last_dfa_split. */
 int  mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, uint64_t* serial_strings, uint64_t* serial_bytes);
+/* What cutting long strings did in the last match call on this SET-WALK image and device (mfa_match_batch, mfa_match_batch_resume_set; any
+ * pointer may be NULL): strings taken, chunks they were cut into, the chunk size in bytes the device chose, chunks walked again by the
+ * repair rounds, strings whose chunks still did not join up so that the last step walked their rest serially, and the bytes walked that
+ * way.  All 0 when the path did not run (no long string, another kind of image, MFA_SET_SPLIT=0, MFA_DFA_SPLIT=0).  Same locking,
+ * synchronisation and errors as mfa_last_dfa_split. */
+int  mfa_last_set_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes, uint64_t* rewalked_chunks,
+                        uint64_t* serial_strings, uint64_t* serial_bytes);
 /* Device-side time of the region pass of that launch (0 if it ran none). */
 int  mfa_last_region_ms(mfa_image_t* img, int device, float* ms);
 

@@ -79,7 +79,7 @@ int ctx_acquire(DeviceState& ds, void* stream, LaunchCtx** out) {
         ds.ctxs.push_back(cx);
         pick = cx;
     }
-    pick->used = true; pick->stream = stream; pick->ran_regions = false; pick->split_ran = false; pick->spec_ran = false;
+    pick->used = true; pick->stream = stream; pick->ran_regions = false; pick->split_ran = false; pick->spec_ran = false; pick->set_split_ran = false;
     ds.last = pick;
     *out = pick;
     return MFA_OK;
@@ -440,6 +440,20 @@ int mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, u
     uint32_t h[SPLIT_H_WORDS] = {0};
     const int rc = last_split_header(img, device, &LaunchCtx::spec_ran, h);
     if (rc != MFA_OK) return rc;
+    if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
+    if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
+    if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
+    return MFA_OK;
+}
+
+int mfa_last_set_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes, uint64_t* rewalked_chunks,
+                       uint64_t* serial_strings, uint64_t* serial_bytes) {
+    uint32_t h[SPLIT_H_WORDS] = {0};
+    const int rc = last_split_header(img, device, &LaunchCtx::set_split_ran, h);
+    if (rc != MFA_OK) return rc;
+    if (strings) *strings = h[SPLIT_H_STRINGS];
+    if (chunks) *chunks = h[SPLIT_H_CHUNKS];
+    if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
     if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
     if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
     if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;

@@ -41,25 +41,7 @@ dfa_spec_big_kernel(const T* __restrict__ trans, const uint8_t* __restrict__ acc
     }
 }
 
-// ---- chunks ------------------------------------------------------------------------------------------
-struct SpecChunk { uint32_t q, k; uint64_t b, e, lo, hi; };     // chunk k (scan order) of queued string q = [b, e): the bytes [lo, hi)
-
-// the string of arena chunk c: the last queue entry with first <= c (c < the plan's chunk count, n_q >= 1)
-template <bool REV>
-__device__ __forceinline__ SpecChunk spec_chunk(const SplitEntry* __restrict__ queue, uint32_t n_q, const uint64_t* __restrict__ offsets, uint32_t chunk, uint32_t c) {
-    uint32_t lo = 0u, hi = n_q;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (queue[mid].first <= c) lo = mid; else hi = mid;
-    }
-    SpecChunk r;
-    r.q = lo; r.k = c - queue[lo].first;
-    const uint64_t sid = queue[lo].sid;
-    r.b = offsets[sid]; r.e = offsets[sid + 1u];
-    split_chunk_range<REV>(r.b, r.e, chunk, queue[lo].nc, r.k, &r.lo, &r.hi);
-    return r;
-}
-
+// ---- chunks (spec_chunk: dfa_split.h) ------------------------------------------------------------------
 // Round 0, one lane per chunk: chunk 0 of a string from its true state (1, or its word of `states`), every other from a guess.
 template <bool REV, class T>
 __global__ void __launch_bounds__(256)
@@ -173,7 +155,7 @@ int spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, Sp
     // main kernel alone, so traffic of short strings never pays for the seven launches behind it, and the first batch with long strings on
     // a workspace is walked whole, as it was before this path existed; from the next call on the workspace keeps the tail for good.
     // MFA_DFA_SPLIT=2 launches the tail from the first call on.
-    const int rc = split_begin_arena(cx, n, stream, out, kSpecWordsPerChunk * sizeof(uint32_t), true);
+    const int rc = split_begin_arena(cx, n, stream, out, kSpecWordsPerChunk * sizeof(uint32_t), true, kSplitChunkMin);
     cx.spec_ran = cx.split_ran;
     return rc;
 }

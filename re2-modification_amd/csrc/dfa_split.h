@@ -17,6 +17,8 @@ enum : uint32_t {
     SPLIT_H_WORDS = 8,
 };
 
+static constexpr uint32_t kSplitChunkMin = 4096;            // MFA_DFA_CHUNK of the tabulated engines; DESIGN.md section 4.5 has the sweep
+
 struct SplitEntry {
     uint64_t sid;            // string number
     uint32_t first, nc;      // its first map in the arena, its chunk count; maps are stored in scan order
@@ -46,6 +48,25 @@ __device__ __forceinline__ bool split_take(const SplitArgs& sp, uint64_t sid) {
     if (slot >= sp.qcap) return false;
     sp.queue[slot].sid = sid;
     return true;
+}
+
+// ---- one lane per chunk (dfa_spec.hip, nfa_set_split.hip) -------------------------------------------------
+struct SpecChunk { uint32_t q, k; uint64_t b, e, lo, hi; };     // chunk k (scan order) of queued string q = [b, e): the bytes [lo, hi)
+
+// the string of arena chunk c: the last queue entry with first <= c (c < the plan's chunk count, n_q >= 1)
+template <bool REV>
+__device__ __forceinline__ SpecChunk spec_chunk(const SplitEntry* __restrict__ queue, uint32_t n_q, const uint64_t* __restrict__ offsets, uint32_t chunk, uint32_t c) {
+    uint32_t lo = 0u, hi = n_q;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (queue[mid].first <= c) lo = mid; else hi = mid;
+    }
+    SpecChunk r;
+    r.q = lo; r.k = c - queue[lo].first;
+    const uint64_t sid = queue[lo].sid;
+    r.b = offsets[sid]; r.e = offsets[sid + 1u];
+    split_chunk_range<REV>(r.b, r.e, chunk, queue[lo].nc, r.k, &r.lo, &r.hi);
+    return r;
 }
 
 // ---- state policy --------------------------------------------------------------------------------------

@@ -15,7 +15,6 @@ namespace mfa {
 
 static constexpr uint32_t kSplitQueueCap = 16384;           // long strings per call; the ones beyond are walked by the main kernel
 static constexpr uint32_t kSplitArenaChunks = 131072;       // the chunk size grows so that the chunks stay near this count
-static constexpr uint32_t kSplitChunkMin = 4096;            // MFA_DFA_CHUNK; DESIGN.md section 4.5 has the sweep
 static constexpr uint64_t kSplitMinDefault = 64u * 1024u;   // MFA_DFA_SPLIT_MIN; never below 64 KiB by default
 static constexpr uint32_t kFoldTileBytes = 32768;           // maps of one string staged in LDS per round of the fold
 static constexpr uint32_t kPlanThreads = 1024;
@@ -188,13 +187,14 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
     cx.spec_ran = false;
     if (!split_applies(img)) return MFA_OK;
     out->lanes_log2 = split_lanes_log2(img.dfa_states);
-    return split_begin_arena(cx, n, stream, out, (size_t)1 << out->lanes_log2, false);
+    return split_begin_arena(cx, n, stream, out, (size_t)1 << out->lanes_log2, false, kSplitChunkMin);
 }
 
 // What split_begin and spec_begin (dfa_spec.hip) share: the knobs, the quiet-workspace rule, queue and arena -- `per_chunk` bytes of arena for
 // each of the map_cap chunks the plan can hand out -- and the zeroed header.  *out is the caller's, cleared but for what it has set itself.
 // start_quiet: a workspace counts as quiet from its first call on, not after kSplitQuietCalls calls without a long string (dfa_spec.hip).
-int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet) {
+// chunk_min_default: the chunk minimum where MFA_DFA_CHUNK is not set (kSplitChunkMin; nfa_set_split.hip has its own).
+int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default) {
     const char* on = getenv("MFA_DFA_SPLIT");
     // (n < 2^31: the queue counter is a 32-bit word that every long string increments, also when the queue is full; it must not wrap)
     if ((on && on[0] == '0') || n >= 0x80000000ull) return MFA_OK;
@@ -217,7 +217,7 @@ int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out,
         cx.split_quiet = seen == 1u ? cx.split_quiet + 1u : 0u;
         if (!cx.split_keep && (start_quiet || cx.split_quiet >= kSplitQuietCalls) && !(on && on[0] == '2')) return MFA_OK;      // args.hdr stays NULL: no tail
     }
-    uint64_t chunk_min = (env_u64("MFA_DFA_CHUNK", kSplitChunkMin) + 15u) & ~(uint64_t)15;
+    uint64_t chunk_min = (env_u64("MFA_DFA_CHUNK", chunk_min_default) + 15u) & ~(uint64_t)15;
     if (chunk_min < 16u) chunk_min = 16u;
     if (chunk_min > (1u << 30)) chunk_min = 1u << 30;
     uint64_t arena = env_u64("MFA_DFA_ARENA", kSplitArenaChunks);       // (tests shrink it to see the chunk size grow)

@@ -224,7 +224,36 @@ int nfa_set_build(HostImage& img) {
     out[SET_H_TOTAL] = (uint32_t)out.size();
     img.set_walk = true;
     img.dfa_states = 0; img.dfa_trans.clear(); img.dfa_accept.clear();
+    nfa_set_home(img, img.set_home);
     return MFA_OK;
+}
+
+// The second seed of nfa_set_split.hip's guesses (nfa_set_split_core.h), for texts on which a walk from {start} dies in mid-text: what
+// spec_home_state (dfa_spec_core.h) is for a table, on node sets.  The set a deterministic pseudo-random walk from {start} ends in:
+// every step draws a byte class (xorshift32, the seed of spec_home_state) and takes the first class from there on, cyclically, whose
+// step (Stepper: the norm) does not lead to the empty set; a set with no such class ends the walk.  4096 steps.  Never empty.
+// img.byte_class and img.n_classes are nfa_byte_classes' (nfa_set_build has called it).
+void nfa_set_home(const HostImage& img, uint32_t (&home)[8]) {
+    const uint32_t n = img.h.n_nodes, C = img.n_classes;
+    std::vector<int> rep(C, 0);
+    for (int b = 255; b >= 0; b--) rep[img.byte_class[b]] = b;       // (any byte of a class steps alike)
+    Stepper st(img);
+    std::vector<uint8_t> cur(n, 0);
+    cur[img.h.start] = 1;
+    uint32_t x = 0x9e3779b9u;
+    for (uint32_t step = 0; step < 4096u && C != 0u; step++) {
+        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
+        const uint32_t c0 = x % C;
+        bool moved = false;
+        for (uint32_t k = 0; k < C && !moved; k++) {
+            const std::vector<uint8_t> nx = st.step(cur, rep[(c0 + k) % C]);
+            if (std::find(nx.begin(), nx.end(), (uint8_t)1) != nx.end()) { cur = nx; moved = true; }
+        }
+        if (!moved) break;
+    }
+    for (uint32_t& w : home) w = 0u;
+    for (uint32_t v = 0; v < n && v < 256u; v++)
+        if (cur[v]) home[v >> 5] |= 1u << (v & 31u);
 }
 
 // What mfa_image_create does with a memory-less automaton: tabulate it, and when the state sets pass the limit (MFA_DFA_STATE_LIMIT,

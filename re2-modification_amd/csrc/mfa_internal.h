@@ -43,6 +43,7 @@ struct HostImage {
     // MFA_KIND_NFA whose tabulation passed the limit: the tables of the set walk (nfa_set_core.h); dfa_states is then 0
     bool                  set_walk = false;
     std::vector<uint32_t> set_tables;
+    uint32_t              set_home[8] = {0};   //   ... and the second seed of nfa_set_split.hip's guesses, a node set (image_host.cpp: nfa_set_home)
     mutable int           jit_source_ok = -1;      // MFA kind: the generated kernel's source is of a size a compiler finishes (jit.hip; -1 = not looked at)
 };
 
@@ -50,6 +51,7 @@ int parse_blob(const void* blob, size_t n_bytes, HostImage& out);   // MFA_OK / 
 int check_mfa_invariants(const HostImage& img);                      // MFA_OK / MFA_ERR_UNSUPPORTED
 int tabulate_nfa(HostImage& img, uint32_t max_states = MFA_MAX_DFA_STATES, std::vector<std::string>* sets_out = nullptr);   // fills the dfa_* members; MFA_ERR_UNSUPPORTED beyond max_states state sets
 int nfa_set_build(HostImage& img);                                   // fills set_tables instead (MFA_ERR_UNSUPPORTED: outside the set walk's limits)
+void nfa_set_home(const HostImage& img, uint32_t (&home)[8]);        // a set-walk image's home set (nfa_set_build fills set_home with it)
 int nfa_image_build(HostImage& img);                                 // MFA_KIND_NFA at image creation: one or the other
 
 // ---- per-device state -----------------------------------------------------------------------
@@ -83,6 +85,7 @@ struct LaunchCtx {
     bool                split_keep = false;    // a launch without the split kernels met a long string once: this workspace keeps them
     bool                split_ran = false;     // this launch has the split kernels behind its main kernel
     bool                spec_ran = false;      //   ... those of dfa_spec.hip (a table in L2): its header holds the words of mfa_last_dfa_spec
+    bool                set_split_ran = false; // this launch has the kernels of nfa_set_split.hip behind its main kernel (mfa_last_set_split; the two above stay false)
 };
 
 struct DeviceState {
@@ -149,7 +152,7 @@ struct SplitLaunch {
 uint64_t env_u64(const char* name, uint64_t dflt);
 bool split_applies(const HostImage& img);
 int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
-int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet);
+int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default);
 int  split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream);
 // d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
@@ -163,6 +166,12 @@ int  spec_main(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, con
                uint8_t* d_results, void* stream, uint32_t* d_states, unsigned blocks);
 int  spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
+// nfa_set_split.hip: the same three steps for a set-walk image.  set_split_begin leaves out->args.split_min == 0 when the path is off
+// (MFA_SET_SPLIT=0, MFA_DFA_SPLIT=0, n >= 2^31); nfa_set.hip hands out->args to its main kernel and calls set_split_tail behind it.
+// d_states != NULL (mfa_match_batch_resume_set): chunk 0 of a queued piece starts from its record, which gets the set reached.
+int  set_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+int  set_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                    uint8_t* d_results, void* stream, uint32_t* d_states);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

@@ -7,93 +7,86 @@
 //   Input: 16 bytes per lane per load, in aligned blocks that hold a byte of the string: nothing beyond offsets[n] rounded up to 16.
 //   Grid: persistent, capped by what the CUs keep resident (lds_blocks_per_cu), strings dealt out by lane number.
 // Supported: up to 256 nodes (W = 1, 2, 4, 8 words for up to 32, 64, 128, 256), 255 byte classes, epsilon chains of up to 49 nodes.
-// A long string is walked whole by its lane: the state is a set, not a number, and the split paths compose maps of numbers.
+// A long string is cut across the whole GPU by nfa_set_split.hip, behind the main kernel of this file.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
-#include "mfa_internal.h"
-#include "nfa_set_core.h"
+#include "nfa_set.h"
 
 namespace mfa {
 
-static constexpr size_t kSetLdsMax = 64u * 1024u;
-
+// A string of sp.split_min bytes or more (and within the limit) is handed to nfa_set_split.hip (split_take: the one hand-over, no string
+// is lost); sp.split_min == 0: the queue is off and every string is walked here, as before that path existed.
 template <bool REV, int W>
 __global__ void __launch_bounds__(256)
 nfa_set_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t stack_words, uint32_t tables_in_lds,
-               const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results) {
+               const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     uint32_t* stack = lds + threadIdx.x;                               // slot s of this lane: stack[s * 256]
-    const uint32_t* base = tables;
-    if (tables_in_lds) {
-        uint32_t* copy = lds + stack_words;
-        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
-        __syncthreads();
-        base = copy;
-    }
-    const NfaSetView t = nfa_set_view(tables, base);
+    const NfaSetView t = nfa_set_view(tables, set_tables_base(lds, tables, table_words, stack_words, tables_in_lds));
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
-    for (uint64_t sid = (uint64_t)blockIdx.x * 256u + threadIdx.x; sid < n; sid += stride)
-        results[sid] = nfa_set_walk<REV, W>(t, stack, 256u, bytes, offsets[sid], offsets[sid + 1]);
+    for (uint64_t sid = (uint64_t)blockIdx.x * 256u + threadIdx.x; sid < n; sid += stride) {
+        const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        if (sp.split_min != 0u && e - b >= sp.split_min && e - b <= kSetMaxString && split_take(sp, sid)) continue;      // queued: the result is nfa_set_resolve_kernel's
+        results[sid] = nfa_set_walk<REV, W>(t, stack, 256u, bytes, b, e);
+    }
 }
 
 // The same walk for strings in pieces (mfa_match_batch_resume_set): the lane's set comes from its record of `states` (twelve words, read as
 // three aligned 16-byte loads) instead of {start}, and goes back into it behind the piece (three 16-byte stores); `results` may be NULL.
-// Same grid, same LDS layout, same residency cap.  Record and rule: nfa_set_core.h.
+// Same grid, same LDS layout, same residency cap.  Record and rule: nfa_set_core.h.  Only a piece that enters with a live set is queued:
+// dead, invalid and over-long records are answered here, and a queued piece's record is left as it came for the kernels behind this one.
 template <bool REV, int W>
 __global__ void __launch_bounds__(256)
 nfa_set_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t stack_words, uint32_t tables_in_lds,
                       const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint4* __restrict__ states,
-                      uint8_t* __restrict__ results) {
+                      uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     uint32_t* stack = lds + threadIdx.x;
-    const uint32_t* base = tables;
-    if (tables_in_lds) {
-        uint32_t* copy = lds + stack_words;
-        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
-        __syncthreads();
-        base = copy;
-    }
-    const NfaSetView t = nfa_set_view(tables, base);
+    const NfaSetView t = nfa_set_view(tables, set_tables_base(lds, tables, table_words, stack_words, tables_in_lds));
     const uint32_t n_nodes = tables[SET_H_NODES];
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
     for (uint64_t sid = (uint64_t)blockIdx.x * 256u + threadIdx.x; sid < n; sid += stride) {
         uint4* rec = states + sid * 3u;
         uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
-        const uint8_t r = nfa_set_resume_piece<REV, W>(t, n_nodes, stack, 256u, bytes, offsets[sid], offsets[sid + 1], q0, q1, q2);
+        const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        uint32_t cur[W];
+        const uint32_t tag = nfa_set_state_decode<W>(t, n_nodes, q0, q1, q2, e - b, cur);
+        if (sp.split_min != 0u && e - b >= sp.split_min && tag == kSetStateLive) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int k = 0; k < W; k++) any |= cur[k];
+            if (any != 0u && split_take(sp, sid)) continue;
+        }
+        const uint8_t r = nfa_set_resume_entered<REV, W>(t, stack, 256u, bytes, b, e, tag, cur, q0, q1, q2);
         rec[0] = q0; rec[1] = q1; rec[2] = q2;
         if (results) results[sid] = r;
     }
 }
 
-// d_states == nullptr: nfa_set_kernel; else nfa_set_resume_kernel on these records
+// d_states == nullptr: nfa_set_kernel; else nfa_set_resume_kernel on these records.  Behind either, the kernels of nfa_set_split.hip for
+// the strings it queued (set_split_begin, set_split_tail); ev_start and ev_stop enclose all of it.
 template <bool REV, int W, bool RESUME>
 static int launch_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
-    const uint32_t words = (uint32_t)img.set_tables.size(), stack_words = img.set_tables[SET_H_DEPTH] * 256u;
-    static_assert((size_t)kSetMaxDepth * 256u * 4u <= kSetLdsMax, "the stacks alone fit (nfa_set_build holds an image to kSetMaxDepth)");
-    const bool in_lds = ((size_t)stack_words + words) * 4u <= kSetLdsMax;
-    const size_t lds = ((size_t)stack_words + (in_lds ? words : 0u)) * 4u;
-    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(lds);
+    const SetLds l = set_lds_of(img);
+    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(l.bytes);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    const void* kern = RESUME ? (const void*)nfa_set_resume_kernel<REV, W> : (const void*)nfa_set_kernel<REV, W>;
-    // per instantiation and device, once; images hold different locks, so the flags are atomic (two first launches at once both set it)
-    static std::atomic<bool> lds_allowed[64];
-    const bool tracked = ds.device >= 0 && ds.device < 64;
-    if (!tracked || !lds_allowed[ds.device].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSetLdsMax));
-        if (tracked) lds_allowed[ds.device].store(true, std::memory_order_release);
-    }
+    int rc = RESUME ? set_allow_lds<nfa_set_resume_kernel<REV, W>>(ds.device) : set_allow_lds<nfa_set_kernel<REV, W>>(ds.device);
+    if (rc != MFA_OK) return rc;
+    SplitLaunch sl;
+    rc = set_split_begin(img, cx, n, s, &sl);
+    if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
     if (RESUME)
-        hipLaunchKernelGGL((nfa_set_resume_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words,
-                           in_lds ? 1u : 0u, d_bytes, d_offsets, n, reinterpret_cast<uint4*>(d_states), d_results);
+        hipLaunchKernelGGL((nfa_set_resume_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.stack_words,
+                           l.in_lds, d_bytes, d_offsets, n, reinterpret_cast<uint4*>(d_states), d_results, sl.args);
     else
-        hipLaunchKernelGGL((nfa_set_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), lds, s, (const uint32_t*)ds.d_set_tables, words, stack_words,
-                           in_lds ? 1u : 0u, d_bytes, d_offsets, n, d_results);
+        hipLaunchKernelGGL((nfa_set_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.stack_words,
+                           l.in_lds, d_bytes, d_offsets, n, d_results, sl.args);
     HIP_TRY(hipGetLastError());
+    rc = set_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
+    if (rc != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }

@@ -248,19 +248,28 @@ __host__ __device__ __forceinline__ uint8_t nfa_set_state_result(const NfaSetVie
     return tag == kSetStateLive ? nfa_set_accepts<W>(t, cur) : (uint8_t)2;      // (the empty set meets no mask: 0)
 }
 
-// One lane, one piece [b, e) of the batch: the record in q0, q1, q2 is replaced by the one behind the piece; returns the result byte.  A
-// string that enters dead (LIVE with the empty set) or in error leaves as it came and its bytes are not read.
+// The piece [b, e) of a string that nfa_set_state_decode has entered with (tag, cur): the record behind the piece goes to q0, q1, q2;
+// returns the result byte.  (Apart from nfa_set_resume_piece so that a kernel can look at what the string enters with -- a long piece
+// with a live set is handed to nfa_set_split.hip -- without decoding twice.)
 template <bool REV, int W>
-__device__ inline uint8_t nfa_set_resume_piece(const NfaSetView& t, uint32_t n_nodes, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e,
-                                               uint4& q0, uint4& q1, uint4& q2) {
-    uint32_t cur[W];
-    uint32_t tag = nfa_set_state_decode<W>(t, n_nodes, q0, q1, q2, e - b, cur);
+__device__ inline uint8_t nfa_set_resume_entered(const NfaSetView& t, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e, uint32_t tag,
+                                                 uint32_t (&cur)[W], uint4& q0, uint4& q1, uint4& q2) {
     uint32_t any = 0;
 #pragma unroll
     for (int k = 0; k < W; k++) any |= cur[k];
     if (tag == kSetStateLive && any != 0u && nfa_set_walk_from<REV, W>(t, stack, stride, bytes, b, e, cur) == 2u) tag = kSetStateInvalid;
     nfa_set_state_encode<W>(tag, cur, q0, q1, q2);
     return nfa_set_state_result<W>(t, tag, cur);
+}
+
+// One lane, one piece [b, e) of the batch: the record in q0, q1, q2 is replaced by the one behind the piece; returns the result byte.  A
+// string that enters dead (LIVE with the empty set) or in error leaves as it came and its bytes are not read.
+template <bool REV, int W>
+__device__ inline uint8_t nfa_set_resume_piece(const NfaSetView& t, uint32_t n_nodes, uint32_t* stack, uint32_t stride, const uint8_t* bytes, uint64_t b, uint64_t e,
+                                               uint4& q0, uint4& q1, uint4& q2) {
+    uint32_t cur[W];
+    const uint32_t tag = nfa_set_state_decode<W>(t, n_nodes, q0, q1, q2, e - b, cur);
+    return nfa_set_resume_entered<REV, W>(t, stack, stride, bytes, b, e, tag, cur, q0, q1, q2);
 }
 
 }  // namespace mfa

@@ -188,11 +188,13 @@ void piece_of(uint64_t b, uint64_t e, uint64_t r, bool reversed, uint64_t* lo, u
     else { *lo = b + skip; *hi = *lo + take; }
 }
 
-// the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call
-void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
+// the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call.  set_walk: the
+// image walks node sets (dfa_states == 0), so a string's state between two pieces is a record of mfa_match_batch_resume_set_host, not one word
+void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
     uint64_t rounds = 1;
     for (uint64_t k : which) rounds = std::max(rounds, (offsets[k + 1] - offsets[k] + kPieceBytes - 1) / kPieceBytes);
-    vector<uint32_t> states(which.size(), MFA_DFA_STATE_START);
+    vector<uint32_t> states(set_walk ? 0 : which.size(), MFA_DFA_STATE_START);
+    vector<mfa_set_state> sets(set_walk ? which.size() : 0, mfa_set_state{});      // zeroed: MFA_SET_STATE_START
     vector<uint8_t> res(which.size()), stage;
     vector<uint64_t> off(which.size() + 1);
     for (uint64_t r = 0; r < rounds; r++) {
@@ -205,8 +207,10 @@ void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const 
             off[j + 1] = stage.size();
         }
         stage.resize(stage.size() + 16);
-        const int rc = mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), r + 1 == rounds ? res.data() : nullptr, device);
-        if (rc != MFA_OK) fail("mfa_match_batch_resume_host", rc);
+        uint8_t* out = r + 1 == rounds ? res.data() : nullptr;
+        const int rc = set_walk ? mfa_match_batch_resume_set_host(img, stage.data(), off.data(), which.size(), sets.data(), out, device)
+                                : mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), out, device);
+        if (rc != MFA_OK) fail(set_walk ? "mfa_match_batch_resume_set_host" : "mfa_match_batch_resume_host", rc);
     }
     for (size_t j = 0; j < which.size(); j++) results[which[j]] = res[j];
 }
@@ -216,8 +220,9 @@ void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const 
 void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     mfa_image* img = image_for_match();
     mfa_image_info info;
-    // (a set-walk image -- dfa_states == 0 -- hands no state from call to call: a string beyond the limit is refused as a memory automaton's is)
-    if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA && info.dfa_states != 0) {
+    // (a memory-less image hands its state from call to call -- one word, or for a set-walk image, dfa_states == 0, a record of node sets --
+    // so its strings may be longer than one call takes; a memory automaton's are refused)
+    if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA) {
         vector<uint64_t> longs;
         for (uint64_t k = 0; k < n; k++)
             if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) longs.push_back(k);
@@ -229,7 +234,7 @@ void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint6
                 if (to > from) match_packed_short(img, bytes, offsets + from, to - from, results + from);
                 from = to + 1;
             }
-            match_in_pieces(img, info.is_reversed != 0, bytes, offsets, longs, results, device);
+            match_in_pieces(img, info.is_reversed != 0, info.dfa_states == 0, bytes, offsets, longs, results, device);
             return;
         }
     }
@@ -396,7 +401,7 @@ vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector
     vector<Automata*> long_owner;
     for (size_t k = 0; k < strs.size(); k++) {
         mfa_image_info info;
-        const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA && info.dfa_states != 0;      // (tabulated: its strings may go in pieces)
+        const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA;      // (tabulated or set walk: its strings may go in pieces)
         for (const string& s : strs[k]) {
             if (memory_less && s.size() > MFA_MAX_STRING_BYTES) { longs.push_back({off.size() - 1, &s}); long_owner.push_back(automata[k]); }
             else bytes.insert(bytes.end(), s.begin(), s.end());

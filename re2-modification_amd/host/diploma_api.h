@@ -136,8 +136,8 @@ public:
     bool isDeterministic();
 
     // reference automata.cpp:177-210, on the GPU (a batch of one).  A memory-less automaton takes strings of any length: one beyond the
-    // device's per-call limit (MFA_MAX_STRING_BYTES) is cut into pieces of 8 MiB that go through mfa_match_batch_resume_host round by
-    // round, last piece first for a reversed automaton; match_batch, match_packed and the memory-less segments of match_mixed do the
+    // device's per-call limit (MFA_MAX_STRING_BYTES) is cut into pieces of 8 MiB that go through mfa_match_batch_resume_host (for an automaton
+    // walked as a set of nodes: mfa_match_batch_resume_set_host) round by round, last piece first for a reversed automaton; match_batch, match_packed and the memory-less segments of match_mixed do the
     // same, and the shorter strings of the batch take the one call they always took.  A memory automaton refuses such a string as before.
     bool match(const string& str);
     // the same for many strings in one launch; result[k] is what match(strs[k]) returns

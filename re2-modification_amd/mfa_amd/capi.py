@@ -20,7 +20,7 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_mixed_create", "mfa_mixed_destroy", "mfa_match_mixed", "mfa_match_mixed_sized", "mfa_match_mixed_host", "mfa_mixed_last_ms", "mfa_mixed_timing",
            "mfa_mixed_last_launches", "mfa_mixed_last_dfa", "mfa_pack_result_bitmap", "mfa_last_dfa_split",
            "mfa_match_batch_resume", "mfa_match_batch_resume_host", "mfa_last_dfa_spec",
-           "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host"]
+           "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 SET_STATE_WORDS = 12                                                        # a record of mfa_match_batch_resume_set: tag, reserved[3], nodes[8]
@@ -82,6 +82,8 @@ def lib():
             L.mfa_last_dfa_split.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32)]
         if hasattr(L, "mfa_last_dfa_spec"):               # (as above: an older build)
             L.mfa_last_dfa_spec.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        if hasattr(L, "mfa_last_set_split"):              # (as above: an older build)
+            L.mfa_last_set_split.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32)] + [ctypes.POINTER(u64)] * 3
         L.mfa_mixed_create.argtypes = [ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp)]
         L.mfa_mixed_destroy.argtypes = [vp]
         L.mfa_mixed_destroy.restype = None
@@ -244,6 +246,15 @@ class Image:
         rw, ss, sb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mfa_last_dfa_spec(self._h, device, ctypes.byref(rw), ctypes.byref(ss), ctypes.byref(sb)), "mfa_last_dfa_spec")
         return rw.value, ss.value, sb.value
+
+    def last_set_split(self, device=0):
+        """(strings, chunks, chunk_bytes, rewalked_chunks, serial_strings, serial_bytes) of the split path for long strings of a set-walk
+        image in the last match call; all 0 if it did not run"""
+        st, ch, cb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        rw, ss, sb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mfa_last_set_split(self._h, device, ctypes.byref(st), ctypes.byref(ch), ctypes.byref(cb), ctypes.byref(rw), ctypes.byref(ss),
+                                        ctypes.byref(sb)), "mfa_last_set_split")
+        return st.value, ch.value, cb.value, rw.value, ss.value, sb.value
 
     def close(self):
         if self._h:

@@ -12,6 +12,15 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
       lines appended to profiles/r12_nfa_set_resume.jsonl
 
   nfa_setwalk.py [REPS] [STRINGS] [all|tables|resume]      tables: (a) and (b) only; resume: (c) only
+
+  nfa_setwalk.py long sweep|gain|short [REPS] [OUT.jsonl]   long strings cut across the GPU (csrc/nfa_set_split.hip), on (a|b)*abb forced to the
+      set walk and on the k = 20 Thompson image; random ab; one JSON line per measurement, appended to OUT.jsonl (default
+      profiles/r13_nfa_set_split.jsonl).  Medians of REPS calls (default 7) after five uncounted ones; the answers of the first two
+      strings are held to the CPU restatement.
+      sweep   8 x 1 MiB and 8 x (16 MiB - 1): MFA_DFA_CHUNK 256 .. 4096 x MFA_SET_SPLIT_LOOKBACK 32 .. 256 x MFA_SET_SPLIT_ROUNDS 0, 3
+      gain    8 x 1 MiB with the library's defaults against MFA_SET_SPLIT=0 (the whole walk: one uncounted call and three counted ones, it
+              takes seconds per call)
+      short   1 Mi x 1 KiB (no long string): this build's kernel time per call, to be set against another build's (MFA_LIB_PATH) process by process
 """
 import json
 import os
@@ -124,7 +133,79 @@ def compare_resume(what, img, blob, flat, d_off, reps):
         f.write(line + "\n")
 
 
+_WANT = {}
+
+
+def long_measure(what, img, blob, flat, d_off, reps, warm, env, out_path):
+    """median kernel time of `reps` calls after `warm` uncounted ones under the knobs of `env` (read per call), one JSON line"""
+    for k, v in env.items():
+        os.environ[k] = str(v)
+    n = d_off.numel() - 1
+    res = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+    ms = []
+    for _ in range(warm + reps):
+        img.match_tensors(flat, d_off, res)
+        ms.append(img.last_kernel_ms(0))
+    report = img.last_set_split(0) if hasattr(capi.lib(), "mfa_last_set_split") else None
+    for k in env:
+        del os.environ[k]
+    m = min(n, 2 if int(d_off[1]) > SAMPLE else SAMPLE)
+    off = d_off[:m + 1].cpu().numpy().astype(np.uint64)
+    key = (id(blob), flat.data_ptr())
+    if key not in _WANT:                                   # (once per image and batch: the sweep comes back to them)
+        _WANT[key] = oracle_lib.OracleImage(blob).match_packed(flat[:int(off[-1])].cpu().numpy(), off).astype(np.uint8)[:m]
+    want = _WANT[key]
+    total = int(d_off[-1])
+    med = float(np.median(ms[warm:]))
+    out = {"what": what, "device": torch.cuda.get_device_name(0), "strings": n, "bytes": total, "knobs": env, "kernel_ms": ms[warm:], "median_ms": med,
+           "spread_ms": float(max(ms[warm:]) - min(ms[warm:])), "MB/s": total / (med * 1e-3) / 1e6, "results_exact_on_sample": bool(np.array_equal(res[:m].cpu().numpy(), want)),
+           "sample": m, "set_split(strings,chunks,chunk_bytes,rewalked,serial_strings,serial_bytes)": report, "lib": os.environ.get("MFA_LIB_PATH", "this build"),
+           "kernel": KERNELS[img.info()["last_kernel"]]}
+    line = json.dumps(out)
+    print(line, flush=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+    return med
+
+
+def long_main():
+    mode = sys.argv[2] if len(sys.argv) > 2 else "sweep"
+    reps = max(3, int(sys.argv[3])) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "r13_nfa_set_split.jsonl")
+    assert mode in ("sweep", "gain", "short")
+    abb = image.blob_from_dump(oracle_lib.load_dump("nfa_abb_thompson"))
+    images = [("(a|b)*abb forced to the set walk (W = 1)", created(abb, "1")[0], abb)]
+    if mode != "short" or "k20" in sys.argv:
+        b20 = front_end("(a|b)*a" + "(a|b)" * 20, "-thompson")
+        images.append(("(a|b)*a(a|b)^20 Thompson (W = 4)", created(b20)[0], b20))
+    assert all(img.info()["dfa_states"] == 0 for _, img, _ in images)
+    if mode == "short":
+        flat, d_off, _ = batch([1024] * (1 << 20), 2)
+        for name, img, blob in images:
+            long_measure("1 Mi x 1 KiB, " + name, img, blob, flat, d_off, reps, 5, {}, out_path)
+        return
+    mib = batch([1 << 20] * 8, 5)
+    if mode == "gain":
+        for name, img, blob in images:
+            cut = long_measure("8 x 1 MiB, cut (defaults), " + name, img, blob, mib[0], mib[1], reps, 5, {}, out_path)
+            whole = long_measure("8 x 1 MiB, walked whole, " + name, img, blob, mib[0], mib[1], 3, 1, {"MFA_SET_SPLIT": 0}, out_path)
+            print(json.dumps({"what": "gain, " + name, "whole_over_cut": whole / cut}), flush=True)
+        return
+    big = batch([(16 << 20) - 1] * 8, 6)
+    for name, img, blob in images:
+        for label, (flat, d_off, _) in (("8 x 1 MiB", mib), ("8 x (16 MiB - 1)", big)):
+            for chunk in (256, 512, 1024, 2048, 4096):
+                if (int(d_off[-1]) // 131072 + 15) // 16 * 16 > chunk:      # the arena makes the device choose a larger chunk: the same run as that one
+                    continue
+                for lookback in (32, 64, 128, 256):
+                    for rounds in (0, 3):
+                        long_measure("%s, %s" % (label, name), img, blob, flat, d_off, reps, 5,
+                                     {"MFA_DFA_CHUNK": chunk, "MFA_SET_SPLIT_LOOKBACK": lookback, "MFA_SET_SPLIT_ROUNDS": rounds}, out_path)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "long":
+        return long_main()
     reps = max(5, int(sys.argv[1]) if len(sys.argv) > 1 else 7)
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 1 << 20
     which = sys.argv[3] if len(sys.argv) > 3 else "all"

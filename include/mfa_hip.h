@@ -68,7 +68,7 @@ typedef struct mfa_image_info {
 #define MFA_KERNEL_WALK        1u /* walk_kernel: table-driven memory-automaton walk over a list of live states (any automaton, no compiler) */
 #define MFA_KERNEL_SPECIALISED 2u /* mfa_jit_kernel: the walk generated for one automaton, one slot per node in VGPRs */
 #define MFA_KERNEL_TABLE       3u /* dfa_walk_kernel: tabulated memory-less automaton                    */
-#define MFA_KERNEL_NODESET     4u /* nfa_set_kernel, nfa_set_resume_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
+#define MFA_KERNEL_NODESET     4u /* nfa_set_kernel, nfa_set_resume_kernel, nfa_set_wave_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
 
 /* Build an image from a blob (include/mfa_image_format.h).  Host-only work: parse,
  * check the structural invariants the kernels rely on, and for MFA_KIND_NFA tabulate
@@ -79,9 +79,16 @@ typedef struct mfa_image_info {
  * from the environment) is not tabulated: the image keeps the automaton's nodes, dfa_states is 0, and the match calls walk the SET of
  * live nodes, one string per lane, with the reference's own step per byte (last_kernel: MFA_KERNEL_NODESET).  MFA_NFA_SETWALK=1 makes
  * every memory-less image such an image without tabulating, MFA_NFA_SETWALK=0 none (beyond the limit: MFA_ERR_UNSUPPORTED, as it used
- * to be); both knobs are read here, at image creation.  Limits of such an image (MFA_ERR_UNSUPPORTED at creation): at most 256 nodes and
+ * to be); both knobs are read here, at image creation.  Limits of such an image (MFA_ERR_UNSUPPORTED at creation): at most 2048 nodes and
  * 255 byte classes, no cycle of epsilon edges among the nodes reachable from the start (the reference's evaluateState would not return),
- * epsilon chains of at most 49 nodes.  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
+ * and, for an image of up to 256 nodes, epsilon chains of at most 49 nodes.  Wave images: up to 256 nodes a lane holds the set and walks
+ * a string (nfa_set_kernel); an image of 257 to 2048 nodes is a WAVE image: one string per wave, the set across its 64 lanes
+ * (nfa_set_wave_kernel; last_kernel is MFA_KERNEL_NODESET all the same), epsilon chains of any length.  mfa_match_batch, _host, _regions
+ * and a mixed object walk every string of a wave image whole, whatever its length up to MFA_MAX_STRING_BYTES: nothing below about long
+ * strings or strings in pieces applies to it -- no string is cut (one long string holds one wave for its whole length),
+ * mfa_last_set_split answers zeros, and mfa_match_batch_resume_set refuses it.  MFA_SET_WAVE=1, read here too, makes EVERY set-walk
+ * image a wave image, the narrow ones as well: a knob for measurements and tests, never the default (the lane kernel is many times
+ * faster where it applies).  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
  * mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the device is touched, and mfa_match_batch_resume_set (below)
  * is the call that carries such a set from piece to piece.  Long strings: a string of MFA_DFA_SPLIT_MIN bytes or more (default 65536) is
  * cut into chunks inside the same call, as for a table in L2 (mfa_match_batch below has the scheme): every chunk is walked from ONE node
@@ -223,8 +230,9 @@ int  mfa_match_batch_resume_host(mfa_image_t* img, const uint8_t* bytes, const u
  * MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launches.  Re-entrant per (image, device, stream), and legal inside a stream capture
  * once a first call has run (it allocates the workspace and raises the kernel's LDS limit).
  * MFA_ERR_INVALID_ARG: img, d_offsets or d_states is NULL, or d_states is not 16-byte aligned.  MFA_ERR_UNSUPPORTED: a memory automaton,
- * or a tabulated image (dfa_states != 0: its state is one number and the call above carries it).  All are answered before the device is
- * touched; n == 0 is MFA_OK. */
+ * a tabulated image (dfa_states != 0: its state is one number and the call above carries it), or a wave image (more than 256 nodes, or
+ * made under MFA_SET_WAVE=1: its set may take 64 words and a record has eight; the records are left as they came).  All are answered
+ * before the device is touched; n == 0 is MFA_OK. */
 #define MFA_SET_STATE_START   0u           /* first piece; `nodes` is ignored.  A zero-filled buffer is "every string at its start" */
 #define MFA_SET_STATE_LIVE    1u           /* `nodes` is the set reached so far; the empty set is dead: absorbing, rejecting */
 #define MFA_SET_STATE_INVALID 0xffffffffu  /* sticky error */

@@ -291,7 +291,7 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
     // MFA_VERBOSE=1: which kernel walks, on stderr
     if (is_mfa && !jit) { const char* rq = getenv("MFA_REQUIRE_JIT"); if (rq && rq[0] == '1') return MFA_ERR_JIT; }
     if (const char* vb = getenv("MFA_VERBOSE"))
-        if (vb[0] == '1') fprintf(stderr, "mfa_hip: %s\n", !is_mfa ? img->host.set_walk ? "set walk of the automaton's nodes (nfa_set_kernel)" : "table walk of the tabulated automaton (dfa_*_kernel)" : jit ? "kernel generated for this automaton (mfa_jit_kernel)" : "table-driven walk (walk_kernel)");
+        if (vb[0] == '1') fprintf(stderr, "mfa_hip: %s\n", !is_mfa ? img->host.set_wave ? "set walk of the automaton's nodes, one string per wave (nfa_set_wave_kernel)" : img->host.set_walk ? "set walk of the automaton's nodes (nfa_set_kernel)" : "table walk of the tabulated automaton (dfa_*_kernel)" : jit ? "kernel generated for this automaton (mfa_jit_kernel)" : "table-driven walk (walk_kernel)");
     LaunchCtx* cx = nullptr;
     rc = ctx_acquire(*ds, stream, &cx);
     if (rc != MFA_OK) return rc;
@@ -391,6 +391,7 @@ int mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const u
     if (!img || !d_offsets || !d_states) return MFA_ERR_INVALID_ARG;
     if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;      // a memory automaton's state holds spans of the input: nothing to hand over
     if (!img->host.set_walk) return MFA_ERR_UNSUPPORTED;                   // a tabulated image's state is one number: mfa_match_batch_resume
+    if (img->host.set_wave) return MFA_ERR_UNSUPPORTED;                    // a wave image's set may take 64 words, a record has eight: the records are left as they came
     if ((uintptr_t)d_states & 15u) return MFA_ERR_INVALID_ARG;             // the kernel reads and writes a record as 16-byte quarters
     if (n == 0) return MFA_OK;
     std::lock_guard<std::mutex> lk(img->mu);
@@ -410,7 +411,7 @@ int mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const u
 int mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, mfa_set_state* states, uint8_t* results,
                                     int device) {
     if (!img || !offsets || !states) return MFA_ERR_INVALID_ARG;
-    if (img->host.h.kind != MFA_KIND_NFA || !img->host.set_walk) return MFA_ERR_UNSUPPORTED;
+    if (img->host.h.kind != MFA_KIND_NFA || !img->host.set_walk || img->host.set_wave) return MFA_ERR_UNSUPPORTED;
     return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void* d_st) {
         return mfa_match_batch_resume_set(img, d_bytes, d_off, n, (mfa_set_state*)d_st, d_res, device, nullptr); }, states, sizeof(mfa_set_state), false);
 }

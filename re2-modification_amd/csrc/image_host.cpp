@@ -10,6 +10,7 @@
 
 #include "mfa_internal.h"
 #include "nfa_set_core.h"
+#include "nfa_set_wave_core.h"
 
 namespace mfa {
 
@@ -170,7 +171,10 @@ int nfa_eps_chain(const HostImage& img, uint32_t* chain, std::vector<uint8_t>* r
 
 // The tables of the set walk (nfa_set_core.h has the layout and the rule).  MFA_ERR_UNSUPPORTED: more nodes, classes, items or a
 // longer epsilon chain than the kernel holds, or a cycle of epsilon edges.
-int nfa_set_build(HostImage& img) {
+// wave: the tables of the wave-cooperative walk instead (nfa_set_wave_core.h): the same header and sections, a mask row of W =
+// ceil(n / 32) words for up to kWaveMaxNodes nodes, 11 bits of node number in an epsilon item, a stack of up to n slots (the chain is
+// never longer), items held to 2^kWavePosBits; no home set (nothing cuts a wave image's strings).
+static int set_tables_build(HostImage& img, bool wave) {
     const uint32_t n = img.h.n_nodes;
     std::vector<int> rep;
     int rc = nfa_byte_classes(img, rep);
@@ -179,8 +183,8 @@ int nfa_set_build(HostImage& img) {
     std::vector<uint8_t> reached;
     rc = nfa_eps_chain(img, &chain, &reached);
     if (rc != MFA_OK) return rc;
-    if (n > kSetMaxNodes || chain - 1u > kSetMaxDepth) return MFA_ERR_UNSUPPORTED;
-    const uint32_t W = n <= 32 ? 1u : n <= 64 ? 2u : n <= 128 ? 4u : 8u, C = img.n_classes;
+    if (wave ? n > kWaveMaxNodes || chain - 1u > n : n > kSetMaxNodes || chain - 1u > kSetMaxDepth) return MFA_ERR_UNSUPPORTED;
+    const uint32_t W = wave ? wave_words_of(n) : n <= 32 ? 1u : n <= 64 ? 2u : n <= 128 ? 4u : 8u, C = img.n_classes;
     std::vector<uint32_t> item_begin(n + 1, 0), items, masks;
     uint32_t runs = 0;
     for (uint32_t u = 0; u < n; u++) {
@@ -195,7 +199,7 @@ int nfa_set_build(HostImage& img) {
         }
     }
     item_begin[n] = (uint32_t)items.size();
-    if (items.size() >= (1u << kSetPosBits) || masks.size() >= (1u << 26)) return MFA_ERR_UNSUPPORTED;
+    if (items.size() >= (1u << (wave ? kWavePosBits : kSetPosBits)) || masks.size() >= (1u << 26)) return MFA_ERR_UNSUPPORTED;
     // accept: the nodes from which `finish` is reached over epsilon edges alone (finish itself among them)
     std::vector<uint32_t> accept(W, 0u);
     for (uint32_t u = 0; u < n; u++) {
@@ -223,10 +227,14 @@ int nfa_set_build(HostImage& img) {
     std::memcpy(out.data() + out[SET_H_BYTE_CLASS], img.byte_class, 256);
     out[SET_H_TOTAL] = (uint32_t)out.size();
     img.set_walk = true;
+    img.set_wave = wave;
     img.dfa_states = 0; img.dfa_trans.clear(); img.dfa_accept.clear();
-    nfa_set_home(img, img.set_home);
+    if (!wave) nfa_set_home(img, img.set_home);
     return MFA_OK;
 }
+
+int nfa_set_build(HostImage& img) { return set_tables_build(img, false); }
+int nfa_set_wave_build(HostImage& img) { return set_tables_build(img, true); }
 
 // The second seed of nfa_set_split.hip's guesses (nfa_set_split_core.h), for texts on which a walk from {start} dies in mid-text: what
 // spec_home_state (dfa_spec_core.h) is for a table, on node sets.  The set a deterministic pseudo-random walk from {start} ends in:
@@ -256,14 +264,24 @@ void nfa_set_home(const HostImage& img, uint32_t (&home)[8]) {
         if (cur[v]) home[v >> 5] |= 1u << (v & 31u);
 }
 
+// Which tables an image that is to be walked as a node set gets.  Those of the lane kernel (one string per lane) up to kSetMaxNodes nodes,
+// exactly as before the wave kernel existed -- a chain beyond that kernel's stack stays a refusal -- and those of the wave kernel (one
+// string per wave) for kSetMaxNodes + 1 to kWaveMaxNodes nodes.  MFA_SET_WAVE=1, read here, once per image: wave tables for every such
+// image, the narrow ones too (for measurements and tests; never the default).
+static int nfa_set_any_build(HostImage& img) {
+    const char* wv = getenv("MFA_SET_WAVE");
+    if ((wv && wv[0] == '1') || img.h.n_nodes > kSetMaxNodes) return nfa_set_wave_build(img);
+    return nfa_set_build(img);
+}
+
 // What mfa_image_create does with a memory-less automaton: tabulate it, and when the state sets pass the limit (MFA_DFA_STATE_LIMIT,
-// at most MFA_MAX_DFA_STATES) build the tables of the set walk instead.  MFA_NFA_SETWALK=1: the set walk without tabulating;
+// at most MFA_MAX_DFA_STATES) build the tables of the set walk instead (nfa_set_any_build).  MFA_NFA_SETWALK=1: the set walk without tabulating;
 // MFA_NFA_SETWALK=0: no set walk, the refusal of old.  Both are read here, once per image.
 int nfa_image_build(HostImage& img) {
     int rc = nfa_eps_chain(img, nullptr, nullptr);
     if (rc != MFA_OK) return rc;
     const char* sw = getenv("MFA_NFA_SETWALK");
-    if (sw && sw[0] == '1') return nfa_set_build(img);
+    if (sw && sw[0] == '1') return nfa_set_any_build(img);
     uint64_t limit = MFA_MAX_DFA_STATES;
     if (const char* e = getenv("MFA_DFA_STATE_LIMIT")) {
         const uint64_t v = strtoull(e, nullptr, 10);
@@ -271,7 +289,7 @@ int nfa_image_build(HostImage& img) {
     }
     rc = tabulate_nfa(img, (uint32_t)limit);
     if (rc != MFA_ERR_UNSUPPORTED || img.n_classes > 255 || (sw && sw[0] == '0')) return rc;
-    return nfa_set_build(img);
+    return nfa_set_any_build(img);
 }
 
 int tabulate_nfa(HostImage& img, uint32_t max_states, std::vector<std::string>* sets_out) {

@@ -296,6 +296,7 @@ static int launch_dfa_any(const HostImage& img, DeviceState& ds, LaunchCtx& cx, 
 
 int launch_dfa_walk(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
                     uint64_t n, uint8_t* d_results, void* stream) {
+    if (img.set_wave) return launch_nfa_set_wave(img, ds, cx, d_bytes, d_offsets, n, d_results, stream);   // no table, wave tables: one string per wave (nfa_set_wave.hip)
     if (img.set_walk) return launch_nfa_set(img, ds, cx, d_bytes, d_offsets, n, d_results, stream);      // no table: the set walk (nfa_set.hip)
     return launch_dfa_any(img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, (hipStream_t)stream);
 }

@@ -43,6 +43,7 @@ struct HostImage {
     // MFA_KIND_NFA whose tabulation passed the limit: the tables of the set walk (nfa_set_core.h); dfa_states is then 0
     bool                  set_walk = false;
     std::vector<uint32_t> set_tables;
+    bool                  set_wave = false;    //   ... in the form of the wave-cooperative walk (nfa_set_wave_core.h): one string per wave, up to 2048 nodes
     uint32_t              set_home[8] = {0};   //   ... and the second seed of nfa_set_split.hip's guesses, a node set (image_host.cpp: nfa_set_home)
     mutable int           jit_source_ok = -1;      // MFA kind: the generated kernel's source is of a size a compiler finishes (jit.hip; -1 = not looked at)
 };
@@ -51,6 +52,7 @@ int parse_blob(const void* blob, size_t n_bytes, HostImage& out);   // MFA_OK / 
 int check_mfa_invariants(const HostImage& img);                      // MFA_OK / MFA_ERR_UNSUPPORTED
 int tabulate_nfa(HostImage& img, uint32_t max_states = MFA_MAX_DFA_STATES, std::vector<std::string>* sets_out = nullptr);   // fills the dfa_* members; MFA_ERR_UNSUPPORTED beyond max_states state sets
 int nfa_set_build(HostImage& img);                                   // fills set_tables instead (MFA_ERR_UNSUPPORTED: outside the set walk's limits)
+int nfa_set_wave_build(HostImage& img);                              // ... in the wave form (sets set_wave beside set_walk; MFA_ERR_UNSUPPORTED beyond 2048 nodes)
 void nfa_set_home(const HostImage& img, uint32_t (&home)[8]);        // a set-walk image's home set (nfa_set_build fills set_home with it)
 int nfa_image_build(HostImage& img);                                 // MFA_KIND_NFA at image creation: one or the other
 
@@ -137,6 +139,9 @@ int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const u
 // words, 16-byte aligned); d_results may be NULL
 int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                           uint32_t* d_states, uint8_t* d_results, void* stream);
+// nfa_set_wave.hip: the same for an image with wave tables (HostImage::set_wave), one string per wave; nothing is cut, nothing resumes
+int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                        uint8_t* d_results, void* stream);
 // workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
 inline uint64_t lds_blocks_per_cu(size_t lds) {
     const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);

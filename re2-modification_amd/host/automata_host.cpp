@@ -189,8 +189,12 @@ void piece_of(uint64_t b, uint64_t e, uint64_t r, bool reversed, uint64_t* lo, u
 }
 
 // the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call.  set_walk: the
-// image walks node sets (dfa_states == 0), so a string's state between two pieces is a record of mfa_match_batch_resume_set_host, not one word
-void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
+// image walks node sets (dfa_states == 0), so a string's state between two pieces is a record of mfa_match_batch_resume_set_host, not one word.
+// That record holds 256 nodes: an image of more (n_nodes) is walked one string per wave and hands nothing from call to call.
+void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, uint32_t n_nodes, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
+    if (set_walk && n_nodes > 256u)
+        throw std::runtime_error("Automata::match: a string beyond the limit of one call, and the automaton is walked as a set of " + std::to_string(n_nodes) +
+                                 " nodes -- more than 256 nodes: strings in pieces are not available");
     uint64_t rounds = 1;
     for (uint64_t k : which) rounds = std::max(rounds, (offsets[k + 1] - offsets[k] + kPieceBytes - 1) / kPieceBytes);
     vector<uint32_t> states(set_walk ? 0 : which.size(), MFA_DFA_STATE_START);
@@ -210,6 +214,8 @@ void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, const uint8_t
         uint8_t* out = r + 1 == rounds ? res.data() : nullptr;
         const int rc = set_walk ? mfa_match_batch_resume_set_host(img, stage.data(), off.data(), which.size(), sets.data(), out, device)
                                 : mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), out, device);
+        if (set_walk && rc == MFA_ERR_UNSUPPORTED)      // (MFA_SET_WAVE=1 gives a narrow image the wave form too)
+            throw std::runtime_error("Automata::match: a string beyond the limit of one call, and the automaton is walked one string per wave: strings in pieces are not available");
         if (rc != MFA_OK) fail(set_walk ? "mfa_match_batch_resume_set_host" : "mfa_match_batch_resume_host", rc);
     }
     for (size_t j = 0; j < which.size(); j++) results[which[j]] = res[j];
@@ -234,7 +240,7 @@ void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint6
                 if (to > from) match_packed_short(img, bytes, offsets + from, to - from, results + from);
                 from = to + 1;
             }
-            match_in_pieces(img, info.is_reversed != 0, info.dfa_states == 0, bytes, offsets, longs, results, device);
+            match_in_pieces(img, info.is_reversed != 0, info.dfa_states == 0, info.n_nodes, bytes, offsets, longs, results, device);
             return;
         }
     }

@@ -1,0 +1,214 @@
+"""What tests/test_nfa_set_wave_cpu.py and tests/test_nfa_set_wave_gpu.py share: the host harness tests/emul/nfa_set_wave_emul.cpp built
+once per session, its input files and its output, and the wide images and strings both walk -- TEST INFRASTRUCTURE ONLY: no tests, no
+fixtures, no marks in here."""
+import atexit
+import os
+import random
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+import nfa_fuzz
+import oracle_lib
+from mfa_amd import image
+from testlib import DIPLOMA, EMUL_DIR, LENGTHS, front_end_blob, k_regex, out_offsets, wide_strings, write_batch
+
+CSRC = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "csrc")
+LANE_MAX_NODES, WAVE_MAX_NODES = 256, 2048
+COUNTER300 = "(" + "a" * 300 + ")*"                # 303 nodes: the counter tests/setsplit_lib.py had to shrink
+EDGE_LENGTHS = [1023, 1024, 1025, 2049]            # the edges of a fetch round (64 blocks of 16 bytes), and two rounds and a byte
+RAW_NODES = (257, 288, 512, 513, 1024, 1025, 2047, 2048)
+# seeds for which the ORACLE answers both ways on the sampled strings (a scan of seeds 0 to 7 on the CPU restatement alone; odd seeds scan
+# from the end); six labels keep the live sets tens of nodes wide
+RAW_SEEDS = {257: (0, 1, 3), 288: (2, 3, 7), 512: (0, 1, 3), 513: (0, 1, 3), 1024: (2, 4, 5), 1025: (0, 1, 5), 2047: (0, 1, 3), 2048: (2, 3, 6)}
+RAW_LABELS = 6
+
+_built = {}
+
+
+def wave_emul_exe(flags=""):
+    """tests/emul/nfa_set_wave_emul.cpp, built with the g++ line tests/emul/build.sh has for its nfa_set row (that script has no row for
+    this name; -O2: the harness does 64 lanes' work per step) and `flags` behind the caller's EMUL_FLAGS, once per session, in a
+    temporary directory of its own; the compiler is heard only when it fails"""
+    if flags not in _built:
+        folder = tempfile.mkdtemp(prefix="nfa_set_wave_emul_")
+        atexit.register(shutil.rmtree, folder, ignore_errors=True)
+        exe = os.path.join(folder, "nfa_set_wave_emul")
+        cmd = (["g++", "-O2", "-g", "-std=c++17"] + (os.environ.get("EMUL_FLAGS", "") + " " + flags).split()
+               + ["-Wall", "-Ishim", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-unused-variable", "-I" + CSRC,
+                  "-I" + os.path.join(oracle_lib.ROOT, "include"), "-o", exe, "nfa_set_wave_emul.cpp", os.path.join(CSRC, "image_host.cpp")])
+        p = subprocess.run(cmd, cwd=EMUL_DIR, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert p.returncode == 0, "building nfa_set_wave_emul failed:\n%s" % p.stdout
+        _built[flags] = exe
+    return _built[flags]
+
+
+def run_step(exe, tmp_path, blob):
+    """the harness's `step` mode: (states, classes, W, depth) of its "ok" line"""
+    (tmp_path / "a.blob").write_bytes(blob)
+    p = subprocess.run([exe, "step", str(tmp_path / "a.blob")], capture_output=True)
+    assert p.returncode == 0, p.stderr.decode()[-600:]
+    f = p.stdout.split()
+    assert f[0] == b"ok"
+    return tuple(int(x) for x in f[1:])
+
+
+def run_match(exe, tmp_path, blob, strings):
+    """the harness's `match` mode: one result byte per string"""
+    (tmp_path / "a.blob").write_bytes(blob)
+    write_batch(tmp_path / "batch.bin", strings)
+    p = subprocess.run([exe, "match", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin")], capture_output=True)
+    assert p.returncode == 0, p.stderr.decode()[-600:]
+    return np.frombuffer(p.stdout.strip(), dtype=np.uint8) - ord("0")
+
+
+def words_of(n_nodes):
+    return (n_nodes + 31) // 32
+
+
+# ---- images -----------------------------------------------------------------------------------------------------------------------------
+def eps_chain(d):
+    """the most nodes on one path of epsilon edges of a parsed dump (what image_host.cpp: nfa_eps_chain counts)"""
+    nodes, memo = d["nodes"], {}
+    old = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(old, 4 * len(nodes) + 100))
+
+    def go(u):
+        if u not in memo:
+            memo[u] = 1 + max([go(to) for lab, to, _ in nodes[u]["edges"] if lab is None] or [0])
+        return memo[u]
+
+    try:
+        return max(go(u) for u in range(len(nodes)))
+    finally:
+        sys.setrecursionlimit(old)
+
+
+def k_for(lo, hi, tmp_path):
+    """the smallest k whose Thompson compile of k_regex(k) has more than lo nodes; asserted to have at most hi.  (5 k + 9 nodes today:
+    found by asking the front-end, not by that slope)"""
+    nodes = lambda k: image.blob_info(front_end_blob(k_regex(k), tmp_path))["n_nodes"]
+    k = max(1, lo // 5 - 3)
+    while nodes(k) <= lo:
+        k += 1
+    assert lo < nodes(k) <= hi
+    return k
+
+
+def deep_wide_dump(tmp_path):
+    """nested alternations in the style of testlib.wide_images()["deep"], more of them: the parsed dump, made to scan from the end"""
+    deep = "a"
+    for _ in range(14):
+        deep = "((" + deep + "|b)|c)"
+    p = subprocess.run([DIPLOMA, "-dump", "-thompson"], input="(" + deep + ")*" + deep + deep + "\n", capture_output=True, text=True, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr
+    d = image.parse_dump(p.stdout)
+    d["reversed"] = 1
+    return d
+
+
+def wide_regex_images(tmp_path):
+    """name -> (blob, alphabet, min_len): k_regex Thompson images in (256, 512], (512, 1024] and (1024, 2048] nodes, the first also
+    scanning from the end, and the deep one (more than 256 nodes AND an epsilon chain beyond the lane kernel's 49 nodes).  alphabet and
+    min_len are for regex_strings: (a|b)*a(a|b)^k accepts nothing with a `c` and nothing shorter than k + 1 bytes"""
+    out = {}
+    for name, lo, hi in (("k_512", 256, 512), ("k_1024", 512, 1024), ("k_2048", 1024, 2048)):
+        k = k_for(lo, hi, tmp_path)
+        out[name] = (front_end_blob(k_regex(k), tmp_path), b"ab", k + 1)
+        if lo == 256:
+            out[name + "_rev"] = (front_end_blob(k_regex(k), tmp_path, 1), b"ab", k + 1)
+    d = deep_wide_dump(tmp_path)
+    assert len(d["nodes"]) > LANE_MAX_NODES and eps_chain(d) > 49
+    out["deep"] = (image.to_blob(d), b"abc", 0)
+    return out
+
+
+def raw_image(n_nodes, seed):
+    """a raw random image (nfa_fuzz.random_image: forward epsilon edges only, so no cycle; `finish` drawn anywhere), scanning from the end
+    for odd seeds: (dict, blob)"""
+    rng = random.Random(1000003 * n_nodes + seed)
+    d = nfa_fuzz.random_image(rng, n_nodes, RAW_LABELS, rev=seed & 1)
+    return d, image.to_blob(d)
+
+
+# ---- strings ----------------------------------------------------------------------------------------------------------------------------
+def pack_every_offset(strings, filler):
+    """the strings with fillers (filler(k) -> a short string) put between them until, packed back to back, they start at every offset
+    mod 16"""
+    out = list(strings)
+    k = 0
+    while len({o % 16 for o in out_offsets(out)}) < 16:
+        out.append(filler(k))
+        k += 1
+        assert k < 400
+    return out
+
+
+def regex_strings(rng, alphabet=b"abc", min_len=0):
+    """testlib.wide_strings (its `c` made a `b` for an alphabet without one) plus LENGTHS plus EDGE_LENGTHS over the alphabet, plus, for
+    an image that accepts nothing below min_len bytes, 60 strings of up to 300 bytes more than that; a start at every offset mod 16"""
+    pick = lambda ln: bytes(rng.choice(list(alphabet), size=int(ln)).tolist())
+    strings = wide_strings(rng)
+    if b"c" not in alphabet:
+        strings = [s.replace(b"c", b"b") for s in strings]
+    strings += [pick(ln) for ln in LENGTHS + EDGE_LENGTHS]
+    if min_len:
+        strings += [pick(min_len + int(x)) for x in rng.integers(0, 300, size=60)]
+    strings = pack_every_offset(strings, lambda k: pick(1 + k % 7))
+    assert {o % 16 for o in out_offsets(strings)} == set(range(16)) and set(LENGTHS + EDGE_LENGTHS) <= {len(s) for s in strings}
+    return strings
+
+
+def raw_strings(d, seed):
+    """strings for a raw image, drawn from the automaton (nfa_fuzz's sampler: random text never accepts there): the sampler's own batch,
+    and one string of every length of LENGTHS and EDGE_LENGTHS where the automaton has a loop to pump; None when nothing pumps.  In the
+    order the image reads them (mirrored for a reversed scan); a start at every offset mod 16."""
+    rng = random.Random(77 * seed + len(d["nodes"]))
+    E, start, finish = nfa_fuzz.edges_by_rank(d)
+    got = nfa_fuzz.sample_strings(E, start, finish, rng, 0)
+    if got is None:
+        return None
+    strings = list(got[0])
+    sm = nfa_fuzz.Sampler(E, start, finish, rng)
+    for ln in LENGTHS + EDGE_LENGTHS:
+        s, cur = [], frozenset([sm.w.start])        # exactly ln bytes that keep the set alive (the sampler's own strings stop at LONG_MAX)
+        while len(s) < ln:
+            nb = sm.next_byte(cur)
+            if nb is None:
+                return None
+            s.append(nb[0])
+            cur = nb[1]
+        strings.append(bytes(s))
+    strings = pack_every_offset(strings, lambda k: strings[k % 16][:1 + k % 7])
+    assert {o % 16 for o in out_offsets(strings)} == set(range(16)) and set(LENGTHS + EDGE_LENGTHS) <= {len(s) for s in strings}
+    return [s[::-1] for s in strings] if d["reversed"] else strings
+
+
+def raw_corpus(node_counts=RAW_NODES, per=3):
+    """[(name, blob, strings, want)] over the node counts and the first `per` of their RAW_SEEDS, and the number dropped: an image is
+    dropped when nothing pumps or when the ORACLE does not answer both ways on its strings -- a filter on the reference alone"""
+    out, dropped = [], 0
+    for n_nodes in node_counts:
+        for seed in RAW_SEEDS[n_nodes][:per]:
+            d, blob = raw_image(n_nodes, seed)
+            strings = raw_strings(d, seed)
+            want = None if strings is None else np.asarray(oracle_lib.OracleImage(blob).match(strings)).copy()
+            if want is None or not 0 < int(want.sum()) < len(strings):
+                dropped += 1
+                continue
+            want.setflags(write=False)
+            out.append(("raw_%d_seed%d" % (n_nodes, seed), blob, strings, want))
+    return out, dropped
+
+
+_raw = {}
+
+
+def raw_corpus_once(node_counts=RAW_NODES, per=3):
+    """raw_corpus, made once per session and left unchanged"""
+    if (node_counts, per) not in _raw:
+        _raw[(node_counts, per)] = raw_corpus(node_counts, per)
+    return _raw[(node_counts, per)]

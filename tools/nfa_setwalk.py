@@ -21,6 +21,16 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
       gain    8 x 1 MiB with the library's defaults against MFA_SET_SPLIT=0 (the whole walk: one uncounted call and three counted ones, it
               takes seconds per call)
       short   1 Mi x 1 KiB (no long string): this build's kernel time per call, to be set against another build's (MFA_LIB_PATH) process by process
+
+  nfa_setwalk.py wave narrow|wide [REPS] [STRINGS] [OUT.jsonl] [first]   the wave-cooperative step (csrc/nfa_set_wave.hip: one string per wave), lines appended
+      to OUT.jsonl (default profiles/r14_nfa_set_wave.jsonl).  Medians of REPS calls (default 7) after five uncounted ones, the sides
+      alternating; the first strings' answers are held to the CPU restatement.
+      narrow  the lane kernel against MFA_SET_WAVE=1 on the same build, on (a|b)*abb forced to the set walk (W = 1) and on the k = 20
+              Thompson image (W = 4): STRINGS x 1 KiB (default 1 Mi), 8 192 x 1 KiB, and 8 x 1 MiB with MFA_SET_SPLIT=0 (walked whole:
+              one uncounted call and three counted ones)
+      wide    images the lane kernel cannot hold: (a|b)*a(a|b)^k Thompson with 257 to 512 and with 1025 to 2048 nodes, STRINGS x 1 KiB;
+              bytes per second and per resident wave, and the CPU restatement's time on the first 1024 strings beside it, for scale;
+              `first`: the narrower image only (a call on the wider one takes a minute at 1 Mi strings)
 """
 import json
 import os
@@ -203,9 +213,91 @@ def long_main():
                                      {"MFA_DFA_CHUNK": chunk, "MFA_SET_SPLIT_LOOKBACK": lookback, "MFA_SET_SPLIT_ROUNDS": rounds}, out_path)
 
 
+def created_wave(blob, setwalk=None):
+    """created() with MFA_SET_WAVE=1 while the image is made: wave tables, whatever its width"""
+    os.environ["MFA_SET_WAVE"] = "1"
+    try:
+        return created(blob, setwalk)[0]
+    finally:
+        del os.environ["MFA_SET_WAVE"]
+
+
+def wave_sides(what, sides, blob, flat, d_off, reps, warm, env, out_path, extra=None):
+    """sides: name -> image of `blob`; every round runs every side once under the knobs of `env`; one JSON line"""
+    for k, v in env.items():
+        os.environ[k] = str(v)
+    n = d_off.numel() - 1
+    total = int(d_off[-1])
+    res = {k: torch.full((n,), 7, dtype=torch.uint8, device=DEV) for k in sides}
+    ms = {k: [] for k in sides}
+    for r in range(warm + reps):
+        for k, img in sides.items():
+            img.match_tensors(flat, d_off, res[k])
+            t = img.last_kernel_ms(0)
+            print("  %s, call %d, %s: %.3f ms" % (what, r, k, t), file=sys.stderr, flush=True)      # (a call may take a minute: a sign of life)
+            if r >= warm:
+                ms[k].append(t)
+    for k in env:
+        del os.environ[k]
+    m = min(n, 2 if int(d_off[1]) > SAMPLE else SAMPLE)
+    off = d_off[:m + 1].cpu().numpy().astype(np.uint64)
+    t = time.perf_counter()
+    want = oracle_lib.OracleImage(blob).match_packed(flat[:int(off[-1])].cpu().numpy(), off).astype(np.uint8)[:m]
+    cpu_s = time.perf_counter() - t
+    first = next(iter(res.values()))
+    out = {"what": what, "device": torch.cuda.get_device_name(0), "strings": n, "bytes": total, "knobs": env,
+           "sides_equal_on_all_strings": all(bool(torch.equal(first, v)) for v in res.values()),
+           "cpu_restatement": {"strings": m, "bytes": int(off[-1]), "seconds": cpu_s, "MB/s": int(off[-1]) / cpu_s / 1e6}}
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for k, v in ms.items():
+        med = float(np.median(v))
+        out[k] = {"kernel_ms": v, "median_ms": med, "spread_ms": float(max(v) - min(v)), "MB/s": total / (med * 1e-3) / 1e6,
+                  "results_exact_on_sample": bool(np.array_equal(res[k][:m].cpu().numpy(), want)), "sample": m, "accepted_in_sample": int(want.sum()),
+                  "kernel": KERNELS[sides[k].info()["last_kernel"]], "n_nodes": sides[k].info()["n_nodes"]}
+        if k.startswith("wave"):                               # one string per wave: the rate of one of the waves that run at once (at most 32 per CU)
+            out[k]["kB/s per wave"] = total / (med * 1e-3) / 1e3 / min(n, cus * 32)
+    if len(ms) == 2:
+        a, b = list(ms)
+        out["%s over %s" % (b, a)] = out[b]["median_ms"] / out[a]["median_ms"]
+    out.update(extra or {})
+    line = json.dumps(out)
+    print(line, flush=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
+def wave_main():
+    mode = sys.argv[2] if len(sys.argv) > 2 else "narrow"
+    reps = max(3, int(sys.argv[3])) if len(sys.argv) > 3 else 7
+    n = int(sys.argv[4]) if len(sys.argv) > 4 else 1 << 20
+    out_path = sys.argv[5] if len(sys.argv) > 5 else os.path.join(ROOT, "profiles", "r14_nfa_set_wave.jsonl")
+    assert mode in ("narrow", "wide")
+    kib = batch([1024] * n, 2)
+    if mode == "wide":
+        for lo, hi in ((256, 512), (1024, 2048))[:1 if "first" in sys.argv[6:] else 2]:
+            k = (lo - 9) // 5 + 1                                # the Thompson compile has 5 k + 9 nodes
+            blob = front_end("(a|b)*a" + "(a|b)" * k, "-thompson")
+            img, _ = created(blob, "1")
+            assert lo < img.info()["n_nodes"] <= hi and img.info()["dfa_states"] == 0
+            wave_sides("%d x 1 KiB, (a|b)*a(a|b)^%d Thompson, %d nodes" % (n, k, img.info()["n_nodes"]), {"wave kernel": img}, blob, kib[0], kib[1], reps, 5, {}, out_path)
+        return
+    abb = image.blob_from_dump(oracle_lib.load_dump("nfa_abb_thompson"))
+    b20 = front_end("(a|b)*a" + "(a|b)" * 20, "-thompson")
+    small = batch([1024] * 8192, 3)
+    mib = batch([1 << 20] * 8, 5)
+    for name, blob in (("(a|b)*abb forced to the set walk (W = 1)", abb), ("(a|b)*a(a|b)^20 Thompson (W = 4)", b20)):
+        sides = {"lane kernel": created(blob, "1")[0], "wave kernel (MFA_SET_WAVE=1)": created_wave(blob, "1")}
+        assert all(img.info()["dfa_states"] == 0 for img in sides.values())
+        wave_sides("%d x 1 KiB, %s" % (n, name), sides, blob, kib[0], kib[1], reps, 5, {}, out_path)
+        wave_sides("8 192 x 1 KiB, " + name, sides, blob, small[0], small[1], reps, 5, {}, out_path)
+        wave_sides("8 x 1 MiB, walked whole, " + name, sides, blob, mib[0], mib[1], 3, 1, {"MFA_SET_SPLIT": 0}, out_path)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "long":
         return long_main()
+    if len(sys.argv) > 1 and sys.argv[1] == "wave":
+        return wave_main()
     reps = max(5, int(sys.argv[1]) if len(sys.argv) > 1 else 7)
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 1 << 20
     which = sys.argv[3] if len(sys.argv) > 3 else "all"

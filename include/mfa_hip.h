@@ -85,12 +85,14 @@ typedef struct mfa_image_info {
  * a string (nfa_set_kernel); an image of 257 to 2048 nodes is a WAVE image: one string per wave, the set across its 64 lanes
  * (nfa_set_wave_kernel; last_kernel is MFA_KERNEL_NODESET all the same), epsilon chains of any length.  mfa_match_batch, _host, _regions
  * and a mixed object walk every string of a wave image whole, whatever its length up to MFA_MAX_STRING_BYTES: nothing below about long
- * strings or strings in pieces applies to it -- no string is cut (one long string holds one wave for its whole length),
- * mfa_last_set_split answers zeros, and mfa_match_batch_resume_set refuses it.  MFA_SET_WAVE=1, read here too, makes EVERY set-walk
+ * strings applies to it -- no string is cut (one long string holds one wave for its whole length) and mfa_last_set_split answers
+ * zeros -- and its strings in pieces have a record and a call of their own: mfa_match_batch_resume_set refuses it,
+ * mfa_match_batch_resume_set_wide (further down) takes it.  MFA_SET_WAVE=1, read here too, makes EVERY set-walk
  * image a wave image, the narrow ones as well: a knob for measurements and tests, never the default (the lane kernel is many times
  * faster where it applies).  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
  * mfa_match_batch_resume and _resume_host answer MFA_ERR_UNSUPPORTED before the device is touched, and mfa_match_batch_resume_set (below)
- * is the call that carries such a set from piece to piece.  Long strings: a string of MFA_DFA_SPLIT_MIN bytes or more (default 65536) is
+ * is the call that carries such a set from piece to piece (for a wave image: mfa_match_batch_resume_set_wide;
+ * mfa_image_resume_state_bytes tells which).  Long strings: a string of MFA_DFA_SPLIT_MIN bytes or more (default 65536) is
  * cut into chunks inside the same call, as for a table in L2 (mfa_match_batch below has the scheme): every chunk is walked from ONE node
  * set by a lane of its own -- the first chunk from the true set, the others from a guess, the set reached over the MFA_SET_SPLIT_LOOKBACK
  * bytes (default 64) in front of the chunk from {start} or, if that walk dies, from a "home" set chosen per image -- then
@@ -243,6 +245,38 @@ int  mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const 
  * a piece beyond the limit is the sticky error above, not MFA_ERR_TOO_LONG */
 int  mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
                                      mfa_set_state* states, uint8_t* results, int device);
+
+/* ---- strings in pieces (wave images) ----------------------------------------------------------------
+ * A wave image (a set-walk image of more than 256 nodes, or one made under MFA_SET_WAVE=1) holds its set across the 64 lanes of a wave:
+ * up to 64 words.  Its record is mfa_set_state_wide, 272 bytes per string -- the tag quarter of mfa_set_state and nodes[64] -- and its
+ * call is mfa_match_batch_resume_set_wide.  The contract is that of mfa_match_batch_resume_set above with nodes[64] in place of
+ * nodes[8]: pointers, batch layout, the 16-byte read rule, asynchrony and scan order; d_states is n records of device memory, 16-byte
+ * aligned, read and written in place; the tags are MFA_SET_STATE_START (`nodes` is ignored: a zero-filled buffer is "every string at
+ * its start"), MFA_SET_STATE_LIVE (node v is bit v & 31 of nodes[v >> 5]; the empty set is dead) and MFA_SET_STATE_INVALID.  On return
+ * the tag is LIVE or INVALID, `reserved` is zero and every word of `nodes` at and beyond the image's W = ceil(n_nodes / 32) is zero.
+ * d_results may be NULL; otherwise results[k] is what the plain call would answer for the concatenation of the pieces given so far.
+ * Equivalence, "do not store them" and the sticky errors are as above: a tag other than START or LIVE, a `reserved` word that is not
+ * zero, a bit for a node the image lacks (any word at or beyond W included), a piece longer than MFA_MAX_STRING_BYTES or a stack
+ * overflow leaves tag MFA_SET_STATE_INVALID, `nodes` zero and result 2, and so does every later call on that record.  The SUM of a
+ * string's pieces has no limit.  A record that enters LIVE with the empty set leaves as it came with result 0 and its bytes are not read.
+ * Nothing is cut: a piece is walked whole by one wave whatever its length (nfa_set_wave_resume_kernel), and mfa_last_set_split answers
+ * zeros.  last_kernel becomes MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launch.  Re-entrant per (image, device, stream), and
+ * legal inside a stream capture once a first call has run (it allocates the workspace and raises the kernel's LDS limit).
+ * MFA_ERR_INVALID_ARG: img, d_offsets or d_states is NULL, or d_states is not 16-byte aligned.  MFA_ERR_UNSUPPORTED, with the records
+ * as they came: a memory automaton, a tabulated image, or a lane image (a set-walk image of up to 256 nodes made without
+ * MFA_SET_WAVE=1: its call is the 48-byte one).  All are answered before the device is touched; n == 0 is MFA_OK. */
+typedef struct mfa_set_state_wide { uint32_t tag; uint32_t reserved[3]; uint32_t nodes[64]; } mfa_set_state_wide;   /* 272 bytes: 17 quarters of 16 */
+int  mfa_match_batch_resume_set_wide(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                                     mfa_set_state_wide* d_states, uint8_t* d_results, int device, void* stream);
+/* the same with HOST pointers (copy in, match, copy records and results out, synchronise; `states` needs no alignment beyond its type's);
+ * a piece beyond the limit is the sticky error above, not MFA_ERR_TOO_LONG */
+int  mfa_match_batch_resume_set_wide_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                                          mfa_set_state_wide* states, uint8_t* results, int device);
+
+/* Which resume call an image takes, as the bytes of one string's state: 0 for a memory automaton (nothing is carried), 4 for a
+ * tabulated image (mfa_match_batch_resume), 48 for a lane set-walk image (mfa_match_batch_resume_set), 272 for a wave image
+ * (mfa_match_batch_resume_set_wide).  Touches no device.  MFA_ERR_INVALID_ARG: img or bytes is NULL. */
+int  mfa_image_resume_state_bytes(mfa_image_t* img, uint32_t* bytes);
 
 /* ---- region tables -------------------------------------------------------------------------------
  * Before a memory automaton walks a batch, one streaming pass over the batch (region_scan_kernel)

@@ -416,6 +416,54 @@ int mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, cons
         return mfa_match_batch_resume_set(img, d_bytes, d_off, n, (mfa_set_state*)d_st, d_res, device, nullptr); }, states, sizeof(mfa_set_state), false);
 }
 
+static_assert(sizeof(mfa_set_state_wide) == 272 && offsetof(mfa_set_state_wide, nodes) == 16, "a wide record is seventeen 16-byte quarters: tag and reserved, then nodes[64], lane l's word at nodes[l]");
+
+// which of the memory-less images the wide call takes: MFA_OK for a wave image, else the refusal
+static int wide_takes(const mfa_image_t* img) {
+    if (img->host.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;      // a memory automaton's state holds spans of the input: nothing to hand over
+    if (!img->host.set_walk) return MFA_ERR_UNSUPPORTED;                   // a tabulated image's state is one number: mfa_match_batch_resume
+    if (!img->host.set_wave) return MFA_ERR_UNSUPPORTED;                   // a lane image's set takes eight words: mfa_match_batch_resume_set
+    return MFA_OK;
+}
+
+int mfa_match_batch_resume_set_wide(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, mfa_set_state_wide* d_states,
+                                    uint8_t* d_results, int device, void* stream) {
+    if (!img || !d_offsets || !d_states) return MFA_ERR_INVALID_ARG;
+    int rc = wide_takes(img);
+    if (rc != MFA_OK) return rc;
+    if ((uintptr_t)d_states & 15u) return MFA_ERR_INVALID_ARG;             // the kernel reads and writes a record's tag as one 16-byte quarter
+    if (n == 0) return MFA_OK;
+    std::lock_guard<std::mutex> lk(img->mu);
+    DeviceState* ds = nullptr;
+    rc = device_prepare(img, device, &ds);
+    if (rc != MFA_OK) return rc;
+    if (const char* vb = getenv("MFA_VERBOSE"))      // (as mfa_match_batch: which kernel walks, on stderr)
+        if (vb[0] == '1') fprintf(stderr, "mfa_hip: set walk of the automaton's nodes on strings in pieces, one string per wave (nfa_set_wave_resume_kernel)\n");
+    LaunchCtx* cx = nullptr;
+    rc = ctx_acquire(*ds, stream, &cx);
+    if (rc != MFA_OK) return rc;
+    DoneGuard done_guard{cx, stream};
+    img->last_kernel = MFA_KERNEL_NODESET;
+    return launch_nfa_set_wave_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
+}
+
+// host pointers: as mfa_match_batch_resume_set_host, with records of sizeof(mfa_set_state_wide)
+int mfa_match_batch_resume_set_wide_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, mfa_set_state_wide* states, uint8_t* results,
+                                         int device) {
+    if (!img || !offsets || !states) return MFA_ERR_INVALID_ARG;
+    const int rc = wide_takes(img);
+    if (rc != MFA_OK) return rc;
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void* d_st) {
+        return mfa_match_batch_resume_set_wide(img, d_bytes, d_off, n, (mfa_set_state_wide*)d_st, d_res, device, nullptr); }, states, sizeof(mfa_set_state_wide), false);
+}
+
+int mfa_image_resume_state_bytes(mfa_image_t* img, uint32_t* bytes) {
+    if (!img || !bytes) return MFA_ERR_INVALID_ARG;
+    const HostImage& h = img->host;
+    *bytes = h.h.kind != MFA_KIND_NFA ? 0u : !h.set_walk ? (uint32_t)sizeof(uint32_t) : h.set_wave ? (uint32_t)sizeof(mfa_set_state_wide) : (uint32_t)sizeof(mfa_set_state);
+    return MFA_OK;
+}
+
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {
     if (!img || !ms) return MFA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(img->mu);

@@ -139,9 +139,13 @@ int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const u
 // words, 16-byte aligned); d_results may be NULL
 int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                           uint32_t* d_states, uint8_t* d_results, void* stream);
-// nfa_set_wave.hip: the same for an image with wave tables (HostImage::set_wave), one string per wave; nothing is cut, nothing resumes
+// nfa_set_wave.hip: the same for an image with wave tables (HostImage::set_wave), one string per wave; nothing is cut
 int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_results, void* stream);
+// the same walk with every string's set read from and written to its record of d_states (mfa_match_batch_resume_set_wide: n records of
+// 68 words, 16-byte aligned); d_results may be NULL
+int launch_nfa_set_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                               uint32_t* d_states, uint8_t* d_results, void* stream);
 // workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
 inline uint64_t lds_blocks_per_cu(size_t lds) {
     const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);

@@ -6,8 +6,10 @@
 //   count: 32 KiB at the most), and behind them the automaton's tables when both fit 64 KiB; else the tables are read through L2.
 //   Input: up to 64 aligned 16-byte blocks per wave and round, lane l block l; only blocks that hold a byte of the string.
 //   Grid: persistent, capped by what the CUs keep resident (lds_blocks_per_cu), strings dealt out by wave number.
-// Nothing is cut and nothing resumes: one long string holds one wave for its whole length, mfa_match_batch_resume_set refuses the image
-// (capi.hip).  The lane kernel (nfa_set.hip) stays the default for every image it can walk.
+// Strings in pieces (mfa_match_batch_resume_set_wide): nfa_set_wave_resume_kernel, the same grid and LDS, a record of 68 words per
+// string (mfa_set_state_wide) read before the piece and written behind it.  Nothing is cut: one long string, or one long piece, holds
+// one wave for its whole length, and mfa_match_batch_resume_set (the 48-byte record) keeps refusing the image (capi.hip).  The lane
+// kernel (nfa_set.hip) stays the default for every image it can walk.
 #include <hip/hip_runtime.h>
 
 #include "nfa_set.h"
@@ -41,6 +43,33 @@ nfa_set_wave_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, u
     }
 }
 
+// The same walk for strings in pieces: the wave's set comes from its string's record of `states` (kWaveStateWords words, 16-byte
+// aligned: a tag quarter, then lane l's word) and goes back there behind the piece (nfa_set_wave_core.h: nfa_wave_resume_piece).  A
+// record is read and written by the one wave that has its string.  results may be NULL.
+template <bool REV, bool IN_LDS>
+__global__ void __launch_bounds__(256)
+nfa_set_wave_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t depth, const uint8_t* __restrict__ bytes,
+                           const uint64_t* __restrict__ offsets, uint64_t n, uint32_t* states, uint8_t* results) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t wave = WaveDev::uni(threadIdx.x >> 6);
+    uint32_t* stack = lds + wave * depth;
+    const uint32_t* base = tables;
+    if (IN_LDS) {
+        uint32_t* copy = lds + 4u * depth;
+        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
+        __syncthreads();
+        base = copy;
+    }
+    const NfaSetView t = nfa_set_view(tables, base);
+    const uint32_t W = tables[SET_H_WORDS], n_nodes = tables[SET_H_NODES];
+    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t sid = (uint64_t)blockIdx.x * 4u + wave; sid < n; sid += n_waves) {
+        const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        const uint8_t r = nfa_wave_resume_piece<REV, WaveDev>(t, n_nodes, W, stack, bytes, b, e, states + sid * kWaveStateWords);
+        if (results && WaveDev::lane() == 0u) results[sid] = r;
+    }
+}
+
 // what a block takes of LDS: the four stacks and, when both fit kSetLdsMax, the tables behind them
 struct WaveLds { uint32_t words, depth, in_lds; size_t bytes; };
 
@@ -70,16 +99,48 @@ static int launch_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, con
     return MFA_OK;
 }
 
+// what both launches ask of the image before anything is enqueued: wave tables on the device, of a width and depth the kernels hold
+static bool wave_tables_ok(const HostImage& img, const DeviceState& ds) {
+    if (!img.set_wave || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return false;
+    const uint32_t W = img.set_tables[SET_H_WORDS];
+    return W >= 1u && W <= kWaveLanes && W == wave_words_of(img.set_tables[SET_H_NODES]) && img.set_tables[SET_H_DEPTH] <= kWaveMaxNodes;
+}
+
 int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_results, void* stream) {
-    if (!img.set_wave || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
-    const uint32_t W = img.set_tables[SET_H_WORDS];
-    if (W < 1u || W > kWaveLanes || W != wave_words_of(img.set_tables[SET_H_NODES]) || img.set_tables[SET_H_DEPTH] > kWaveMaxNodes) return MFA_ERR_UNSUPPORTED;
+    if (!wave_tables_ok(img, ds)) return MFA_ERR_UNSUPPORTED;
     const WaveLds l = wave_lds_of(img);
     hipStream_t s = (hipStream_t)stream;
     if (img.h.is_reversed)
         return l.in_lds ? launch_wave<true, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s) : launch_wave<true, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s);
     return l.in_lds ? launch_wave<false, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s) : launch_wave<false, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s);
+}
+
+template <bool REV, bool IN_LDS>
+static int launch_wave_resume(DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
+                              uint8_t* d_results, hipStream_t s) {
+    uint64_t blocks = (n + 3) / 4, cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    const int rc = set_allow_lds<nfa_set_wave_resume_kernel<REV, IN_LDS>>(ds.device);
+    if (rc != MFA_OK) return rc;
+    // nothing is queued or cut: the split flags stay as ctx_acquire left them, mfa_last_set_split answers zeros
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
+    hipLaunchKernelGGL((nfa_set_wave_resume_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.depth,
+                       d_bytes, d_offsets, n, d_states, d_results);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
+    return MFA_OK;
+}
+
+int launch_nfa_set_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                               uint32_t* d_states, uint8_t* d_results, void* stream) {
+    if (!wave_tables_ok(img, ds)) return MFA_ERR_UNSUPPORTED;
+    const WaveLds l = wave_lds_of(img);
+    hipStream_t s = (hipStream_t)stream;
+    if (img.h.is_reversed)
+        return l.in_lds ? launch_wave_resume<true, true>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<true, false>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
+    return l.in_lds ? launch_wave_resume<false, true>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<false, false>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
 }
 
 }  // namespace mfa

@@ -20,9 +20,15 @@
 // row and `accept` are W words for any W from 1 to 64; a node number takes 11 bits in an item and in a stack word; a stack word is
 // node << kWavePosBits | next item, which holds an image to 2^21 items.
 //
-// Deliberately not here: a resume record for sets beyond 256 nodes (mfa_set_state has eight node words: mfa_match_batch_resume_set
-// refuses a wave image), cutting a long string of a wave image across the GPU (one long string holds one wave for its whole length), and
-// the wave kernel as the default for any image the lane kernel walks (MFA_SET_WAVE=1 forces it, for measurements and tests).
+// Strings in pieces (mfa_match_batch_resume_set_wide, the last section of this header): a record of 68 words per string, mfa_set_state_wide,
+// carries the set from call to call -- a tag quarter and 64 node words, lane l word l; its decode and check, the walk of one piece
+// from the set it holds, its encode.  The host harness of that section is tests/emul/nfa_set_wave_resume_emul.cpp, with the primitives
+// of tests/emul/wave_lanes_resume.h.  (The 48-byte record of the lane kernel, mfa_set_state, has eight node words:
+// mfa_match_batch_resume_set keeps refusing a wave image.)
+//
+// Deliberately not here: cutting a long string of a wave image across the GPU (one long string, or one long piece, holds one wave for
+// its whole length; the records above are what the chunks of such a cut would hand on), and the wave kernel as the default for any image
+// the lane kernel walks (MFA_SET_WAVE=1 forces it, for measurements and tests).
 #ifndef MFA_NFA_SET_WAVE_CORE_H
 #define MFA_NFA_SET_WAVE_CORE_H
 
@@ -74,6 +80,23 @@ struct WaveDev {
     static __device__ __forceinline__ uint32_t pop(const uint32_t* stack, uint32_t sp) {
         __builtin_amdgcn_wave_barrier();
         return uni(stack[sp]);
+    }
+    // ---- the record of a string in pieces (the last section of this header); rec is 16-byte aligned ----
+    // a row of 64 words: every lane stores its word, 256 bytes in one coalesced vector store
+    static __device__ __forceinline__ void store_row(uint32_t* row, Reg r) { row[lane()] = r; }
+    // the nodes this lane's word has, of an image of n_nodes: all ones up to n_nodes, a partial last word, zero beyond
+    static __device__ __forceinline__ Reg have(uint32_t n_nodes) {
+        const uint32_t first = lane() * 32u;
+        return n_nodes >= first + 32u ? 0xffffffffu : n_nodes > first ? (1u << (n_nodes - first)) - 1u : 0u;
+    }
+    // the tag quarter (tag, reserved[3]): one 16-byte read that every lane makes of the same place, made uniform for the compiler; and
+    // its store (tag, 0, 0, 0) by one lane, an ordinary 16-byte vector store
+    static __device__ __forceinline__ void load_tag(const uint32_t* rec, uint32_t (&q)[4]) {
+        const uint4 v = *reinterpret_cast<const uint4*>(rec);
+        q[0] = uni(v.x); q[1] = uni(v.y); q[2] = uni(v.z); q[3] = uni(v.w);
+    }
+    static __device__ __forceinline__ void store_tag(uint32_t* rec, uint32_t tag) {
+        if (lane() == 0u) *reinterpret_cast<uint4*>(rec) = make_uint4(tag, 0u, 0u, 0u);
     }
 };
 #endif
@@ -181,6 +204,56 @@ __device__ inline uint8_t nfa_wave_walk(const NfaSetView& t, uint32_t W, uint32_
     const uint32_t alive = nfa_wave_walk_from<REV, P>(t, W, stack, bytes, b, e, cur);
     if (alive != 1u) return alive == 0u ? (uint8_t)0 : (uint8_t)2;
     return nfa_wave_accepts<P>(t, W, cur);
+}
+
+// ---- strings in pieces (mfa_match_batch_resume_set_wide) ------------------------------------------------------------------------------
+// As in nfa_set_core.h: the state of the set walk between two bytes is the set itself, so a string may be cut anywhere and a record per
+// string carries the set from call to call.  The record (mfa_set_state_wide, include/mfa_hip.h) is 68 32-bit words, seventeen 16-byte
+// quarters: tag, reserved[3], then nodes[64] -- lane l's word of the mask is nodes[l], whatever W the image has.  Node v is bit v & 31
+// of nodes[v >> 5].  The tags and their meaning are nfa_set_core.h's (kSetStateStart, kSetStateLive, kSetStateInvalid).
+static constexpr uint32_t kWaveStateWords = 4u + kWaveLanes;
+static_assert(kWaveStateWords * 4u == 272u && kWaveStateWords % 4u == 0u, "a wide record is seventeen 16-byte quarters");
+
+// The set a piece of `len` bytes is entered with: returns kSetStateLive, or kSetStateInvalid (and the empty set) for a record this image
+// cannot have written -- a tag other than START or LIVE (INVALID among them, so an error stays one), a reserved word that is not zero,
+// a bit for a node the image lacks (any word at or beyond its W among them) -- and for a piece beyond the limit.  START is {start}:
+// `nodes` is loaded with the rest and not looked at.  n_nodes: the header's SET_H_NODES.
+template <class P>
+__device__ inline uint32_t nfa_wave_state_decode(const NfaSetView& t, uint32_t n_nodes, const uint32_t* rec, uint64_t len, typename P::Reg& cur) {
+    uint32_t q[4];
+    P::load_tag(rec, q);
+    const typename P::Reg in = P::load_row(rec + 4, kWaveLanes);
+    bool ok = (q[1] | q[2] | q[3]) == 0u && len <= kSetMaxString;
+    if (q[0] == kSetStateStart) {
+        cur = nfa_wave_start<P>(t);
+    } else {
+        ok = ok && q[0] == kSetStateLive && !P::any(in & ~P::have(n_nodes));
+        cur = in;
+    }
+    if (ok) return kSetStateLive;
+    cur = P::zero();
+    return kSetStateInvalid;
+}
+
+// the record of a string that has reached cur (tag LIVE; lanes at and beyond W hold zero already), or of one in error (tag INVALID:
+// `nodes` is zero whatever cur holds): all 64 lanes store their word, one lane the tag quarter
+template <class P>
+__device__ inline void nfa_wave_state_encode(uint32_t tag, const typename P::Reg& cur, uint32_t* rec) {
+    P::store_row(rec + 4, tag == kSetStateLive ? cur : P::zero());
+    P::store_tag(rec, tag);
+}
+
+// One wave, one piece [b, e) of the batch: the record at rec is replaced by the one behind the piece; returns the result byte -- what
+// the plain call answers for the concatenation of the pieces so far (the empty set meets no mask: 0).  A string that enters dead (LIVE
+// with the empty set) or in error leaves as it came and its bytes are not read.
+template <bool REV, class P>
+__device__ inline uint8_t nfa_wave_resume_piece(const NfaSetView& t, uint32_t n_nodes, uint32_t W, uint32_t* stack, const uint8_t* bytes, uint64_t b, uint64_t e,
+                                                uint32_t* rec) {
+    typename P::Reg cur;
+    uint32_t tag = nfa_wave_state_decode<P>(t, n_nodes, rec, e - b, cur);
+    if (tag == kSetStateLive && P::any(cur) && nfa_wave_walk_from<REV, P>(t, W, stack, bytes, b, e, cur) == 2u) tag = kSetStateInvalid;
+    nfa_wave_state_encode<P>(tag, cur, rec);
+    return tag == kSetStateLive ? nfa_wave_accepts<P>(t, W, cur) : (uint8_t)2;
 }
 
 }  // namespace mfa

@@ -181,24 +181,42 @@ namespace {
 
 constexpr uint64_t kPieceBytes = 8ull << 20;      // pieces of a string beyond the device's per-call limit; a multiple of 16
 
-// piece r IN SCAN ORDER of the string [b, e) cut every kPieceBytes from the end the scan starts at; empty once the string is used up
-void piece_of(uint64_t b, uint64_t e, uint64_t r, bool reversed, uint64_t* lo, uint64_t* hi) {
-    const uint64_t len = e - b, skip = r * kPieceBytes < len ? r * kPieceBytes : len, take = len - skip < kPieceBytes ? len - skip : kPieceBytes;
+// Beyond how many bytes a memory-less automaton's string goes in pieces, and the pieces' size: the device's per-call limit and
+// kPieceBytes.  DIPLOMA_PIECE_BYTES=n (tests: n a multiple of 16, at least 16; anything else is ignored) makes both n, so that strings
+// of a few KiB take the path of those beyond 16 MiB.
+struct PieceRule { uint64_t beyond, piece; };
+PieceRule piece_rule() {
+    if (const char* e = getenv("DIPLOMA_PIECE_BYTES")) {
+        char* end = nullptr;
+        const unsigned long long n = strtoull(e, &end, 10);
+        if (end != e && *end == 0 && n >= 16 && n % 16 == 0) return {n, n};
+    }
+    return {MFA_MAX_STRING_BYTES, kPieceBytes};
+}
+
+// piece r IN SCAN ORDER of the string [b, e) cut every `piece` bytes from the end the scan starts at; empty once the string is used up
+void piece_of(uint64_t b, uint64_t e, uint64_t r, bool reversed, uint64_t piece, uint64_t* lo, uint64_t* hi) {
+    const uint64_t len = e - b, skip = r * piece < len ? r * piece : len, take = len - skip < piece ? len - skip : piece;
     if (reversed) { *hi = e - skip; *lo = *hi - take; }
     else { *lo = b + skip; *hi = *lo + take; }
 }
 
-// the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call.  set_walk: the
-// image walks node sets (dfa_states == 0), so a string's state between two pieces is a record of mfa_match_batch_resume_set_host, not one word.
-// That record holds 256 nodes: an image of more (n_nodes) is walked one string per wave and hands nothing from call to call.
-void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, uint32_t n_nodes, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
-    if (set_walk && n_nodes > 256u)
-        throw std::runtime_error("Automata::match: a string beyond the limit of one call, and the automaton is walked as a set of " + std::to_string(n_nodes) +
-                                 " nodes -- more than 256 nodes: strings in pieces are not available");
+// the strings `which` of a memory-less automaton's batch, each given to the device in pieces, one round of pieces per call.  What a string's
+// state between two pieces is, and so which resume call carries it, is the image's to say (mfa_image_resume_state_bytes): one word of a
+// tabulated image, a record of eight node words of a set-walk image of up to 256 nodes, a record of 64 of an image walked one string per wave.
+void match_in_pieces(mfa_image* img, bool reversed, const uint8_t* bytes, const uint64_t* offsets, const vector<uint64_t>& which, uint8_t* results, int device) {
+    const uint64_t piece = piece_rule().piece;
+    uint32_t state_bytes = 0;
+    int rc = mfa_image_resume_state_bytes(img, &state_bytes);
+    if (rc != MFA_OK) fail("mfa_image_resume_state_bytes", rc);
+    if (state_bytes != sizeof(uint32_t) && state_bytes != sizeof(mfa_set_state) && state_bytes != sizeof(mfa_set_state_wide))
+        throw std::runtime_error("Automata::match: a string in pieces, and the image carries " + std::to_string(state_bytes) + " bytes from piece to piece: no call for that");
     uint64_t rounds = 1;
-    for (uint64_t k : which) rounds = std::max(rounds, (offsets[k + 1] - offsets[k] + kPieceBytes - 1) / kPieceBytes);
-    vector<uint32_t> states(set_walk ? 0 : which.size(), MFA_DFA_STATE_START);
-    vector<mfa_set_state> sets(set_walk ? which.size() : 0, mfa_set_state{});      // zeroed: MFA_SET_STATE_START
+    for (uint64_t k : which) rounds = std::max(rounds, (offsets[k + 1] - offsets[k] + piece - 1) / piece);
+    vector<uint32_t> states(state_bytes == sizeof(uint32_t) ? which.size() : 0, MFA_DFA_STATE_START);
+    vector<mfa_set_state> sets(state_bytes == sizeof(mfa_set_state) ? which.size() : 0, mfa_set_state{});                  // zeroed: MFA_SET_STATE_START
+    vector<mfa_set_state_wide> wide(state_bytes == sizeof(mfa_set_state_wide) ? which.size() : 0, mfa_set_state_wide{});
+    const char* call = !states.empty() ? "mfa_match_batch_resume_host" : !sets.empty() ? "mfa_match_batch_resume_set_host" : "mfa_match_batch_resume_set_wide_host";
     vector<uint8_t> res(which.size()), stage;
     vector<uint64_t> off(which.size() + 1);
     for (uint64_t r = 0; r < rounds; r++) {
@@ -206,17 +224,16 @@ void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, uint32_t n_no
         off[0] = 0;
         for (size_t j = 0; j < which.size(); j++) {
             uint64_t lo, hi;
-            piece_of(offsets[which[j]], offsets[which[j] + 1], r, reversed, &lo, &hi);
+            piece_of(offsets[which[j]], offsets[which[j] + 1], r, reversed, piece, &lo, &hi);
             stage.insert(stage.end(), bytes + lo, bytes + hi);
             off[j + 1] = stage.size();
         }
         stage.resize(stage.size() + 16);
         uint8_t* out = r + 1 == rounds ? res.data() : nullptr;
-        const int rc = set_walk ? mfa_match_batch_resume_set_host(img, stage.data(), off.data(), which.size(), sets.data(), out, device)
-                                : mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), out, device);
-        if (set_walk && rc == MFA_ERR_UNSUPPORTED)      // (MFA_SET_WAVE=1 gives a narrow image the wave form too)
-            throw std::runtime_error("Automata::match: a string beyond the limit of one call, and the automaton is walked one string per wave: strings in pieces are not available");
-        if (rc != MFA_OK) fail(set_walk ? "mfa_match_batch_resume_set_host" : "mfa_match_batch_resume_host", rc);
+        rc = !states.empty() ? mfa_match_batch_resume_host(img, stage.data(), off.data(), which.size(), states.data(), out, device)
+           : !sets.empty()   ? mfa_match_batch_resume_set_host(img, stage.data(), off.data(), which.size(), sets.data(), out, device)
+                             : mfa_match_batch_resume_set_wide_host(img, stage.data(), off.data(), which.size(), wide.data(), out, device);
+        if (rc != MFA_OK) fail(call, rc);
     }
     for (size_t j = 0; j < which.size(); j++) results[which[j]] = res[j];
 }
@@ -226,12 +243,13 @@ void match_in_pieces(mfa_image* img, bool reversed, bool set_walk, uint32_t n_no
 void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     mfa_image* img = image_for_match();
     mfa_image_info info;
-    // (a memory-less image hands its state from call to call -- one word, or for a set-walk image, dfa_states == 0, a record of node sets --
-    // so its strings may be longer than one call takes; a memory automaton's are refused)
+    // (a memory-less image hands its state from call to call -- one word, or for a set-walk image, dfa_states == 0, a record of its node set,
+    // narrow or wide -- so its strings may be longer than one call takes; a memory automaton's are refused)
     if (mfa_image_get_info(img, &info) == MFA_OK && info.kind == MFA_KIND_NFA) {
         vector<uint64_t> longs;
+        const uint64_t beyond = piece_rule().beyond;
         for (uint64_t k = 0; k < n; k++)
-            if (offsets[k + 1] - offsets[k] > MFA_MAX_STRING_BYTES) longs.push_back(k);
+            if (offsets[k + 1] - offsets[k] > beyond) longs.push_back(k);
         if (!longs.empty()) {
             // the runs of shorter strings between them lie back to back in the caller's buffer: each takes the one call it always took
             uint64_t from = 0;
@@ -240,7 +258,7 @@ void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint6
                 if (to > from) match_packed_short(img, bytes, offsets + from, to - from, results + from);
                 from = to + 1;
             }
-            match_in_pieces(img, info.is_reversed != 0, info.dfa_states == 0, info.n_nodes, bytes, offsets, longs, results, device);
+            match_in_pieces(img, info.is_reversed != 0, bytes, offsets, longs, results, device);
             return;
         }
     }
@@ -314,7 +332,7 @@ void Automata::Stream::feed(const string& block) {
     vector<uint8_t> stage;
     for (uint64_t r = 0; r == 0 || r * kPieceBytes < block.size(); r++) {
         uint64_t lo, hi;
-        piece_of(0, block.size(), r, info.is_reversed != 0, &lo, &hi);
+        piece_of(0, block.size(), r, info.is_reversed != 0, kPieceBytes, &lo, &hi);
         stage.assign(bytes + lo, bytes + hi);
         stage.resize(stage.size() + 16);
         const uint64_t off[2] = {0, hi - lo};
@@ -409,7 +427,7 @@ vector<vector<bool>> match_mixed(const vector<Automata*>& automata, const vector
         mfa_image_info info;
         const bool memory_less = mfa_image_get_info(images[k], &info) == MFA_OK && info.kind == MFA_KIND_NFA;      // (tabulated or set walk: its strings may go in pieces)
         for (const string& s : strs[k]) {
-            if (memory_less && s.size() > MFA_MAX_STRING_BYTES) { longs.push_back({off.size() - 1, &s}); long_owner.push_back(automata[k]); }
+            if (memory_less && s.size() > piece_rule().beyond) { longs.push_back({off.size() - 1, &s}); long_owner.push_back(automata[k]); }
             else bytes.insert(bytes.end(), s.begin(), s.end());
             off.push_back(bytes.size());
         }

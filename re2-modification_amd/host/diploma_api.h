@@ -137,8 +137,10 @@ public:
 
     // reference automata.cpp:177-210, on the GPU (a batch of one).  A memory-less automaton takes strings of any length: one beyond the
     // device's per-call limit (MFA_MAX_STRING_BYTES) is cut into pieces of 8 MiB that go through mfa_match_batch_resume_host (for an automaton
-    // walked as a set of nodes: mfa_match_batch_resume_set_host) round by round, last piece first for a reversed automaton; match_batch, match_packed and the memory-less segments of match_mixed do the
+    // walked as a set of nodes: mfa_match_batch_resume_set_host, or _set_wide_host when it is walked one string per wave;
+    // mfa_image_resume_state_bytes says which) round by round, last piece first for a reversed automaton; match_batch, match_packed and the memory-less segments of match_mixed do the
     // same, and the shorter strings of the batch take the one call they always took.  A memory automaton refuses such a string as before.
+    // Environment, for tests: DIPLOMA_PIECE_BYTES=n (a multiple of 16, at least 16) makes both the limit and the piece size n.
     bool match(const string& str);
     // the same for many strings in one launch; result[k] is what match(strs[k]) returns
     vector<bool> match_batch(const vector<string>& strs);

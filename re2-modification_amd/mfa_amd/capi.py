@@ -20,11 +20,13 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_mixed_create", "mfa_mixed_destroy", "mfa_match_mixed", "mfa_match_mixed_sized", "mfa_match_mixed_host", "mfa_mixed_last_ms", "mfa_mixed_timing",
            "mfa_mixed_last_launches", "mfa_mixed_last_dfa", "mfa_pack_result_bitmap", "mfa_last_dfa_split",
            "mfa_match_batch_resume", "mfa_match_batch_resume_host", "mfa_last_dfa_spec",
-           "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split"]
+           "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split",
+           "mfa_match_batch_resume_set_wide", "mfa_match_batch_resume_set_wide_host", "mfa_image_resume_state_bytes"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 SET_STATE_WORDS = 12                                                        # a record of mfa_match_batch_resume_set: tag, reserved[3], nodes[8]
-SET_STATE_START, SET_STATE_LIVE, SET_STATE_INVALID = 0, 1, 0xffffffff       # its tags (records are never stored either)
+SET_STATE_WIDE_WORDS = 68                                                   # a record of mfa_match_batch_resume_set_wide (wave images): tag, reserved[3], nodes[64]
+SET_STATE_START, SET_STATE_LIVE, SET_STATE_INVALID = 0, 1, 0xffffffff       # their tags (records are never stored either)
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
 
 
@@ -77,6 +79,10 @@ def lib():
         if hasattr(L, "mfa_match_batch_resume_set"):      # (a library of an older build given by MFA_LIB_PATH for an A/B run lacks it)
             L.mfa_match_batch_resume_set.argtypes = [vp, vp, vp, u64, vp, vp, i32, vp]
             L.mfa_match_batch_resume_set_host.argtypes = [vp, vp, vp, u64, vp, vp, i32]
+        if hasattr(L, "mfa_match_batch_resume_set_wide"):      # (as above: an older build)
+            L.mfa_match_batch_resume_set_wide.argtypes = [vp, vp, vp, u64, vp, vp, i32, vp]
+            L.mfa_match_batch_resume_set_wide_host.argtypes = [vp, vp, vp, u64, vp, vp, i32]
+            L.mfa_image_resume_state_bytes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
         L.mfa_last_kernel_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
         if hasattr(L, "mfa_last_dfa_split"):              # (a library of an older build given by MFA_LIB_PATH for an A/B run lacks it)
             L.mfa_last_dfa_split.argtypes = [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32)]
@@ -228,6 +234,39 @@ class Image:
         _check(lib().mfa_match_batch_resume_set_host(self._h, data.ctypes.data, offsets.ctypes.data, n, states.ctypes.data,
                                                      res.ctypes.data if want_results else None, device), "mfa_match_batch_resume_set_host")
         return res[:n] if want_results else None
+
+    def match_tensors_resume_set_wide(self, d_bytes, d_offsets, d_states, d_results=None, stream=None):
+        """mfa_match_batch_resume_set_wide on torch CUDA tensors: one round of pieces of n strings of a wave image (resume_state_bytes() ==
+        4 * SET_STATE_WIDE_WORDS), in scan order.  d_states: int32 or uint32 tensor of n * SET_STATE_WIDE_WORDS words, updated in place
+        (all zero before a string's first piece); d_results: uint8 tensor of n bytes, or None for no result bytes.  Returns d_results.
+        Asynchronous on `stream`."""
+        import torch
+        n = d_offsets.numel() - 1
+        assert d_states.element_size() == 4 and d_states.numel() >= n * SET_STATE_WIDE_WORDS
+        dev = d_offsets.device.index or 0
+        s = stream if stream is not None else torch.cuda.current_stream(d_offsets.device)
+        _check(lib().mfa_match_batch_resume_set_wide(self._h, d_bytes.data_ptr(), d_offsets.data_ptr(), n, d_states.data_ptr(),
+                                                     d_results.data_ptr() if d_results is not None else None, dev, ctypes.c_void_p(s.cuda_stream)),
+               "mfa_match_batch_resume_set_wide")
+        return d_results
+
+    def match_host_resume_set_wide(self, data, offsets, states, want_results=True, device=0):
+        """mfa_match_batch_resume_set_wide_host: numpy uint8 data, uint64 offsets (n + 1) and uint32 states (n * SET_STATE_WIDE_WORDS words,
+        updated in place) in host memory; returns the numpy uint8 results, or None with want_results=False."""
+        import numpy as np
+        n = len(offsets) - 1
+        assert states.dtype == np.uint32 and states.size >= n * SET_STATE_WIDE_WORDS
+        res = np.zeros(max(n, 1), dtype=np.uint8) if want_results else None
+        _check(lib().mfa_match_batch_resume_set_wide_host(self._h, data.ctypes.data, offsets.ctypes.data, n, states.ctypes.data,
+                                                          res.ctypes.data if want_results else None, device), "mfa_match_batch_resume_set_wide_host")
+        return res[:n] if want_results else None
+
+    def resume_state_bytes(self):
+        """mfa_image_resume_state_bytes: the bytes of one string's state between two pieces, which names the resume call the image takes --
+        0 a memory automaton (none), 4 match_tensors_resume, 48 match_tensors_resume_set, 272 match_tensors_resume_set_wide"""
+        out = ctypes.c_uint32()
+        _check(lib().mfa_image_resume_state_bytes(self._h, ctypes.byref(out)), "mfa_image_resume_state_bytes")
+        return out.value
 
     def last_kernel_ms(self, device=0):
         ms = ctypes.c_float()

@@ -9,7 +9,8 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
       Every side's answers are held to the CPU restatement of its own image on the first 1024 strings
   (c) strings in pieces: on the two set-walk images of (a) and (b), mfa_match_batch_resume_set on the whole strings from zeroed records
       (nfa_set_resume_kernel: the same step loop, 48 bytes of record in and out per string) against mfa_match_batch on the same batch;
-      lines appended to profiles/r12_nfa_set_resume.jsonl
+      lines appended to profiles/r12_nfa_set_resume.jsonl.  (An image that says it takes the wide record -- resume_state_bytes() == 272,
+      a wave image -- goes through mfa_match_batch_resume_set_wide: `wave resume` below.)
 
   nfa_setwalk.py [REPS] [STRINGS] [all|tables|resume]      tables: (a) and (b) only; resume: (c) only
 
@@ -22,7 +23,7 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
               takes seconds per call)
       short   1 Mi x 1 KiB (no long string): this build's kernel time per call, to be set against another build's (MFA_LIB_PATH) process by process
 
-  nfa_setwalk.py wave narrow|wide [REPS] [STRINGS] [OUT.jsonl] [first]   the wave-cooperative step (csrc/nfa_set_wave.hip: one string per wave), lines appended
+  nfa_setwalk.py wave narrow|wide|resume [REPS] [STRINGS] [OUT.jsonl] [first]   the wave-cooperative step (csrc/nfa_set_wave.hip: one string per wave), lines appended
       to OUT.jsonl (default profiles/r14_nfa_set_wave.jsonl).  Medians of REPS calls (default 7) after five uncounted ones, the sides
       alternating; the first strings' answers are held to the CPU restatement.
       narrow  the lane kernel against MFA_SET_WAVE=1 on the same build, on (a|b)*abb forced to the set walk (W = 1) and on the k = 20
@@ -31,6 +32,10 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
       wide    images the lane kernel cannot hold: (a|b)*a(a|b)^k Thompson with 257 to 512 and with 1025 to 2048 nodes, STRINGS x 1 KiB;
               bytes per second and per resident wave, and the CPU restatement's time on the first 1024 strings beside it, for scale;
               `first`: the narrower image only (a call on the wider one takes a minute at 1 Mi strings)
+      resume  strings in pieces on the two images of `wide`: mfa_match_batch_resume_set_wide on the whole strings from zeroed records
+              (nfa_set_wave_resume_kernel: the same walk, 272 bytes of record in and out per string) against mfa_match_batch on the
+              same batch, as (c) does for the lane images (five uncounted rounds, REPS at least 3); lines appended to OUT.jsonl
+              (default profiles/r15_nfa_set_wave_resume.jsonl)
 """
 import json
 import os
@@ -107,16 +112,20 @@ def compare(what, sides, blobs, flat, d_off, reps, extra):
         f.write(line + "\n")
 
 
-def compare_resume(what, img, blob, flat, d_off, reps):
-    """the resume call on whole strings from zeroed records against the plain call, one set-walk image, the same batch"""
+def compare_resume(what, img, blob, flat, d_off, reps, out_path=None):
+    """the resume call on whole strings from zeroed records against the plain call, one set-walk image, the same batch.  Which resume
+    call -- the 48-byte record of a lane image or the 272-byte record of a wave image -- is the image's to say (resume_state_bytes)"""
     n = d_off.numel() - 1
     total = int(d_off[-1])
     m = min(n, SAMPLE)
     off = d_off[:m + 1].cpu().numpy().astype(np.uint64)
     want = torch.from_numpy(oracle_lib.OracleImage(blob).match_packed(flat[:int(off[-1])].cpu().numpy(), off).astype(np.uint8)).to(DEV)
-    names = ("mfa_match_batch", "mfa_match_batch_resume_set, whole strings from zeroed records")
+    wide = img.resume_state_bytes() == 4 * capi.SET_STATE_WIDE_WORDS
+    words = capi.SET_STATE_WIDE_WORDS if wide else capi.SET_STATE_WORDS
+    assert img.resume_state_bytes() == 4 * words
+    names = ("mfa_match_batch", "mfa_match_batch_resume_set%s, whole strings from zeroed records" % ("_wide" if wide else ""))
     res = {k: torch.full((n,), 7, dtype=torch.uint8, device=DEV) for k in names}
-    d_states = torch.zeros(n * capi.SET_STATE_WORDS, dtype=torch.int32, device=DEV)
+    d_states = torch.zeros(n * words, dtype=torch.int32, device=DEV)
 
     def plain():
         img.match_tensors(flat, d_off, res[names[0]])
@@ -124,13 +133,13 @@ def compare_resume(what, img, blob, flat, d_off, reps):
 
     def resume():
         d_states.zero_()                                   # (in front of the start event: not in the kernel's time)
-        img.match_tensors_resume_set(flat, d_off, d_states, res[names[1]])
+        (img.match_tensors_resume_set_wide if wide else img.match_tensors_resume_set)(flat, d_off, d_states, res[names[1]])
         return img.last_kernel_ms(0)
 
     ms = alternate({names[0]: plain, names[1]: resume}, reps)
     assert img.info()["dfa_states"] == 0 and img.info()["last_kernel"] == capi.KERNEL_NODESET
-    tags = d_states.view(n, capi.SET_STATE_WORDS)[:, 0]
-    out = {"what": what, "device": torch.cuda.get_device_name(0), "strings": n, "bytes": total, "record_bytes_in_and_out": 2 * 4 * capi.SET_STATE_WORDS * n,
+    tags = d_states.view(n, words)[:, 0]
+    out = {"what": what, "device": torch.cuda.get_device_name(0), "strings": n, "bytes": total, "n_nodes": img.info()["n_nodes"], "record_bytes_in_and_out": 2 * 4 * words * n,
            "results_equal_on_all_strings": bool(torch.equal(res[names[0]], res[names[1]])), "all_records_live": bool((tags == capi.SET_STATE_LIVE).all())}
     for k, v in ms.items():
         med = float(np.median(v))
@@ -139,7 +148,7 @@ def compare_resume(what, img, blob, flat, d_off, reps):
     out["resume_over_plain"] = out[names[1]]["median_ms"] / out[names[0]]["median_ms"]
     line = json.dumps(out)
     print(line, flush=True)
-    with open(os.path.join(ROOT, "profiles", "r12_nfa_set_resume.jsonl"), "a") as f:
+    with open(out_path or os.path.join(ROOT, "profiles", "r12_nfa_set_resume.jsonl"), "a") as f:
         f.write(line + "\n")
 
 
@@ -271,14 +280,19 @@ def wave_main():
     reps = max(3, int(sys.argv[3])) if len(sys.argv) > 3 else 7
     n = int(sys.argv[4]) if len(sys.argv) > 4 else 1 << 20
     out_path = sys.argv[5] if len(sys.argv) > 5 else os.path.join(ROOT, "profiles", "r14_nfa_set_wave.jsonl")
-    assert mode in ("narrow", "wide")
+    assert mode in ("narrow", "wide", "resume")
+    if mode == "resume" and len(sys.argv) <= 5:
+        out_path = os.path.join(ROOT, "profiles", "r15_nfa_set_wave_resume.jsonl")
     kib = batch([1024] * n, 2)
-    if mode == "wide":
+    if mode in ("wide", "resume"):
         for lo, hi in ((256, 512), (1024, 2048))[:1 if "first" in sys.argv[6:] else 2]:
             k = (lo - 9) // 5 + 1                                # the Thompson compile has 5 k + 9 nodes
             blob = front_end("(a|b)*a" + "(a|b)" * k, "-thompson")
             img, _ = created(blob, "1")
             assert lo < img.info()["n_nodes"] <= hi and img.info()["dfa_states"] == 0
+            if mode == "resume":
+                compare_resume("%d x 1 KiB, (a|b)*a(a|b)^%d Thompson, %d nodes" % (n, k, img.info()["n_nodes"]), img, blob, kib[0], kib[1], reps, out_path)
+                continue
             wave_sides("%d x 1 KiB, (a|b)*a(a|b)^%d Thompson, %d nodes" % (n, k, img.info()["n_nodes"]), {"wave kernel": img}, blob, kib[0], kib[1], reps, 5, {}, out_path)
         return
     abb = image.blob_from_dump(oracle_lib.load_dump("nfa_abb_thompson"))

@@ -83,10 +83,11 @@ typedef struct mfa_image_info {
  * 255 byte classes, no cycle of epsilon edges among the nodes reachable from the start (the reference's evaluateState would not return),
  * and, for an image of up to 256 nodes, epsilon chains of at most 49 nodes.  Wave images: up to 256 nodes a lane holds the set and walks
  * a string (nfa_set_kernel); an image of 257 to 2048 nodes is a WAVE image: one string per wave, the set across its 64 lanes
- * (nfa_set_wave_kernel; last_kernel is MFA_KERNEL_NODESET all the same), epsilon chains of any length.  mfa_match_batch, _host, _regions
- * and a mixed object walk every string of a wave image whole, whatever its length up to MFA_MAX_STRING_BYTES: nothing below about long
- * strings applies to it -- no string is cut (one long string holds one wave for its whole length) and mfa_last_set_split answers
- * zeros -- and its strings in pieces have a record and a call of their own: mfa_match_batch_resume_set refuses it,
+ * (nfa_set_wave_kernel; last_kernel is MFA_KERNEL_NODESET all the same), epsilon chains of any length.  What is said below about long
+ * strings applies to a wave image too (mfa_match_batch, _host, _regions, its segment of a mixed object, and the wide resume call), with
+ * a WAVE per chunk where a lane image has a lane: the same scheme, the same knobs and the same report in mfa_last_set_split; only the
+ * chunk minimum (1024 bytes) and the arena differ -- a chunk takes 816 bytes of it and at most 32768 chunks are planned for, about 55 MB
+ * per overlapping launch.  Its strings in pieces have a record and a call of their own: mfa_match_batch_resume_set refuses it,
  * mfa_match_batch_resume_set_wide (further down) takes it.  MFA_SET_WAVE=1, read here too, makes EVERY set-walk
  * image a wave image, the narrow ones as well: a knob for measurements and tests, never the default (the lane kernel is many times
  * faster where it applies).  Strings in pieces: its state between two bytes is a set of nodes, not one 32-bit number, so
@@ -259,9 +260,13 @@ int  mfa_match_batch_resume_set_host(mfa_image_t* img, const uint8_t* bytes, con
  * zero, a bit for a node the image lacks (any word at or beyond W included), a piece longer than MFA_MAX_STRING_BYTES or a stack
  * overflow leaves tag MFA_SET_STATE_INVALID, `nodes` zero and result 2, and so does every later call on that record.  The SUM of a
  * string's pieces has no limit.  A record that enters LIVE with the empty set leaves as it came with result 0 and its bytes are not read.
- * Nothing is cut: a piece is walked whole by one wave whatever its length (nfa_set_wave_resume_kernel), and mfa_last_set_split answers
- * zeros.  last_kernel becomes MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the launch.  Re-entrant per (image, device, stream), and
- * legal inside a stream capture once a first call has run (it allocates the workspace and raises the kernel's LDS limit).
+ * Long pieces: a piece of MFA_DFA_SPLIT_MIN bytes or more (and within MFA_MAX_STRING_BYTES) whose record holds a live set that is not
+ * empty is cut into chunks inside the same call, a wave per chunk, as mfa_match_batch cuts a long string of such an image
+ * (mfa_image_create above); the first chunk starts from the record's set, and the record gets the set reached.  Dead, invalid and
+ * over-long records are answered as before, by the main kernel (nfa_set_wave_resume_kernel).  mfa_last_set_split tells what the call
+ * did (zeros when no piece was queued).  last_kernel becomes MFA_KERNEL_NODESET and mfa_last_kernel_ms covers the kernel and the
+ * launches behind it.  Re-entrant per (image, device, stream), and legal inside a stream capture once a first call has run (it
+ * allocates the workspace and raises the kernels' LDS limit).
  * MFA_ERR_INVALID_ARG: img, d_offsets or d_states is NULL, or d_states is not 16-byte aligned.  MFA_ERR_UNSUPPORTED, with the records
  * as they came: a memory automaton, a tabulated image, or a lane image (a set-walk image of up to 256 nodes made without
  * MFA_SET_WAVE=1: its call is the 48-byte one).  All are answered before the device is touched; n == 0 is MFA_OK. */

@@ -94,6 +94,7 @@ void device_release(DeviceState& ds) {
     if (ds.d_dfa_accept) (void)hipFree(ds.d_dfa_accept);
     if (ds.d_byte_class) (void)hipFree(ds.d_byte_class);
     if (ds.d_set_tables) (void)hipFree(ds.d_set_tables);
+    if (ds.d_set_home) (void)hipFree(ds.d_set_home);
     if (ds.d_walk) (void)hipFree(ds.d_walk);
     for (LaunchCtx* cx : ds.ctxs) { ctx_free(*cx); delete cx; }
     jit_unload(ds);
@@ -122,6 +123,7 @@ int device_prepare(mfa_image* img, int device, DeviceState** out) {
         if (img->walk_ok) rc = up((void**)&ds.d_walk, img->walk.words.data(), img->walk.words.size() * 4);
     } else if (h.set_walk) {
         rc = up((void**)&ds.d_set_tables, h.set_tables.data(), h.set_tables.size() * 4);
+        if (rc == MFA_OK && h.set_wave) rc = up((void**)&ds.d_set_home, h.set_home_wide, sizeof h.set_home_wide);      // (the table layout stays as it is)
     } else {
         if (h.dfa_states <= 0xffffu) {
             std::vector<uint16_t> t16(h.dfa_trans.begin(), h.dfa_trans.end());

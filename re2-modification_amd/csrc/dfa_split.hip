@@ -194,7 +194,9 @@ int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, S
 // each of the map_cap chunks the plan can hand out -- and the zeroed header.  *out is the caller's, cleared but for what it has set itself.
 // start_quiet: a workspace counts as quiet from its first call on, not after kSplitQuietCalls calls without a long string (dfa_spec.hip).
 // chunk_min_default: the chunk minimum where MFA_DFA_CHUNK is not set (kSplitChunkMin; nfa_set_split.hip has its own).
-int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default) {
+// arena_cap: the most chunks of arena this caller reserves records for (0: kSplitArenaChunks; nfa_set_wave_split.hip's records are 816 bytes).
+int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default,
+                      uint32_t arena_cap) {
     const char* on = getenv("MFA_DFA_SPLIT");
     // (n < 2^31: the queue counter is a 32-bit word that every long string increments, also when the queue is full; it must not wrap)
     if ((on && on[0] == '0') || n >= 0x80000000ull) return MFA_OK;
@@ -220,9 +222,10 @@ int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out,
     uint64_t chunk_min = (env_u64("MFA_DFA_CHUNK", chunk_min_default) + 15u) & ~(uint64_t)15;
     if (chunk_min < 16u) chunk_min = 16u;
     if (chunk_min > (1u << 30)) chunk_min = 1u << 30;
-    uint64_t arena = env_u64("MFA_DFA_ARENA", kSplitArenaChunks);       // (tests shrink it to see the chunk size grow)
+    if (arena_cap == 0u || arena_cap > kSplitArenaChunks) arena_cap = kSplitArenaChunks;
+    uint64_t arena = env_u64("MFA_DFA_ARENA", arena_cap);               // (tests shrink it to see the chunk size grow)
     if (arena < 1u) arena = 1u;
-    if (arena > kSplitArenaChunks) arena = kSplitArenaChunks;
+    if (arena > arena_cap) arena = arena_cap;
     out->chunk_min = (uint32_t)chunk_min;
     out->arena_chunks = (uint32_t)arena;
     out->map_cap = (uint32_t)split_map_capacity(arena, kSplitQueueCap);

@@ -173,7 +173,7 @@ int nfa_eps_chain(const HostImage& img, uint32_t* chain, std::vector<uint8_t>* r
 // longer epsilon chain than the kernel holds, or a cycle of epsilon edges.
 // wave: the tables of the wave-cooperative walk instead (nfa_set_wave_core.h): the same header and sections, a mask row of W =
 // ceil(n / 32) words for up to kWaveMaxNodes nodes, 11 bits of node number in an epsilon item, a stack of up to n slots (the chain is
-// never longer), items held to 2^kWavePosBits; no home set (nothing cuts a wave image's strings).
+// never longer), items held to 2^kWavePosBits; the home set is the wide one (nfa_set_home_wide: 64 words, for nfa_set_wave_split.hip).
 static int set_tables_build(HostImage& img, bool wave) {
     const uint32_t n = img.h.n_nodes;
     std::vector<int> rep;
@@ -229,7 +229,8 @@ static int set_tables_build(HostImage& img, bool wave) {
     img.set_walk = true;
     img.set_wave = wave;
     img.dfa_states = 0; img.dfa_trans.clear(); img.dfa_accept.clear();
-    if (!wave) nfa_set_home(img, img.set_home);
+    if (wave) nfa_set_home_wide(img, img.set_home_wide);
+    else nfa_set_home(img, img.set_home);
     return MFA_OK;
 }
 
@@ -241,7 +242,7 @@ int nfa_set_wave_build(HostImage& img) { return set_tables_build(img, true); }
 // every step draws a byte class (xorshift32, the seed of spec_home_state) and takes the first class from there on, cyclically, whose
 // step (Stepper: the norm) does not lead to the empty set; a set with no such class ends the walk.  4096 steps.  Never empty.
 // img.byte_class and img.n_classes are nfa_byte_classes' (nfa_set_build has called it).
-void nfa_set_home(const HostImage& img, uint32_t (&home)[8]) {
+static std::vector<uint8_t> set_home_nodes(const HostImage& img) {
     const uint32_t n = img.h.n_nodes, C = img.n_classes;
     std::vector<int> rep(C, 0);
     for (int b = 255; b >= 0; b--) rep[img.byte_class[b]] = b;       // (any byte of a class steps alike)
@@ -259,8 +260,21 @@ void nfa_set_home(const HostImage& img, uint32_t (&home)[8]) {
         }
         if (!moved) break;
     }
+    return cur;
+}
+
+void nfa_set_home(const HostImage& img, uint32_t (&home)[8]) {
+    const std::vector<uint8_t> cur = set_home_nodes(img);
     for (uint32_t& w : home) w = 0u;
-    for (uint32_t v = 0; v < n && v < 256u; v++)
+    for (uint32_t v = 0; v < img.h.n_nodes && v < 256u; v++)
+        if (cur[v]) home[v >> 5] |= 1u << (v & 31u);
+}
+
+// the same set for a wave image (nfa_set_wave_split_core.h: wave_spec_guess): 64 words, lane l of a wave its word l
+void nfa_set_home_wide(const HostImage& img, uint32_t (&home)[64]) {
+    const std::vector<uint8_t> cur = set_home_nodes(img);
+    for (uint32_t& w : home) w = 0u;
+    for (uint32_t v = 0; v < img.h.n_nodes && v < kWaveMaxNodes; v++)
         if (cur[v]) home[v >> 5] |= 1u << (v & 31u);
 }
 

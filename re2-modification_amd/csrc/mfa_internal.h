@@ -45,6 +45,7 @@ struct HostImage {
     std::vector<uint32_t> set_tables;
     bool                  set_wave = false;    //   ... in the form of the wave-cooperative walk (nfa_set_wave_core.h): one string per wave, up to 2048 nodes
     uint32_t              set_home[8] = {0};   //   ... and the second seed of nfa_set_split.hip's guesses, a node set (image_host.cpp: nfa_set_home)
+    uint32_t              set_home_wide[64] = {0};   //   ... of a wave image: the second seed of nfa_set_wave_split.hip's guesses (nfa_set_home_wide), set_home stays zero
     mutable int           jit_source_ok = -1;      // MFA kind: the generated kernel's source is of a size a compiler finishes (jit.hip; -1 = not looked at)
 };
 
@@ -54,6 +55,7 @@ int tabulate_nfa(HostImage& img, uint32_t max_states = MFA_MAX_DFA_STATES, std::
 int nfa_set_build(HostImage& img);                                   // fills set_tables instead (MFA_ERR_UNSUPPORTED: outside the set walk's limits)
 int nfa_set_wave_build(HostImage& img);                              // ... in the wave form (sets set_wave beside set_walk; MFA_ERR_UNSUPPORTED beyond 2048 nodes)
 void nfa_set_home(const HostImage& img, uint32_t (&home)[8]);        // a set-walk image's home set (nfa_set_build fills set_home with it)
+void nfa_set_home_wide(const HostImage& img, uint32_t (&home)[64]);  // a wave image's home set, the same rule (nfa_set_wave_build fills set_home_wide with it)
 int nfa_image_build(HostImage& img);                                 // MFA_KIND_NFA at image creation: one or the other
 
 // ---- per-device state -----------------------------------------------------------------------
@@ -97,6 +99,7 @@ struct DeviceState {
     uint8_t*  d_dfa_accept = nullptr;
     uint8_t*  d_byte_class = nullptr;
     uint32_t* d_set_tables = nullptr;   // a set-walk image: HostImage::set_tables
+    uint32_t* d_set_home = nullptr;     // a wave image: HostImage::set_home_wide, 64 words of their own
     // launch workspaces
     std::vector<LaunchCtx*> ctxs;
     LaunchCtx*              last = nullptr;    // context of the most recent launch (mfa_last_kernel_ms)
@@ -139,7 +142,8 @@ int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const u
 // words, 16-byte aligned); d_results may be NULL
 int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                           uint32_t* d_states, uint8_t* d_results, void* stream);
-// nfa_set_wave.hip: the same for an image with wave tables (HostImage::set_wave), one string per wave; nothing is cut
+// nfa_set_wave.hip: the same for an image with wave tables (HostImage::set_wave), one string per wave; a long string is cut by
+// nfa_set_wave_split.hip behind the main kernel
 int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_results, void* stream);
 // the same walk with every string's set read from and written to its record of d_states (mfa_match_batch_resume_set_wide: n records of
@@ -161,7 +165,8 @@ struct SplitLaunch {
 uint64_t env_u64(const char* name, uint64_t dflt);
 bool split_applies(const HostImage& img);
 int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
-int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default);
+int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default,
+                       uint32_t arena_cap = 0u);      // arena_cap: the most chunks of arena (0: kSplitArenaChunks)
 int  split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream);
 // d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
@@ -181,6 +186,11 @@ int  spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, con
 int  set_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
 int  set_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                     uint8_t* d_results, void* stream, uint32_t* d_states);
+// nfa_set_wave_split.hip: the same three steps for a wave image, a wave per chunk and records of 68 words (mfa_set_state_wide);
+// nfa_set_wave.hip hands out->args to its main kernel.  d_states != NULL: mfa_match_batch_resume_set_wide.
+int  set_wave_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+int  set_wave_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                         uint8_t* d_results, void* stream, uint32_t* d_states);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

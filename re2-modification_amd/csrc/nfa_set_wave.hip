@@ -7,22 +7,32 @@
 //   Input: up to 64 aligned 16-byte blocks per wave and round, lane l block l; only blocks that hold a byte of the string.
 //   Grid: persistent, capped by what the CUs keep resident (lds_blocks_per_cu), strings dealt out by wave number.
 // Strings in pieces (mfa_match_batch_resume_set_wide): nfa_set_wave_resume_kernel, the same grid and LDS, a record of 68 words per
-// string (mfa_set_state_wide) read before the piece and written behind it.  Nothing is cut: one long string, or one long piece, holds
-// one wave for its whole length, and mfa_match_batch_resume_set (the 48-byte record) keeps refusing the image (capi.hip).  The lane
-// kernel (nfa_set.hip) stays the default for every image it can walk.
+// string (mfa_set_state_wide) read before the piece and written behind it.  mfa_match_batch_resume_set (the 48-byte record) keeps
+// refusing the image (capi.hip).  The lane kernel (nfa_set.hip) stays the default for every image it can walk.
+// A long string, or a long piece that enters with a live set, is cut across the whole GPU by nfa_set_wave_split.hip, behind the main
+// kernel of this file: the wave that holds it hands it over (split_take, dfa_split.h: the one hand-over, no string is lost).
 #include <hip/hip_runtime.h>
 
-#include "nfa_set.h"
-#include "nfa_set_wave_core.h"
+#include "nfa_set_wave.h"
+#include "nfa_set_wave_split_core.h"
 
 namespace mfa {
 
+// What a wave does with a string it may hand to nfa_set_wave_split.hip: lane 0 asks for the queue slot, the answer is made wave-uniform.
+// true: the string is queued, its result (and record) are nfa_set_wave_resolve_kernel's.
+static __device__ __forceinline__ bool wave_split_take(const SplitArgs& sp, uint64_t sid) {
+    uint32_t taken = 0u;
+    if (WaveDev::lane() == 0u) taken = split_take(sp, sid) ? 1u : 0u;
+    return WaveDev::uni(taken) != 0u;
+}
+
 // IN_LDS: the tables' sections are read from their copy behind the stacks (LDS), else from global memory; a template parameter, so that
-// the compiler knows the address space of every table read.
+// the compiler knows the address space of every table read.  sp.split_min == 0: the queue is off and every string is walked here, as
+// before that path existed.
 template <bool REV, bool IN_LDS>
 __global__ void __launch_bounds__(256)
 nfa_set_wave_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t depth, const uint8_t* __restrict__ bytes,
-                    const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results) {
+                    const uint64_t* __restrict__ offsets, uint64_t n, uint8_t* __restrict__ results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     const uint32_t wave = WaveDev::uni(threadIdx.x >> 6);
     uint32_t* stack = lds + wave * depth;                              // slot s of this wave: stack[s]
@@ -38,6 +48,7 @@ nfa_set_wave_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, u
     const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
     for (uint64_t sid = (uint64_t)blockIdx.x * 4u + wave; sid < n; sid += n_waves) {
         const uint64_t b = offsets[sid], e = offsets[sid + 1];
+        if (sp.split_min != 0u && e - b >= sp.split_min && e - b <= kSetMaxString && wave_split_take(sp, sid)) continue;      // ({start} is never empty)
         const uint8_t r = nfa_wave_walk<REV, WaveDev>(t, W, stack, bytes, b, e);
         if (WaveDev::lane() == 0u) results[sid] = r;
     }
@@ -45,11 +56,12 @@ nfa_set_wave_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, u
 
 // The same walk for strings in pieces: the wave's set comes from its string's record of `states` (kWaveStateWords words, 16-byte
 // aligned: a tag quarter, then lane l's word) and goes back there behind the piece (nfa_set_wave_core.h: nfa_wave_resume_piece).  A
-// record is read and written by the one wave that has its string.  results may be NULL.
+// record is read and written by the one wave that has its string.  results may be NULL.  Only a piece whose record decodes to a live,
+// non-empty set is queued: dead, invalid and over-long records are answered here, and a queued piece's record is left as it came.
 template <bool REV, bool IN_LDS>
 __global__ void __launch_bounds__(256)
 nfa_set_wave_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, uint32_t depth, const uint8_t* __restrict__ bytes,
-                           const uint64_t* __restrict__ offsets, uint64_t n, uint32_t* states, uint8_t* results) {
+                           const uint64_t* __restrict__ offsets, uint64_t n, uint32_t* states, uint8_t* results, const SplitArgs sp) {
     extern __shared__ uint32_t lds[];
     const uint32_t wave = WaveDev::uni(threadIdx.x >> 6);
     uint32_t* stack = lds + wave * depth;
@@ -65,45 +77,34 @@ nfa_set_wave_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_w
     const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
     for (uint64_t sid = (uint64_t)blockIdx.x * 4u + wave; sid < n; sid += n_waves) {
         const uint64_t b = offsets[sid], e = offsets[sid + 1];
-        const uint8_t r = nfa_wave_resume_piece<REV, WaveDev>(t, n_nodes, W, stack, bytes, b, e, states + sid * kWaveStateWords);
+        uint32_t* rec = states + sid * kWaveStateWords;
+        WaveDev::Reg cur;
+        const uint32_t tag = nfa_wave_state_decode<WaveDev>(t, n_nodes, rec, e - b, cur);
+        if (sp.split_min != 0u && e - b >= sp.split_min && tag == kSetStateLive && WaveDev::any(cur) && wave_split_take(sp, sid)) continue;
+        const uint8_t r = wave_resume_entered<REV, WaveDev>(t, W, stack, bytes, b, e, tag, cur, rec);      // (nfa_wave_resume_piece behind its decode)
         if (results && WaveDev::lane() == 0u) results[sid] = r;
     }
 }
 
-// what a block takes of LDS: the four stacks and, when both fit kSetLdsMax, the tables behind them
-struct WaveLds { uint32_t words, depth, in_lds; size_t bytes; };
-
-static WaveLds wave_lds_of(const HostImage& img) {
-    WaveLds l;
-    l.words = (uint32_t)img.set_tables.size(); l.depth = img.set_tables[SET_H_DEPTH];
-    l.in_lds = ((size_t)4u * l.depth + l.words) * 4u <= kSetLdsMax ? 1u : 0u;
-    l.bytes = ((size_t)4u * l.depth + (l.in_lds ? l.words : 0u)) * 4u;
-    return l;
-}
-static_assert((size_t)4u * kWaveMaxNodes * 4u <= kSetLdsMax, "the stacks alone fit (a chain is never longer than the image has nodes)");
-
+// Behind either main kernel, the kernels of nfa_set_wave_split.hip for the strings it queued (set_wave_split_begin, set_wave_split_tail);
+// ev_start and ev_stop enclose all of it.
 template <bool REV, bool IN_LDS>
 static int launch_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                        uint8_t* d_results, hipStream_t s) {
     uint64_t blocks = (n + 3) / 4, cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    const int rc = set_allow_lds<nfa_set_wave_kernel<REV, IN_LDS>>(ds.device);
+    int rc = set_allow_lds<nfa_set_wave_kernel<REV, IN_LDS>>(ds.device);
     if (rc != MFA_OK) return rc;
-    // no string is queued for the split path: its flags stay as ctx_acquire left them, mfa_last_set_split answers zeros
+    SplitLaunch sl;
+    if ((rc = set_wave_split_begin(img, cx, n, s, &sl)) != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
     hipLaunchKernelGGL((nfa_set_wave_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.depth, d_bytes,
-                       d_offsets, n, d_results);
+                       d_offsets, n, d_results, sl.args);
     HIP_TRY(hipGetLastError());
+    if ((rc = set_wave_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, nullptr)) != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
-}
-
-// what both launches ask of the image before anything is enqueued: wave tables on the device, of a width and depth the kernels hold
-static bool wave_tables_ok(const HostImage& img, const DeviceState& ds) {
-    if (!img.set_wave || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return false;
-    const uint32_t W = img.set_tables[SET_H_WORDS];
-    return W >= 1u && W <= kWaveLanes && W == wave_words_of(img.set_tables[SET_H_NODES]) && img.set_tables[SET_H_DEPTH] <= kWaveMaxNodes;
 }
 
 int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
@@ -117,18 +118,20 @@ int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, co
 }
 
 template <bool REV, bool IN_LDS>
-static int launch_wave_resume(DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
+static int launch_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
                               uint8_t* d_results, hipStream_t s) {
     uint64_t blocks = (n + 3) / 4, cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    const int rc = set_allow_lds<nfa_set_wave_resume_kernel<REV, IN_LDS>>(ds.device);
+    int rc = set_allow_lds<nfa_set_wave_resume_kernel<REV, IN_LDS>>(ds.device);
     if (rc != MFA_OK) return rc;
-    // nothing is queued or cut: the split flags stay as ctx_acquire left them, mfa_last_set_split answers zeros
+    SplitLaunch sl;
+    if ((rc = set_wave_split_begin(img, cx, n, s, &sl)) != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
     hipLaunchKernelGGL((nfa_set_wave_resume_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.depth,
-                       d_bytes, d_offsets, n, d_states, d_results);
+                       d_bytes, d_offsets, n, d_states, d_results, sl.args);
     HIP_TRY(hipGetLastError());
+    if ((rc = set_wave_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states)) != MFA_OK) return rc;
     HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
     return MFA_OK;
 }
@@ -139,8 +142,8 @@ int launch_nfa_set_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx&
     const WaveLds l = wave_lds_of(img);
     hipStream_t s = (hipStream_t)stream;
     if (img.h.is_reversed)
-        return l.in_lds ? launch_wave_resume<true, true>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<true, false>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
-    return l.in_lds ? launch_wave_resume<false, true>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<false, false>(ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
+        return l.in_lds ? launch_wave_resume<true, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<true, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
+    return l.in_lds ? launch_wave_resume<false, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<false, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
 }
 
 }  // namespace mfa

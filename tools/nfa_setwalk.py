@@ -23,6 +23,14 @@ One JSON line per comparison, also appended to profiles/r11_nfa_setwalk.jsonl.
               takes seconds per call)
       short   1 Mi x 1 KiB (no long string): this build's kernel time per call, to be set against another build's (MFA_LIB_PATH) process by process
 
+  nfa_setwalk.py long sweep|gain|short REPS OUT.jsonl wave [first] [mib]   the same three for WAVE images (csrc/nfa_set_wave_split.hip), on the
+      (a|b)*a(a|b)^k Thompson images of 259 and 1029 nodes (`first`: the 259-node image only); OUT.jsonl is profiles/r16_nfa_set_wave_split.jsonl
+      in DESIGN.md
+      sweep   8 x 1 MiB: MFA_DFA_CHUNK 256 .. 4096 x MFA_SET_SPLIT_LOOKBACK 32 .. 256 (or those of `lb=64,128,256`) x MFA_SET_SPLIT_ROUNDS 0, 3
+      gain    8 x 128 KiB with the library's defaults against MFA_SET_SPLIT=0 (one uncounted call and three counted ones); `mib`: also
+              8 x 1 MiB cut (walked whole it takes about a minute of the device per call: not run)
+      short   64 Ki x 1 KiB on the 259-node image
+
   nfa_setwalk.py wave narrow|wide|resume [REPS] [STRINGS] [OUT.jsonl] [first]   the wave-cooperative step (csrc/nfa_set_wave.hip: one string per wave), lines appended
       to OUT.jsonl (default profiles/r14_nfa_set_wave.jsonl).  Medians of REPS calls (default 7) after five uncounted ones, the sides
       alternating; the first strings' answers are held to the CPU restatement.
@@ -187,11 +195,58 @@ def long_measure(what, img, blob, flat, d_off, reps, warm, env, out_path):
     return med
 
 
+def wide_images(first_only=False):
+    """[(name, image, blob)]: the (a|b)*a(a|b)^k Thompson images of 259 and 1029 nodes (`wave wide` has them too), wave images by themselves"""
+    out = []
+    for lo, hi in ((256, 512), (1024, 2048))[:1 if first_only else 2]:
+        k = (lo - 9) // 5 + 1                                    # the Thompson compile has 5 k + 9 nodes
+        blob = front_end("(a|b)*a" + "(a|b)" * k, "-thompson")
+        img, _ = created(blob, "1")
+        assert lo < img.info()["n_nodes"] <= hi and img.info()["dfa_states"] == 0 and img.resume_state_bytes() == 4 * capi.SET_STATE_WIDE_WORDS
+        out.append(("(a|b)*a(a|b)^%d Thompson, %d nodes" % (k, img.info()["n_nodes"]), img, blob))
+    return out
+
+
+def long_wave_main(mode, reps, out_path):
+    """the wave forms of sweep, gain and short (csrc/nfa_set_wave_split.hip); `first` among the arguments: the 259-node image only"""
+    images = wide_images("first" in sys.argv[5:] or mode == "short")
+    if mode == "short":
+        flat, d_off, _ = batch([1024] * (1 << 16), 2)
+        for name, img, blob in images:
+            long_measure("64 Ki x 1 KiB, " + name, img, blob, flat, d_off, reps, 5, {}, out_path)
+        return
+    if mode == "gain":
+        # 8 x 128 KiB: a whole call is seconds.  (8 x 1 MiB walked whole is about a minute of the device per call: cut only, `mib`)
+        small = batch([128 << 10] * 8, 7)
+        for name, img, blob in images:
+            cut = long_measure("8 x 128 KiB, cut (defaults), " + name, img, blob, small[0], small[1], reps, 5, {}, out_path)
+            whole = long_measure("8 x 128 KiB, walked whole, " + name, img, blob, small[0], small[1], 3, 1, {"MFA_SET_SPLIT": 0}, out_path)
+            print(json.dumps({"what": "gain, " + name, "whole_over_cut": whole / cut}), flush=True)
+        if "mib" in sys.argv[5:]:
+            mib = batch([1 << 20] * 8, 5)
+            for name, img, blob in images:
+                long_measure("8 x 1 MiB, cut (defaults), " + name, img, blob, mib[0], mib[1], reps, 5, {}, out_path)
+        return
+    mib = batch([1 << 20] * 8, 5)
+    # a lookback shorter than the image's memory (k + 1 = 51 and 205 bytes) guesses wrong at every chunk and leaves every string to the
+    # serial walk, most of a minute per call: `lb=64,128,256` among the arguments names the lookbacks to sweep
+    lookbacks = next(([int(x) for x in a[3:].split(",")] for a in sys.argv[5:] if a.startswith("lb=")), [32, 64, 128, 256])
+    for name, img, blob in images:
+        for chunk in (256, 512, 1024, 2048, 4096):
+            for lookback in lookbacks:
+                for rounds in (0, 3):
+                    long_measure("8 x 1 MiB, " + name, img, blob, mib[0], mib[1], reps, 5,
+                                 {"MFA_DFA_CHUNK": chunk, "MFA_SET_SPLIT_LOOKBACK": lookback, "MFA_SET_SPLIT_ROUNDS": rounds}, out_path)
+
+
 def long_main():
     mode = sys.argv[2] if len(sys.argv) > 2 else "sweep"
     reps = max(3, int(sys.argv[3])) if len(sys.argv) > 3 else 7
-    out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "r13_nfa_set_split.jsonl")
+    wave = "wave" in sys.argv[5:]
+    out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "r16_nfa_set_wave_split.jsonl" if wave else "r13_nfa_set_split.jsonl")
     assert mode in ("sweep", "gain", "short")
+    if wave:
+        return long_wave_main(mode, reps, out_path)
     abb = image.blob_from_dump(oracle_lib.load_dump("nfa_abb_thompson"))
     images = [("(a|b)*abb forced to the set walk (W = 1)", created(abb, "1")[0], abb)]
     if mode != "short" or "k20" in sys.argv:

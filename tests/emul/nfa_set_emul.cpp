@@ -8,6 +8,10 @@
 //       stdout: "ok STATES CLASSES W DEPTH"; a difference is exit code 5.
 //   nfa_set_emul match IMAGE.blob BATCH.bin
 //       BATCH.bin: u64 n, u64 offsets[n + 1], then offsets[n] bytes.  stdout: one result digit per string, then a newline.
+//   nfa_set_emul table IMAGE.blob
+//       stdout: "tables WORDS W DEPTH CLASSES" -- the words of the lane tables, their mask width, their stack depth and byte classes: what
+//       set_lds_of (csrc/nfa_set.h) places them by, (DEPTH * 256 + WORDS) * 4 against 65536.
+//   Exit code 3: the image gets no set-walk tables.
 #include <string>
 
 #include "emul_common.h"
@@ -62,7 +66,7 @@ static int run_match(const HostImage& set, const std::vector<uint8_t>& file) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { fprintf(stderr, "usage: nfa_set_emul step IMAGE.blob | match IMAGE.blob BATCH.bin\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: nfa_set_emul step IMAGE.blob | match IMAGE.blob BATCH.bin | table IMAGE.blob\n"); return 2; }
     const std::string mode = argv[1];
     const std::vector<uint8_t> blob = emul::slurp(argv[2]);
     HostImage tab, set;
@@ -72,6 +76,10 @@ int main(int argc, char** argv) {
     if (rc != MFA_OK) { fprintf(stderr, "no set-walk tables: %d\n", rc); return 3; }
     const uint32_t W = set.set_tables[SET_H_WORDS];
     const bool rev = set.h.is_reversed != 0;
+    if (mode == "table") {
+        printf("tables %zu %u %u %u\n", set.set_tables.size(), W, set.set_tables[SET_H_DEPTH], set.set_tables[SET_H_CLASSES]);
+        return 0;
+    }
 #define BY_W(CALL1, CALL2, CALL4, CALL8) (W == 1 ? CALL1 : W == 2 ? CALL2 : W == 4 ? CALL4 : CALL8)
     if (mode == "step") {
         std::vector<std::string> sets;

@@ -10,7 +10,10 @@ step() and accepts() restate that step in plain Python on a rank-numbered edge l
 own beside image_host.cpp (Stepper), nfa_set_core.h and oracle/mfa_oracle.c.
 
 corpus(seed) draws until every line of LINES holds an image per scan direction; an image is kept only if the oracle answers 1 on 10-90 % of
-its strings -- a filter on the reference alone.  What the library refuses is counted, never hidden."""
+its strings -- a filter on the reference alone.  What the library refuses is counted, never hidden.
+
+set_corpus(seed) is the corpus for the tests that walk EVERY image as a node set: the same images, and the direction twin of each whose
+lane tables lie beyond LDS (set_placement, from `nfa_set_emul table`), so that both placements are walked in both directions."""
 import os
 import random
 import subprocess
@@ -436,6 +439,89 @@ def cpu_corpus(seed):
 def gpu_corpus():
     """the one corpus of the GPU tests: seed 0, made once per session"""
     return corpus(0)
+
+
+# ---- the corpus of the set walk: every image, and both table placements in both directions -----------------------------------------------
+SET_LDS_BYTES = 65536                                   # kSetLdsMax (csrc/nfa_set.h)
+_tables, _set_corpora = {}, {}
+
+
+def direction_twin(im):
+    """the same automaton scanning the other way, on the same strings mirrored: an entry like corpus()'s, its info probed anew and its
+    answers asked of the oracle anew (they are the original's when the oracle is right: check_set_lines)"""
+    d = dict(im["dict"], reversed=0 if im["dict"]["reversed"] else 1)
+    blob = image.to_blob(d)
+    info = probe(blob)
+    assert info is not None and info["is_reversed"] == d["reversed"], im["what"]
+    strings = [s[::-1] for s in im["strings"]]
+    want = np.asarray(oracle_lib.OracleImage(blob).match(strings)).copy()
+    want.setflags(write=False)
+    return dict(im, what=im["what"] + ", direction flipped", dict=d, blob=blob, info=info, strings=strings, want=want, twin_of=im)
+
+
+def set_tables(im):
+    """(WORDS, W, DEPTH, CLASSES) of the image's lane tables, from `nfa_set_emul table`; None: the image gets no set-walk tables"""
+    if im["blob"] not in _tables:
+        with tempfile.TemporaryDirectory(prefix="nfa_fuzz_") as folder:
+            path = os.path.join(folder, "a.blob")
+            with open(path, "wb") as f:
+                f.write(im["blob"])
+            p = subprocess.run([testlib.emul_exe("nfa_set"), "table", path], capture_output=True)
+        assert p.returncode in (0, 3), p.stderr.decode()[-400:]
+        f = p.stdout.split()
+        assert p.returncode == 3 or (f[0] == b"tables" and len(f) == 5), p.stdout
+        _tables[im["blob"]] = None if p.returncode == 3 else tuple(int(x) for x in f[1:])
+    return _tables[im["blob"]]
+
+
+def set_placement(im):
+    """"lds" or "l2": where the lane kernels read the image's tables, by set_lds_of's rule (csrc/nfa_set.h) on the harness's figures: the
+    256 stacks and the tables fit 64 KiB, or the tables are read through L2; None: no set-walk tables"""
+    t = set_tables(im)
+    if t is None:
+        return None
+    words, _, depth, _ = t
+    return "lds" if (depth * 256 + words) * 4 <= SET_LDS_BYTES else "l2"
+
+
+def set_corpus(seed):
+    """corpus(seed), unchanged and in its order, and behind it the direction twin of every image whose tables lie beyond LDS: such images
+    are rare, and the draws need not find one per direction.  A list, made once per seed."""
+    if seed not in _set_corpora:
+        c = list(corpus(seed))
+        _set_corpora[seed] = c + [direction_twin(im) for im in c if set_placement(im) == "l2"]
+    return _set_corpora[seed]
+
+
+def set_id(k, im):
+    """the test id of image k of a set corpus: mask width, direction, placement"""
+    return "%d-W%d-%s-%s" % (k, mask_words(im["info"]), "rev" if im["info"]["is_reversed"] else "fwd", set_placement(im))
+
+
+def check_set_lines(c):
+    """a set corpus is what the set-walk tests count on -- from the harness's table figures and the oracle alone: an image per mask width
+    and direction, and per direction one with tables in LDS and one with tables through L2.  A seed without an image beyond LDS fails."""
+    have = {(mask_words(im["info"]), im["info"]["is_reversed"], set_placement(im)) for im in c}
+    assert all(p is not None for _, _, p in have), "an image without set-walk tables"
+    for w in (1, 2, 4, 8):
+        for rev in (0, 1):
+            assert any(h[:2] == (w, rev) for h in have), "no image of %d mask words, reversed %d" % (w, rev)
+    for rev in (0, 1):
+        for place in ("l2", "lds"):
+            assert any(h[1:] == (rev, place) for h in have), "no image with tables in %s, reversed %d: %r" % (place, rev, sorted(have))
+    for im in c:
+        t = set_tables(im)
+        assert t[1] == mask_words(im["info"]) and t[3] == im["info"]["byte_classes"], (im["what"], t)
+        if "twin_of" in im:
+            assert np.array_equal(im["want"], im["twin_of"]["want"]), im["what"]
+            assert len(im["strings"]) % 64 != 0 and [len(s) for s in im["strings"]] == [len(s) for s in im["twin_of"]["strings"]]
+
+
+def report_set(c, seed):
+    print("nfa fuzz seed %d, set corpus: %d images" % (seed, len(c)))
+    for k, im in enumerate(c):
+        if set_placement(im) == "l2":
+            print("  tables through L2: %s -- %d words, W %d, depth %d, %d classes (%s)" % ((set_id(k, im),) + set_tables(im) + (im["what"],)))
 
 
 def report(c, seed):

@@ -44,12 +44,17 @@ def split_emul_exe(flags=""):
 KEYS = ("W", "checks", "rewalked", "serial_strings", "serial_bytes", "home_nodes", "home_guesses")
 
 
-def run_split(exe, tmp_path, blob, strings, chunks, lookbacks, rounds, mode="one"):
-    """the harness on every combination of the three lists, chunks outermost: a list of ((chunk, lookback, rounds), counts, result digits)"""
+def run_split(exe, tmp_path, blob, strings, chunks, lookbacks, rounds, mode="one", run=None):
+    """the harness on every combination of the three lists, chunks outermost: a list of ((chunk, lookback, rounds), counts, result digits).
+    run: what runs the command line instead of subprocess.run -- it returns the finished process, or None for "refused", which is
+    returned as it is"""
     (tmp_path / "a.blob").write_bytes(blob)
     write_batch(tmp_path / "batch.bin", strings)
     as_list = lambda v: ",".join(str(x) for x in v)
-    p = subprocess.run([exe, str(tmp_path / "a.blob"), str(tmp_path / "batch.bin"), as_list(chunks), as_list(lookbacks), as_list(rounds), mode], capture_output=True)
+    cmd = [exe, str(tmp_path / "a.blob"), str(tmp_path / "batch.bin"), as_list(chunks), as_list(lookbacks), as_list(rounds), mode]
+    p = subprocess.run(cmd, capture_output=True) if run is None else run(cmd)
+    if p is None:
+        return None
     assert p.returncode == 0, p.stderr.decode()[-600:]
     lines = p.stdout.split(b"\n")
     combos = [(c, lb, r) for c in chunks for lb in lookbacks for r in rounds]

@@ -56,11 +56,15 @@ def run_step(exe, tmp_path, blob):
     return tuple(int(x) for x in f[1:])
 
 
-def run_match(exe, tmp_path, blob, strings):
-    """the harness's `match` mode: one result byte per string"""
+def run_match(exe, tmp_path, blob, strings, run=None):
+    """the harness's `match` mode: one result byte per string.  run: what runs the command line instead of subprocess.run -- it returns
+    the finished process, or None for "refused", which is returned as it is"""
     (tmp_path / "a.blob").write_bytes(blob)
     write_batch(tmp_path / "batch.bin", strings)
-    p = subprocess.run([exe, "match", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin")], capture_output=True)
+    cmd = [exe, "match", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin")]
+    p = subprocess.run(cmd, capture_output=True) if run is None else run(cmd)
+    if p is None:
+        return None
     assert p.returncode == 0, p.stderr.decode()[-600:]
     return np.frombuffer(p.stdout.strip(), dtype=np.uint8) - ord("0")
 

@@ -41,14 +41,18 @@ KEYS = ("W", "checks", "rewalked", "serial_strings", "serial_bytes", "home_nodes
 COUNT_KEYS = ("rewalked", "serial_strings", "serial_bytes")
 
 
-def run_wave_split(exe, tmp_path, blob, strings, chunks, lookbacks, rounds, depth=None):
+def run_wave_split(exe, tmp_path, blob, strings, chunks, lookbacks, rounds, depth=None, run=None):
     """the harness's `split` mode on every combination of the three lists, chunks outermost: a list of ((chunk, lookback, rounds), counts,
-    result digits).  depth: the stacks' slots, instead of the tables' own"""
+    result digits).  depth: the stacks' slots, instead of the tables' own.  run: what runs the command line instead of subprocess.run --
+    it returns the finished process, or None for "refused", which is returned as it is"""
     (tmp_path / "a.blob").write_bytes(blob)
     write_batch(tmp_path / "batch.bin", strings)
     as_list = lambda v: ",".join(str(x) for x in v)
     cmd = [exe, "split", str(tmp_path / "a.blob"), str(tmp_path / "batch.bin"), as_list(chunks), as_list(lookbacks), as_list(rounds)]
-    p = subprocess.run(cmd + ([str(depth)] if depth is not None else []), capture_output=True)
+    cmd += [str(depth)] if depth is not None else []
+    p = subprocess.run(cmd, capture_output=True) if run is None else run(cmd)
+    if p is None:
+        return None
     assert p.returncode == 0, p.stderr.decode()[-600:]
     lines = p.stdout.split(b"\n")
     combos = [(c, lb, r) for c in chunks for lb in lookbacks for r in rounds]

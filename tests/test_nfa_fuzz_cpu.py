@@ -1,7 +1,8 @@
 """The memory-less engines' host-compilable cores on automata nobody has seen before (tests/nfa_fuzz.py: raw random automata with up to 200
 byte classes, labels of 0x80 and above, letter edges to lower ranks, and random regexes through every compile of the host front-end), all
 against the CPU restatement: the reference's step restated in Python, the set walk's mask step against the table from every state set and
-class, the split path, the resume call's pieces and folds, the L2 table's guesses, the multi-table item walk and the set walk's records.
+class, the split path, the resume call's pieces and folds, the L2 table's guesses, the multi-table item walk and the set walk's records,
+and on every image of nfa_fuzz.set_corpus the set walk's split path from {start} and from every tabulated set and the wave kernels' cores.
 What a corpus must hold -- every packed NLIT, every table size that chooses a kernel, every mask width, both scan directions -- is
 asserted from info() and the oracle alone, not hoped for.  MFA_FUZZ_SEEDS=n: n more seeds (MFA_FUZZ_FIRST=k: seeds k .. k + n).  The
 kernels around the cores are checked by tests/test_nfa_fuzz_gpu.py on the corpus of seed 0."""
@@ -15,6 +16,9 @@ import pytest
 import nfa_fuzz
 import oracle_lib
 import setresume_lib
+import setsplit_lib
+import setwave_lib
+import setwavesplit_lib
 from mfa_amd import capi
 from test_dfa_resume_cpu import run_pieces
 from test_dfa_spec_cpu import run_emul as run_spec
@@ -202,6 +206,98 @@ def test_set_resume_core(seed, tmp_path):
             differ(whole_digits[0], im, "nfa_set_resume_emul whole")
             assert np.array_equal(recs, whole_recs), im["what"]
             setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+
+
+# ---- the set walk's split, resume and wave cores: every image of the set corpus -------------------------------------------------------------
+SPLIT_CHUNKS, SPLIT_LOOKBACKS, SPLIT_ROUNDS = (16, 48), (0, 8, 64), (0, 1, 3)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_the_set_corpus_is_what_the_tests_count_on(seed):
+    c = nfa_fuzz.set_corpus(seed)
+    nfa_fuzz.report_set(c, seed)
+    nfa_fuzz.check_set_lines(c)
+    base = nfa_fuzz.cpu_corpus(seed)
+    assert len(c) > len(base) and all(a is b for a, b in zip(c, base)) and all("twin_of" in im for im in c[len(base):])
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_set_split_core(seed, tmp_path):
+    """nfa_set_split_emul from {start} on every image of the set corpus, every string cut, in all 18 combinations of chunks of 16 and 48
+    bytes, lookbacks of 0, 8 and 64 bytes and 0, 1 and 3 repair rounds: the harness holds every final record to the whole walk's, word
+    for word, and its result digits are the oracle's.  Random automata converge late, never, or at once, so at (16, 64, 3) at least a
+    third of the images have chunks walked again, a third have strings resolved serially and a third have chunks whose guess fell back
+    to the home set; without a byte of lookback or a repair, at either chunk size, every image has strings resolved serially -- but one
+    whose table has two state sets, the empty set and {start}: its only live set is {start}, which no guess can miss (seed 3 draws one:
+    two nodes, an epsilon edge from the start and one letter edge back to it).
+    Measured, each seed 36 images (34 and the direction twins of those beyond LDS), images with chunks walked again / strings resolved
+    serially / home guesses at (16, 64, 3): seed 0: 31, 29, 28; seed 1: 27, 25, 30; seed 2: 28, 24, 25; seed 3: 28, 25, 27.  Tables beyond LDS, in words: seed 0: 30 237 (W 4, 119 classes) and 188 546 (W 8, 201
+    classes); seed 1: 29 699 and 190 144; seed 2: 38 123 and 186 916; seed 3: 172 437.  No run refused."""
+    emul = setsplit_lib.split_emul_exe()
+    c = nfa_fuzz.set_corpus(seed)
+    done = rewalked = serial = home = 0
+    for im in c:
+        runs = setsplit_lib.run_split(emul, tmp_path, im["blob"], im["strings"], SPLIT_CHUNKS, SPLIT_LOOKBACKS, SPLIT_ROUNDS, run=harness)
+        if runs is None:
+            continue
+        done += 1
+        assert len(runs) == 18
+        for combo, counts, digits in runs:
+            assert counts["W"] == nfa_fuzz.mask_words(im["info"]) and counts["checks"] == len(im["strings"]), (im["what"], combo)
+            differ(digits, im, "nfa_set_split_emul one, chunk %d lookback %d rounds %d" % combo)
+            if combo == (16, 64, 3):
+                rewalked += counts["rewalked"] > 0
+                serial += counts["serial_strings"] > 0
+                home += counts["home_guesses"] > 0
+            if combo[1:] == (0, 0):
+                assert (counts["serial_strings"] > 0 or states(im) == 2) and counts["rewalked"] == 0, (im["what"], combo, counts)
+    print("nfa_set_split_emul seed %d: %d images of %d; at (16, 64, 3) %d with chunks walked again, %d with strings resolved serially, %d with home guesses"
+          % (seed, done, len(c), rewalked, serial, home))
+    assert 3 * rewalked >= len(c) and 3 * serial >= len(c) and 3 * home >= len(c)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_set_split_core_from_every_set(seed, tmp_path):
+    """the resume form: nfa_set_split_emul `every` on the images of 2 to 60 state sets -- every string from {start}, from every tabulated
+    node set and from the empty set, every final record held to the whole walk's from the same set -- at (16, 64, 3) and (48, 0, 0).
+    Measured: seed 0, 24 images and 69 233 records per setting; seed 1, 24 and 59 153; seed 2, 25 and 72 500; seed 3, 22 and 37 950."""
+    emul = setsplit_lib.split_emul_exe()
+    done = checks = 0
+    for im in nfa_fuzz.set_corpus(seed):
+        if not 2 <= states(im) <= 60:
+            continue
+        for combo in ((16, 64, 3), (48, 0, 0)):
+            runs = setsplit_lib.run_split(emul, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], mode="every", run=harness)
+            if runs is None:
+                continue
+            (_, counts, digits), = runs
+            assert counts["checks"] == (states(im) + 1) * len(im["strings"]), im["what"]      # {start}, and the table's sets with the empty one
+            differ(digits, im, "nfa_set_split_emul every, chunk %d lookback %d rounds %d" % combo)
+            checks += counts["checks"] if combo[0] == 16 else 0
+        done += 1
+    print("nfa_set_split_emul every, seed %d: %d images, %d records per setting" % (seed, done, checks))
+    assert done >= 10
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_set_wave_cores(seed, tmp_path):
+    """the wave kernels' cores on images they were not made for -- up to 200 byte classes, labels of 0x80 and above, 2 to 130 nodes:
+    nfa_set_wave_emul match on every image of the set corpus, nfa_set_wave_split_emul (every string cut, every record held to the whole
+    walk's) at (16, 64, 3) and (48, 0, 0), all against the oracle.  Measured: seeds 0 to 3, 36 images each, none refused."""
+    wave, split = setwave_lib.wave_emul_exe(), setwavesplit_lib.wave_split_emul_exe()
+    done = 0
+    for im in nfa_fuzz.set_corpus(seed):
+        got = setwave_lib.run_match(wave, tmp_path, im["blob"], im["strings"], run=harness)
+        if got is not None:
+            differ(got, im, "nfa_set_wave_emul match")
+            done += 1
+        for combo in ((16, 64, 3), (48, 0, 0)):
+            runs = setwavesplit_lib.run_wave_split(split, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], run=harness)
+            if runs is not None:
+                (_, counts, digits), = runs
+                assert counts["checks"] == len(im["strings"]) and counts["W"] == setwave_lib.words_of(im["info"]["n_nodes"]), (im["what"], combo, counts)
+                differ(digits, im, "nfa_set_wave_split_emul, chunk %d lookback %d rounds %d" % combo)
+    print("wave harnesses seed %d: %d images" % (seed, done))
 
 
 def test_refusals_stay_under_the_cap():

@@ -5,12 +5,19 @@ NLIT selects of the SGPR-packed kernel, a table reload between automata with dif
 One fixed corpus (tests/nfa_fuzz.py: gpu_corpus, seed 0): raw random automata with labels from all bytes but '.', letter edges to lower
 ranks and 2 to 130 nodes, and regex-derived ones, with about 240 strings each sampled from the automaton itself, 16 of them pumped to 256 -
 3 000 bytes and starting at every offset mod 16.  Every batch has a length that is no multiple of 64, is uploaded with exactly the room
-the 16-byte read rule asks for, and is answered into a buffer prefilled with 7 with 64 guard bytes behind it.  Every comparison is exact."""
+the 16-byte read rule asks for, and is answered into a buffer prefilled with 7 with 64 guard bytes behind it.  Every comparison is exact.
+
+The set walk (section d) takes every image of nfa_fuzz.set_corpus(0), forced to the node set: the lane kernels whole, in pieces, with
+long strings cut (plain and RESUME form of csrc/nfa_set_split.hip) and the wave kernels under MFA_SET_WAVE=1 -- every mask width in both
+directions, and tables in LDS and through L2 in both directions; the test ids say which."""
 import numpy as np
 import pytest
 
 import nfa_fuzz
 import setresume_lib
+import setsplit_lib
+import setwaveresume_lib
+import setwavesplit_lib
 import testlib
 from mfa_amd import capi
 from test_dfa_spec_gpu import prime
@@ -20,7 +27,7 @@ from testlib import ROUNDS, cuts_for, expected_split, feed, new_states, pieces_a
 pytestmark = pytest.mark.gpu
 
 KNOBS = ("MFA_DFA_KERNEL", "MFA_DFA_SPLIT_MIN", "MFA_DFA_CHUNK", "MFA_DFA_SPLIT", "MFA_DFA_SPEC", "MFA_NFA_SETWALK", "MFA_DFA_STATE_LIMIT", "MFA_MIXED_DFA",
-         "MFA_MIXED_DFA_OWN", "MFA_WALK")
+         "MFA_MIXED_DFA_OWN", "MFA_WALK", "MFA_SET_WAVE", "MFA_SET_SPLIT", "MFA_SET_SPLIT_ROUNDS", "MFA_SET_SPLIT_LOOKBACK")
 
 
 @pytest.fixture()
@@ -86,6 +93,8 @@ def test_the_corpus_is_what_the_tests_count_on():
     c = corpus()
     nfa_fuzz.report(c, 0)
     nfa_fuzz.check_lines(c)
+    nfa_fuzz.report_set(set_corpus(), 0)
+    nfa_fuzz.check_set_lines(set_corpus())
     assert GUARD == 64
 
 
@@ -175,15 +184,22 @@ def test_resume(k, im, env):
 
 
 # ---- d. the set walk ------------------------------------------------------------------------------------------------------------------------
-def setwalk_images():
-    return [next((k, im) for k, im in enumerate(corpus()) if nfa_fuzz.mask_words(im["info"]) == w and im["info"]["is_reversed"] == rev)
-            for w in (1, 2, 4, 8) for rev in (0, 1)]
+def set_corpus():
+    return nfa_fuzz.set_corpus(0)
 
 
-@pytest.mark.parametrize("k,im", setwalk_images(), ids=["%d-words-%s" % (w, d) for w in (1, 2, 4, 8) for d in ("fwd", "rev")])
+def every_set():
+    """every image of the set corpus; the id carries mask width, direction and table placement"""
+    images = list(enumerate(set_corpus()))
+    return pytest.mark.parametrize("k,im", images, ids=[nfa_fuzz.set_id(k, im) for k, im in images])
+
+
+@every_set()
 def test_set_walk(k, im, env):
-    """MFA_NFA_SETWALK=1 on one image per mask width and direction: the whole call, and mfa_match_batch_resume_set in ROUNDS rounds --
-    the last round's answers and the records against one call on the whole strings"""
+    """MFA_NFA_SETWALK=1 on every image of the set corpus, so on every mask width in both directions with the tables in LDS, and on W 4
+    and W 8 in both directions with the tables read through L2 (30 237 and 188 546 table words; the forward ones are direction twins):
+    the whole call, and mfa_match_batch_resume_set in ROUNDS rounds -- the last round's answers and the records against one call on the
+    whole strings"""
     img = forced(im, env)
     strings, n = im["strings"], len(im["strings"])
     d_bytes, d_off, _ = upload(strings)
@@ -200,6 +216,158 @@ def test_set_walk(k, im, env):
     assert np.array_equal(recs, setresume_lib.records_of(d_whole, n))
     setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
     assert img.info()["last_kernel"] == capi.KERNEL_NODESET
+    img.close()
+
+
+SPLIT_MIN = 256                                          # MFA_DFA_SPLIT_MIN of the tests below: the corpus's pumped strings are cut
+ZEROS = (0, 0, 0, 0, 0, 0)
+WAVE_ARENA = 32768                                       # the most chunks a wave image's workspace reserves (nfa_set_wave_split_core.h)
+
+
+def long_only(im):
+    """the image's strings of SPLIT_MIN bytes and more, and the oracle's answers for them: a batch the host harnesses of the split paths
+    cut exactly as the kernels do (they cut every string)"""
+    keep = [j for j, s in enumerate(im["strings"]) if len(s) >= SPLIT_MIN]
+    assert len(keep) >= 16 and len(keep) % 64 != 0
+    return [im["strings"][j] for j in keep], im["want"][keep]
+
+
+def compare_long(got, want, strings, im, what):
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "%s, %s: %d of %d long strings wrong, first (len %d) want %d got %d" % (im["what"], what, bad.size, len(strings), len(strings[bad[0]]), want[bad[0]], got[bad[0]])
+
+
+@pytest.mark.parametrize("chunk", [16, 48])
+@every_set()
+def test_set_split(k, im, chunk, env, tmp_path):
+    """MFA_DFA_SPLIT_MIN=256 and chunks of 16 or 48 bytes on every image forced to the set walk: nfa_set_kernel queues the batch's pumped
+    strings, which start at every offset mod 16, and csrc/nfa_set_split.hip cuts them -- the oracle's answers, the header's formulas in
+    mfa_last_set_split, zeros in mfa_last_dfa_split and mfa_last_dfa_spec; MFA_SET_SPLIT=0 answers the same bytes and reports six zeros.
+    Then the long strings alone under (rounds, lookback) of (0, 0), (3, 64) and (1, 8): the oracle's answers, and the counts of chunks
+    walked again, of strings resolved serially and of their bytes are those of the host harness on the same batch and settings.  On
+    random automata those counts run into the thousands (tests/test_nfa_fuzz_cpu.py: test_set_split_core has the figures)."""
+    env.setenv("MFA_DFA_SPLIT_MIN", str(SPLIT_MIN))
+    env.setenv("MFA_DFA_CHUNK", str(chunk))
+    img = forced(im, env)
+    d_bytes, d_off, off = upload(im["strings"])
+    n = len(im["strings"])
+    cut = expected_split(off, SPLIT_MIN, chunk)
+    assert cut[0] >= 16 and cut[2] == chunk
+    got = call(img, d_bytes, d_off, n, "chunk %d" % chunk)
+    compare(got, im, "MFA_DFA_SPLIT_MIN=256 MFA_DFA_CHUNK=%d" % chunk)
+    assert img.last_set_split()[:3] == cut
+    assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0) and img.info()["last_kernel"] == capi.KERNEL_NODESET
+    env.setenv("MFA_SET_SPLIT", "0")
+    plain = call(img, d_bytes, d_off, n, "MFA_SET_SPLIT=0")
+    assert img.last_set_split() == ZEROS and img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
+    compare(plain, im, "MFA_SET_SPLIT=0")
+    assert np.array_equal(got, plain)
+    env.delenv("MFA_SET_SPLIT")
+    longs, want = long_only(im)
+    d_bytes, d_off, off = upload(longs)
+    cut = expected_split(off, SPLIT_MIN, chunk)
+    assert cut[0] == len(longs)
+    for rounds, lookback in ((0, 0), (3, 64), (1, 8)):
+        what = "long strings only, chunk %d rounds %d lookback %d" % (chunk, rounds, lookback)
+        env.setenv("MFA_SET_SPLIT_ROUNDS", str(rounds))
+        env.setenv("MFA_SET_SPLIT_LOOKBACK", str(lookback))
+        compare_long(call(img, d_bytes, d_off, len(longs), what), want, longs, im, what)
+        report = img.last_set_split()
+        assert report[:3] == cut, (what, report)
+        (_, host, digits), = setsplit_lib.run_split(setsplit_lib.split_emul_exe(), tmp_path, im["blob"], longs, (chunk,), (lookback,), (rounds,))
+        assert np.array_equal(digits, want), what
+        assert report[3:] == (host["rewalked"], host["serial_strings"], host["serial_bytes"]), (im["what"], what, report, host)
+    img.close()
+
+
+@every_set()
+def test_set_split_in_pieces(k, im, env, tmp_path):
+    """mfa_match_batch_resume_set under MFA_DFA_SPLIT_MIN=256 and chunks of 16 bytes, the strings in ROUNDS rounds of pieces:
+    nfa_set_resume_kernel queues the long pieces of live records and the RESUME forms of csrc/nfa_set_split.hip cut them, each from the
+    set its record holds.  On odd rounds below the last every second image is given no result buffer (the resolve kernel writes the
+    record alone).  The last round's answers are the oracle's; the records are, word for word, those of one call on the whole strings
+    with MFA_SET_SPLIT=0 (the serial kernel) and those of the whole-walk host harness"""
+    env.setenv("MFA_DFA_SPLIT_MIN", str(SPLIT_MIN))
+    env.setenv("MFA_DFA_CHUNK", "16")
+    img = forced(im, env)
+    strings, n = im["strings"], len(im["strings"])
+    rounds, is_rev = setresume_lib.piece_rounds(im["blob"], strings, np.random.default_rng(3000 + k))
+    assert is_rev == im["info"]["is_reversed"]
+    d_states = setresume_lib.new_records(n)
+    queued = []
+    for r in range(ROUNDS):
+        pieces = [s[b:e] for s, (b, e) in zip(strings, rounds[r])]
+        got = setresume_lib.feed_set(img, pieces, d_states, results=not (r % 2 == 1 and r < ROUNDS - 1 and k % 2 == 1))
+        queued.append(img.last_set_split()[0])
+        assert queued[-1] <= sum(1 for p in pieces if len(p) >= SPLIT_MIN) and img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
+    compare(got, im, "split path, strings in pieces")
+    assert max(queued) > 0, queued
+    recs = setresume_lib.records_of(d_states, n)
+    env.setenv("MFA_SET_SPLIT", "0")
+    d_whole = setresume_lib.new_records(n)
+    compare(setresume_lib.feed_set(img, strings, d_whole), im, "MFA_SET_SPLIT=0, whole strings through the resume call")
+    assert img.last_set_split() == ZEROS
+    assert np.array_equal(recs, setresume_lib.records_of(d_whole, n))
+    digits, recs_host = setresume_lib.run_pieces(setresume_lib.resume_emul_exe(), tmp_path, im["blob"], strings, setresume_lib.whole(strings))
+    assert np.array_equal(digits[0], im["want"]) and np.array_equal(recs, recs_host)
+    setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+    assert img.info()["last_kernel"] == capi.KERNEL_NODESET
+    img.close()
+
+
+def forced_wave(im, env):
+    env.setenv("MFA_SET_WAVE", "1")
+    img = forced(im, env)
+    env.delenv("MFA_SET_WAVE")
+    assert img.resume_state_bytes() == 4 * setwaveresume_lib.WORDS
+    return img
+
+
+@every_set()
+def test_wave_kernels_on_the_corpus(k, im, env, tmp_path):
+    """MFA_SET_WAVE=1: the wave kernels (csrc/nfa_set_wave*.hip) on images of 2 to 130 nodes, up to 201 byte classes and labels of 0x80
+    and above -- they were made for 257 nodes and more and had met six labels.  The plain call: the oracle's answers, byte for byte the
+    lane image's.  mfa_match_batch_resume_set_wide in three rounds of pieces: the last round against the oracle, the wide records
+    (guard quarters round them) against one call on the whole strings.  MFA_DFA_SPLIT_MIN=256 and chunks of 48 bytes: the oracle's
+    answers, the header's formulas with the wave arena of 32 768 chunks, and on the long strings alone at 3 rounds and a lookback of 64
+    the counts of the host harness"""
+    lane, img = forced(im, env), forced_wave(im, env)
+    assert lane.resume_state_bytes() == 4 * setresume_lib.WORDS
+    strings, n = im["strings"], len(im["strings"])
+    d_bytes, d_off, off = upload(strings)
+    got = call(img, d_bytes, d_off, n, "wave")
+    compare(got, im, "MFA_SET_WAVE=1")
+    assert np.array_equal(got, call(lane, d_bytes, d_off, n, "lane")) and img.last_set_split() == ZEROS and img.info()["last_kernel"] == capi.KERNEL_NODESET
+    lane.close()
+    # strings in pieces
+    rounds, is_rev = setwaveresume_lib.three_rounds(im["blob"], strings, np.random.default_rng(4000 + k))
+    assert is_rev == im["info"]["is_reversed"]
+    buf = setwaveresume_lib.new_records(n)
+    for r in range(setwaveresume_lib.N_ROUNDS):
+        got = setwaveresume_lib.feed_wide(img, setwaveresume_lib.pieces_of(strings, rounds[r]), buf)
+    compare(got, im, "MFA_SET_WAVE=1, strings in pieces")
+    whole = setwaveresume_lib.new_records(n)
+    compare(setwaveresume_lib.feed_wide(img, strings, whole), im, "MFA_SET_WAVE=1, whole strings through the wide call")
+    recs = setwaveresume_lib.records_of(buf, n)
+    assert np.array_equal(recs, setwaveresume_lib.records_of(whole, n))
+    setwaveresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+    # long strings cut
+    env.setenv("MFA_DFA_SPLIT_MIN", str(SPLIT_MIN))
+    env.setenv("MFA_DFA_CHUNK", "48")
+    compare(call(img, d_bytes, d_off, n, "wave, chunk 48"), im, "MFA_SET_WAVE=1 MFA_DFA_SPLIT_MIN=256 MFA_DFA_CHUNK=48")
+    cut = expected_split(off, SPLIT_MIN, 48, WAVE_ARENA)
+    assert cut[0] >= 16 and cut[2] == 48 and img.last_set_split()[:3] == cut
+    assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
+    longs, want = long_only(im)
+    d_bytes, d_off, off = upload(longs)
+    env.setenv("MFA_SET_SPLIT_ROUNDS", "3")
+    env.setenv("MFA_SET_SPLIT_LOOKBACK", "64")
+    compare_long(call(img, d_bytes, d_off, len(longs), "wave, long only"), want, longs, im, "MFA_SET_WAVE=1, long strings only")
+    report = img.last_set_split()
+    assert report[:3] == expected_split(off, SPLIT_MIN, 48, WAVE_ARENA) and report[0] == len(longs)
+    (_, host, digits), = setwavesplit_lib.run_wave_split(setwavesplit_lib.wave_split_emul_exe(), tmp_path, im["blob"], longs, (48,), (64,), (3,))
+    assert np.array_equal(digits, want)
+    assert report[3:] == tuple(host[key] for key in setwavesplit_lib.COUNT_KEYS), (im["what"], report, host)
     img.close()
 
 

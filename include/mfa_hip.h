@@ -376,6 +376,59 @@ int  mfa_mixed_last_dfa(mfa_mixed_t* mx, int device, uint32_t* multi_launches, u
  * (the reference matches one string at a time and has no such step: matchers/match_mfa.cpp:28-36 prints each answer as it comes). */
 int  mfa_pack_result_bitmap(const uint8_t* d_results, uint64_t n, uint8_t* d_bitmap, void* stream);
 
+/* ---- text to batch ---------------------------------------------------------------------------------
+ * Every match entry point takes a batch: strings back to back in `bytes`, bounded by offsets[0..n], no separators between them.  These
+ * calls make that batch from a TEXT in device memory -- a file, a log, the rest of stdin -- on the device: separators found, strings
+ * counted, kept bytes compacted, offsets written.  Replaces: the extraction half of the per-string loops, `cin >> text`
+ * (matchers/match.cpp:21-31) and std::getline (matchers/match_mfa.cpp:28-36,72-80).
+ * The rule.  MFA_SPLIT_LINES restates std::getline(file, line): a string ends at byte 0x0a, which is dropped; every other byte is kept,
+ * \r and NUL included; empty lines are strings (two equal offsets); bytes behind the last 0x0a form a last string only if there is at
+ * least one of them ("" gives 0 strings, "\n" one empty string, "a\nb" and "a\nb\n" both 2).  MFA_SPLIT_TOKENS restates `cin >> text`
+ * in the C locale: separators are 0x09..0x0d and 0x20, a string is a maximal run of other bytes, there are no empty strings.  An
+ * optional stop token (tokens mode only; 1 to 15 bytes, none of them a separator; the command line passes "exit") ends the batch at the
+ * first token EQUAL to it: the strings are the tokens in front of it.  A token that merely starts or ends with it does not stop; a stop
+ * token at the very end of the text, with no separator behind it, does.
+ * Two calls.  mfa_split_text_count counts: it fills the workspace (mfa_split_workspace_bytes(n_text_bytes) bytes of device memory,
+ * 16-byte aligned) and the n_strings, n_bytes and stopped fields of *d_info (device memory, 8-byte aligned), and zeroes the other two.
+ * mfa_split_text_write writes the batch into d_bytes (bytes_capacity bytes) and d_offsets (max_strings + 1 entries) and sets
+ * max_string_bytes and overflow.  The text is cut into tiles of mfa_split_tile_bytes(); the passes are plain launches in stream
+ * order, no workgroup waits for another.
+ * Asynchrony and order.  Both calls are asynchronous on `stream`.  `write` uses the workspace and the info record that a `count` of the
+ * same text, mode and stop token left; the two calls may follow each other on one stream with no wait in between when the caller can
+ * bound the sizes itself (a text of t bytes holds at most t kept bytes, t + 1 lines, (t + 1) / 2 tokens); otherwise the caller reads
+ * the 32 bytes of the info back between them and allocates exactly.
+ * Input.  d_text is 16-byte aligned and readable up to n_text_bytes rounded up to 16; the bytes there are never interpreted.
+ * Output capacity.  A d_bytes of capacity round_up(n_bytes, 16) satisfies the read rule of mfa_match_batch.  d_bytes needs no alignment.
+ * What is valid after `write`: offsets[0] = 0; offsets[0 .. min(n_strings, max_strings)] are valid, and so is d_bytes[0 .. offsets[that])
+ * as far as bytes_capacity reaches.  Everything else in the two buffers inside their capacities is unspecified; everything outside them
+ * is untouched: no offset with an index above max_strings is written, and no byte at or beyond bytes_capacity.
+ * Overflow.  `overflow` is set when anything was clipped, by max_strings or by bytes_capacity.  The counts in the info are still the
+ * true ones, so the caller can allocate and call `write` again.
+ * n_text_bytes == 0 (d_text may then be NULL): MFA_OK, 0 strings, offsets[0] = 0, no tile launched.
+ * MFA_ERR_INVALID_ARG, answered before the device is touched: a NULL pointer (d_bytes may be NULL when bytes_capacity is 0); an unknown
+ * mode; a stop token in lines mode; a stop token that is empty, longer than 15 bytes or holds a separator; a d_text or d_workspace that
+ * is not 16-byte aligned, a d_info or d_offsets that is not 8-byte aligned; a text of 2^45 bytes or more.  MFA_ERR_NO_DEVICE as
+ * everywhere else.
+ * Long strings.  The splitter does not look at MFA_MAX_STRING_BYTES: a longer string is answered 2 by the match call, as always;
+ * max_string_bytes lets a caller see it coming. */
+#define MFA_SPLIT_LINES  0u
+#define MFA_SPLIT_TOKENS 1u
+typedef struct mfa_split_info {      /* device memory, 32 bytes */
+    uint64_t n_strings;              /* true count (in front of the stop token, if one was met), whatever max_strings is */
+    uint64_t n_bytes;                /* kept bytes of those strings = offsets[n_strings] */
+    uint64_t max_string_bytes;       /* written by mfa_split_text_write: over the strings it wrote */
+    uint32_t stopped, overflow;      /* stop token met; write clipped by max_strings or bytes_capacity */
+} mfa_split_info;
+uint32_t mfa_split_tile_bytes(void);
+/* MFA_ERR_INVALID_ARG: bytes is NULL, or the text is too long (above) */
+int mfa_split_workspace_bytes(uint64_t n_text_bytes, size_t* bytes);
+int mfa_split_text_count(const uint8_t* d_text, uint64_t n_text_bytes, uint32_t mode, const char* stop_token,
+                         void* d_workspace, mfa_split_info* d_info, int device, void* stream);
+int mfa_split_text_write(const uint8_t* d_text, uint64_t n_text_bytes, uint32_t mode,
+                         const void* d_workspace, mfa_split_info* d_info,
+                         uint8_t* d_bytes, uint64_t bytes_capacity, uint64_t* d_offsets, uint64_t max_strings,
+                         int device, void* stream);
+
 /* Same with HOST pointers: copies the batch to the device, matches, copies the
  * results back, synchronises.  Convenience for callers that hold std::strings
  * (the CLI); throughput is then bounded by the host link, not by the kernel. */

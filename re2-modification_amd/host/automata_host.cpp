@@ -3,6 +3,7 @@
 // through the C-ABI of libmfa_hip.so.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <stdexcept>
 #include <thread>
@@ -265,6 +266,54 @@ void Automata::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint6
     match_packed_short(img, bytes, offsets, n, results);
 }
 
+// text_match.cpp: the text split on the device and matched where it lies
+int diploma_match_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n, uint32_t mode, const char* stop, uint64_t longest_allowed,
+                                 int device, std::vector<uint8_t>& results, uint64_t* longest);
+
+namespace {
+
+// the splitting rule of include/mfa_hip.h ("text to batch") on the host: what match_text falls back to
+void split_on_host(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& bytes, vector<uint64_t>& offsets) {
+    bytes.clear();
+    offsets.assign(1, 0);
+    const size_t stop_len = stop ? strlen(stop) : 0;
+    auto is_sep = [&](uint8_t c) { return tokens ? ((c >= 0x09 && c <= 0x0d) || c == 0x20) : c == 0x0a; };
+    size_t p = 0;
+    while (p < n) {
+        if (tokens) {
+            while (p < n && is_sep(text[p])) p++;
+            if (p == n) break;
+        }
+        size_t e = p;
+        while (e < n && !is_sep(text[e])) e++;
+        if (tokens && stop_len && e - p == stop_len && memcmp(text + p, stop, stop_len) == 0) break;
+        bytes.insert(bytes.end(), text + p, text + e);
+        offsets.push_back(bytes.size());
+        p = tokens ? e : e + 1;                                // (lines: behind the newline; a text that ends there has no further line)
+    }
+}
+
+}  // namespace
+
+void Automata::match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results) {
+    mfa_image* img = image_for_match();
+    uint64_t longest = 0;
+    const uint64_t beyond = piece_rule().beyond;
+    int rc = diploma_match_text_on_device(img, text, n, tokens ? MFA_SPLIT_TOKENS : MFA_SPLIT_LINES, stop, beyond, device, results, &longest);
+    if (rc != MFA_OK) fail("Automata::match_text", rc);
+    if (longest <= beyond) {
+        for (uint8_t& r : results) r = r == 1 ? 1 : 0;
+        return;
+    }
+    // a string beyond what one device call takes: match_packed knows how to cut such strings (or, for a memory automaton, refuses them)
+    vector<uint8_t> bytes;
+    vector<uint64_t> offsets;
+    split_on_host(text, n, tokens, stop, bytes, offsets);
+    results.assign(offsets.size() - 1, 0);
+    bytes.resize(bytes.size() + 16);
+    if (!results.empty()) match_packed(bytes.data(), offsets.data(), offsets.size() - 1, results.data());
+}
+
 void Automata::match_packed_short(mfa_image* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     // the devices of the node: all of them by default (north_star: "the string batch shards trivially across the 8 GPUs of one node")
     const int count = mfa_device_count();
@@ -405,6 +454,10 @@ void MFA::match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n
 }
 
 vector<bool> MFA::match_batch(const vector<string>& strs) { return Automata::match_batch(strs); }
+
+void MFA::match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results) {
+    Automata::match_text(text, n, tokens, stop, results);      // image_blob() is virtual, as for match_packed
+}
 
 vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs) {
     return match_mixed(vector<Automata*>(automata.begin(), automata.end()), strs);

@@ -146,6 +146,12 @@ public:
     vector<bool> match_batch(const vector<string>& strs);
     // packed form: string k is bytes[offsets[k], offsets[k+1]); results gets n bytes of 0/1
     void match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results);
+    // A whole text: split into strings ON THE DEVICE (include/mfa_hip.h, "text to batch") and matched where they lie -- one upload of the
+    // text, the split, one read-back of the 32-byte info record, the plain match call, the results back -- on `device` alone.  tokens:
+    // false = one string per line, as std::getline cuts them; true = one per whitespace-separated token, as `cin >> text` does, up to
+    // the first token equal to `stop` (nullptr: none).  results gets one 0/1 byte per string.  If the text holds a string beyond what one
+    // device call takes, the text is split on the host instead and goes through match_packed, which knows how to cut such strings.
+    void match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results);
 
     // the automaton image handed to the device (include/mfa_image_format.h)
     virtual vector<uint8_t> image_blob() const;
@@ -198,6 +204,7 @@ public:
     bool match(string str);
     vector<bool> match_batch(const vector<string>& strs);
     void match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results);
+    void match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results);
 
     vector<uint8_t> image_blob() const override;
 };
@@ -335,6 +342,9 @@ std::string substr(std::string originalString, int maxLength);
 // matchers/match.cpp:10 -- the `-match` loop: compile once, then 0/1 per whitespace-separated token of
 // stdin until the token `exit` (or end of input), batched onto the GPU
 void match(string regexp_str, bool reverse, bool bnf, bool ssnf, bool use_log = false);
+// `diploma -match-lines FILE`: compile as match() does (the header lines are printed), then one 0/1 line per line of FILE, the file
+// split into lines on the device (Automata::match_text).  false: FILE cannot be read
+bool match_lines(string regexp_str, const string& path, bool reverse, bool bnf, bool ssnf);
 // matchers/match_mfa.cpp:13,58 counterparts: strings from a file (one per line), one batch, results and
 // timing on stdout
 // The cut points of a batch over `parts` devices: cuts[r] .. cuts[r+1]-1 are the strings of part r (parts + 1 values, cuts[0] = 0,

@@ -1,9 +1,12 @@
 // The match loops of the reference's matchers/ directory, batched onto the GPU.
 //   match()      matchers/match.cpp:10-32      `./diploma -match`: regex compiled once, then one 0/1 line per
 //                                              whitespace-separated token of stdin, until the token `exit`
+//   match_lines() (no counterpart)             `./diploma -match-lines FILE`: the same answers for the lines of a file,
+//                                              split into strings on the device
 //   match_gt()   matchers/match_mfa.cpp:13-56  strings from a file against the Glushkov automaton
 //   match_mfa()  matchers/match_mfa.cpp:58-97  strings from a file against toMFA()'s automaton
 //   run_configuration_examples()  matchers/example_runner.cpp:84-151  `./diploma -match N`: growth curve of one example
+#include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cstdint>
@@ -40,7 +43,43 @@ void flush(Automata* a, MFA* m, Batch& b) {
     b.clear();
 }
 
+// the rest of a stream, whole, in large reads (an istreambuf_iterator would take it a character at a time)
+string read_all(std::istream& in) {
+    string text;
+    size_t have = 0;
+    for (size_t step = size_t(1) << 20; in; step = std::min(step * 2, size_t(256) << 20)) {
+        text.resize(have + step);
+        in.read(&text[have], (std::streamsize)step);
+        have += (size_t)in.gcount();
+    }
+    text.resize(have);
+    return text;
+}
+
+// the answers of a text split on the device, printed as flush() prints a batch's
+void answer_text(Automata* a, MFA* m, const string& text, bool tokens, const char* stop) {
+    vector<uint8_t> res;
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+    if (m) m->match_text(bytes, text.size(), tokens, stop, res);
+    else a->match_text(bytes, text.size(), tokens, stop, res);
+    string out;
+    out.reserve(2 * res.size());
+    for (uint8_t r : res) { out += r ? '1' : '0'; out += '\n'; }
+    cout << out << std::flush;
+}
+
 }  // namespace
+
+bool match_lines(string regexp_str, const string& path, bool reverse, bool bnf, bool ssnf) {
+    std::ifstream file(path, std::ios::binary);
+    if (!file.is_open()) return false;
+    const string text = read_all(file);
+    Regexp* regexp = Regexp::parse_regexp(regexp_str);
+    bool is_mfa = false;
+    Automata* automata = regexp->compile(is_mfa, reverse, bnf, ssnf, false);
+    answer_text(automata, is_mfa ? static_cast<MFA*>(automata) : nullptr, text, false, nullptr);
+    return true;
+}
 
 void match(string regexp_str, bool reverse, bool bnf, bool ssnf, bool use_log) {
     Regexp* regexp = Regexp::parse_regexp(regexp_str);
@@ -51,6 +90,14 @@ void match(string regexp_str, bool reverse, bool bnf, bool ssnf, bool use_log) {
     // tokens are collected into batches -- one token per batch when stdin is a terminal, so interactive
     // use still answers immediately -- and end of input ends the loop.
     const bool interactive = isatty(0) != 0;
+    // DIPLOMA_DEVICE_SPLIT=1, stdin not a terminal: the rest of stdin is read whole and cut into tokens on the device, up to the token
+    // `exit`; the answers are those of the loop below
+    const char* device_split = std::getenv("DIPLOMA_DEVICE_SPLIT");
+    if (!interactive && device_split && device_split[0] == '1' && device_split[1] == 0) {
+        const string text = read_all(cin);
+        answer_text(automata, mfa, text, true, "exit");
+        return;
+    }
     const size_t kFlushBytes = size_t(256) << 20;
     Batch batch;
     string text;

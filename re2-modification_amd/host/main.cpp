@@ -2,6 +2,7 @@
 //   diploma -match [-bnf] [-reverse] [-ssnf] [-all] [-log]    regex token, then string tokens until `exit`
 //   diploma -match N                                          timing series over test/example_N (example_runner.cpp)
 //   diploma -match-blocks N [-bnf] [-reverse] [-ssnf] [-all]  as -match for a memory-less regex, every token fed to an Automata::Stream N bytes at a time
+//   diploma -match-lines FILE [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then one 0/1 line per line of FILE, split on the device
 //   diploma -dump  [-thompson|-glushkov|-mfa]                 regex token -> automaton image as text
 //   diploma -match-file <gt|mfa> <file>                       matchers/match_mfa.cpp counterparts
 //   diploma -match-mixed [-bnf|-reverse|-ssnf|-all] FILE...   one regex and its strings per file, all files in ONE device call
@@ -156,6 +157,24 @@ int main(int argc, char* argv[]) {
                 }
                 cout << (stream.accepted() ? 1 : 0) << endl;
             }
+            return 0;
+        }
+        if (argc > 1 && std::strcmp(argv[1], "-match-lines") == 0) {
+            // the lines of FILE as `-match` answers tokens: compile() prints its header lines, then one 0/1 line per line of the file; the file
+            // goes to the device whole and is cut into lines there
+            if (argc < 3) { std::cerr << "diploma: -match-lines: which file?\n"; return 1; }
+            bool bnf = false, reverse = false, ssnf = false;
+            for (int i = 3; i < argc; i++) {
+                const string flag = argv[i];
+                if (flag == "-all") bnf = reverse = ssnf = true;
+                else if (flag == "-bnf") bnf = true;
+                else if (flag == "-reverse") reverse = bnf = true;
+                else if (flag == "-ssnf") ssnf = true;
+                else { std::cerr << "diploma: -match-lines: unknown flag " << flag << "\n"; return 1; }
+            }
+            string regex;
+            cin >> regex;
+            if (!match_lines(regex, argv[2], reverse, bnf, ssnf)) { cout << "ERROR\n"; return 1; }
             return 0;
         }
         if (argc > 1 && std::strcmp(argv[1], "-match") == 0) {

@@ -21,13 +21,15 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_mixed_last_launches", "mfa_mixed_last_dfa", "mfa_pack_result_bitmap", "mfa_last_dfa_split",
            "mfa_match_batch_resume", "mfa_match_batch_resume_host", "mfa_last_dfa_spec",
            "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split",
-           "mfa_match_batch_resume_set_wide", "mfa_match_batch_resume_set_wide_host", "mfa_image_resume_state_bytes"]
+           "mfa_match_batch_resume_set_wide", "mfa_match_batch_resume_set_wide_host", "mfa_image_resume_state_bytes",
+           "mfa_split_tile_bytes", "mfa_split_workspace_bytes", "mfa_split_text_count", "mfa_split_text_write"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 SET_STATE_WORDS = 12                                                        # a record of mfa_match_batch_resume_set: tag, reserved[3], nodes[8]
 SET_STATE_WIDE_WORDS = 68                                                   # a record of mfa_match_batch_resume_set_wide (wave images): tag, reserved[3], nodes[64]
 SET_STATE_START, SET_STATE_LIVE, SET_STATE_INVALID = 0, 1, 0xffffffff       # their tags (records are never stored either)
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
+SPLIT_LINES, SPLIT_TOKENS = 0, 1                                            # modes of the text splitter
 
 
 class MfaError(RuntimeError):
@@ -42,6 +44,12 @@ class MfaError(RuntimeError):
 class ImageInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("kind", "is_reversed", "n_nodes", "n_edges", "n_cells", "dfa_states", "byte_classes", "last_kernel")]
+
+
+class SplitInfo(ctypes.Structure):
+    """mfa_split_info: 32 bytes of device memory"""
+    _fields_ = [("n_strings", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("max_string_bytes", ctypes.c_uint64),
+                ("stopped", ctypes.c_uint32), ("overflow", ctypes.c_uint32)]
 
 
 _lib = None
@@ -102,6 +110,11 @@ def lib():
         L.mfa_match_mixed_host.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, i32]
         L.mfa_mixed_last_ms.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.mfa_mixed_timing.argtypes = [vp, i32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        if hasattr(L, "mfa_split_text_count"):            # (as above: an older build)
+            L.mfa_split_tile_bytes.restype = ctypes.c_uint32
+            L.mfa_split_workspace_bytes.argtypes = [u64, ctypes.POINTER(ctypes.c_size_t)]
+            L.mfa_split_text_count.argtypes = [vp, u64, ctypes.c_uint32, ctypes.c_char_p, vp, vp, i32, vp]
+            L.mfa_split_text_write.argtypes = [vp, u64, ctypes.c_uint32, vp, vp, vp, u64, vp, u64, i32, vp]
         L.mfa_strerror.argtypes = [i32]
         L.mfa_strerror.restype = ctypes.c_char_p
         L.mfa_version.restype = ctypes.c_char_p
@@ -386,6 +399,56 @@ def pack_result_bitmap(d_results, d_bitmap=None, stream=None):
     s = stream if stream is not None else torch.cuda.current_stream(d_results.device)
     _check(lib().mfa_pack_result_bitmap(d_results.data_ptr(), n, d_bitmap.data_ptr(), ctypes.c_void_p(s.cuda_stream)), "mfa_pack_result_bitmap")
     return d_bitmap
+
+
+def split_tile_bytes():
+    """mfa_split_tile_bytes: the bytes of text one workgroup of the splitter takes"""
+    return lib().mfa_split_tile_bytes()
+
+
+def split_workspace_bytes(n_text_bytes):
+    out = ctypes.c_size_t()
+    _check(lib().mfa_split_workspace_bytes(n_text_bytes, ctypes.byref(out)), "mfa_split_workspace_bytes")
+    return out.value
+
+
+def split_text_count(d_text_ptr, n_text_bytes, mode, stop, d_workspace_ptr, d_info_ptr, device=0, stream=0):
+    """mfa_split_text_count on raw device pointers (ints); stop: bytes or None.  Asynchronous on `stream` (a hipStream_t value)."""
+    _check(lib().mfa_split_text_count(d_text_ptr, n_text_bytes, mode, stop, d_workspace_ptr, d_info_ptr, device, ctypes.c_void_p(stream)),
+           "mfa_split_text_count")
+
+
+def split_text_write(d_text_ptr, n_text_bytes, mode, d_workspace_ptr, d_info_ptr, d_bytes_ptr, bytes_capacity, d_offsets_ptr, max_strings,
+                     device=0, stream=0):
+    """mfa_split_text_write on raw device pointers (ints).  Asynchronous on `stream` (a hipStream_t value)."""
+    _check(lib().mfa_split_text_write(d_text_ptr, n_text_bytes, mode, d_workspace_ptr, d_info_ptr, d_bytes_ptr, bytes_capacity, d_offsets_ptr,
+                                      max_strings, device, ctypes.c_void_p(stream)), "mfa_split_text_write")
+
+
+def split_text(text, mode, stop=None, stream=None):
+    """A text in device memory -> the batch the match calls take.  text: a contiguous torch CUDA uint8 tensor whose memory is 16-byte
+    aligned and readable up to its size rounded up to 16 (a tensor with an allocation of its own is; a view into the middle of one
+    may not be); mode: SPLIT_LINES or SPLIT_TOKENS; stop: the stop token (bytes, tokens mode only) or None.
+    Count, ONE read-back of the 32 bytes of the info record, exact allocation, write -- all on `stream` (default: the current one).
+    Returns (bytes, offsets, n, info): a uint8 tensor of n_bytes rounded up to 16 (at least 16) bytes, an int64 tensor of n + 1 offsets,
+    the number of strings, and info = {"n_strings", "n_bytes", "stopped"} as read back, plus "d_info": the device record (int64[4]:
+    n_strings, n_bytes, max_string_bytes, stopped | overflow << 32), where the write call leaves max_string_bytes."""
+    import torch
+    assert text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
+    n_text = text.numel()
+    dev = text.device.index or 0
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(text.device)):      # (allocations belong to that stream too)
+        s = torch.cuda.current_stream(text.device).cuda_stream
+        ptr = text.data_ptr() if n_text else None
+        work = torch.empty(max(split_workspace_bytes(n_text), 16), dtype=torch.uint8, device=text.device)
+        d_info = torch.zeros(4, dtype=torch.int64, device=text.device)
+        split_text_count(ptr, n_text, mode, stop, work.data_ptr(), d_info.data_ptr(), dev, s)
+        head = [int(x) for x in d_info.cpu()]                 # the one read-back (it waits for the count)
+        n, n_bytes = head[0], head[1]
+        d_bytes = torch.empty(max((n_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=text.device)
+        d_offsets = torch.empty(n + 1, dtype=torch.int64, device=text.device)
+        split_text_write(ptr, n_text, mode, work.data_ptr(), d_info.data_ptr(), d_bytes.data_ptr(), d_bytes.numel(), d_offsets.data_ptr(), n, dev, s)
+    return d_bytes, d_offsets, n, {"n_strings": n, "n_bytes": n_bytes, "stopped": head[3] & 0xffffffff, "d_info": d_info}
 
 
 def device_count():

@@ -429,6 +429,60 @@ int mfa_split_text_write(const uint8_t* d_text, uint64_t n_text_bytes, uint32_t 
                          uint8_t* d_bytes, uint64_t bytes_capacity, uint64_t* d_offsets, uint64_t max_strings,
                          int device, void* stream);
 
+/* ---- batch to text ---------------------------------------------------------------------------------
+ * The way out of a batch: the strings that a match call answered 1 -- or 0, with MFA_SELECT_INVERT -- compacted on the device, so that
+ * only what matched travels back: their bytes back to back as a batch of their own, or with a 0x0a behind each as a text
+ * (MFA_SELECT_NEWLINE), their offsets in the output and their indices in the input.  What `grep -x` and `grep -vx` print.  Replaces: the
+ * join of the answers with the input that the per-string loops leave to their caller (matchers/match_mfa.cpp:28-36 prints one answer
+ * per line).
+ * Input.  A batch exactly as mfa_match_batch takes it: offsets[0] need not be 0, d_bytes needs no alignment.  d_results is what a match
+ * call left for it, one byte per string.  String k is kept when d_results[k] is 1, or 0 under MFA_SELECT_INVERT.  Every other value (2:
+ * beyond MFA_MAX_STRING_BYTES) is never kept, with either flag, and is counted in n_unanswered.
+ * Read rule.  The calls read no byte outside the aligned 16-byte blocks of memory that [d_bytes + offsets[0], d_bytes + offsets[n])
+ * touches: narrower than what mfa_match_batch asks for.  They read d_results[0 .. n) and d_offsets[0 .. n].
+ * Two calls.  mfa_select_count fills the workspace (mfa_select_workspace_bytes(n) bytes of device memory, 16-byte aligned) and the counts
+ * of *d_info (device memory, 8-byte aligned), and zeroes overflow.  mfa_select_write writes the kept strings and sets overflow.  The
+ * passes are plain launches in stream order, no workgroup waits for another; the bytes are moved by one workgroup per 16 KiB of OUTPUT,
+ * so a batch of one long string beside a million empty ones is spread like any other.
+ * Output.  Kept strings appear in batch order.  d_out_indices[r] is the index k of the r-th kept string (d_out_indices may be NULL),
+ * d_out_offsets[r] where its bytes start in d_out_bytes; d_out_offsets[0] = 0 and d_out_offsets[n_selected] = n_bytes.  Without
+ * MFA_SELECT_NEWLINE the two output buffers are themselves a batch for any match call (empty strings leave equal offsets), and a
+ * bytes_capacity of round_up(n_bytes, 16) satisfies the read rule of mfa_match_batch.  With it, string r occupies
+ * [out_offsets[r], out_offsets[r+1] - 1) and the byte behind it is 0x0a: d_out_bytes[0 .. n_bytes) is a text that mfa_split_text_* in
+ * lines mode cuts back into the same strings, provided no kept string holds a 0x0a.  d_out_bytes needs no alignment; it may be NULL when
+ * bytes_capacity is 0, which gives indices and offsets only (overflow is then set unless n_bytes is 0).
+ * Validity and clipping, as for mfa_split_text_write.  With v = min(n_selected, max_selected), valid after `write` are
+ * out_offsets[0 .. v], out_indices[0 .. v) and out_bytes[0 .. min(out_offsets[v], bytes_capacity)).  Everything else inside the
+ * capacities is unspecified; everything outside them is untouched: nothing above out_offsets[max_selected] or
+ * out_indices[max_selected - 1] is ever written, and no byte at or beyond bytes_capacity.  `overflow` is set when anything was clipped, by
+ * max_selected or by bytes_capacity; the counts stay the true ones, so the caller can allocate and call `write` again.  The outputs must
+ * not overlap the inputs or each other.
+ * Asynchrony and order.  Both calls are asynchronous on `stream`.  `write` uses the workspace and the info record that a `count` of the
+ * same results, offsets, n and flags left.  The two may follow each other on one stream with no wait in between when the caller bounds
+ * the sizes itself: at most n strings, at most offsets[n] - offsets[0] bytes (+ n with MFA_SELECT_NEWLINE); otherwise the caller reads
+ * the 32 bytes of the info back between them and allocates exactly.  Both calls are legal inside a stream capture: they make no
+ * allocation, no read-back and no upload.
+ * n == 0: MFA_OK, all counts 0, out_offsets[0] = 0.
+ * MFA_ERR_INVALID_ARG, answered before the device is touched: a NULL pointer other than the two allowed above; unknown flag bits; a
+ * d_workspace that is not 16-byte aligned; a d_info, d_offsets, d_out_offsets or d_out_indices that is not 8-byte aligned; an n of 2^40 or
+ * more.  MFA_ERR_NO_DEVICE as everywhere else. */
+#define MFA_SELECT_INVERT  1u  /* keep the strings answered 0 instead of those answered 1 */
+#define MFA_SELECT_NEWLINE 2u  /* one byte 0x0a behind every kept string: the output is a text */
+typedef struct mfa_select_info {     /* device memory, 32 bytes, 8-byte aligned */
+    uint64_t n_selected;             /* true count, whatever max_selected is */
+    uint64_t n_bytes;                /* output bytes of those strings: their lengths, plus n_selected with NEWLINE */
+    uint64_t n_unanswered;           /* strings whose result byte is neither 0 nor 1 (2: beyond MFA_MAX_STRING_BYTES); never kept */
+    uint32_t overflow, reserved;     /* write clipped by max_selected or bytes_capacity; zero */
+} mfa_select_info;
+/* MFA_ERR_INVALID_ARG: bytes is NULL, or n_strings is 2^40 or more */
+int mfa_select_workspace_bytes(uint64_t n_strings, size_t* bytes);
+int mfa_select_count(const uint8_t* d_results, const uint64_t* d_offsets, uint64_t n, uint32_t flags,
+                     void* d_workspace, mfa_select_info* d_info, int device, void* stream);
+int mfa_select_write(const uint8_t* d_bytes, const uint64_t* d_offsets, const uint8_t* d_results, uint64_t n, uint32_t flags,
+                     const void* d_workspace, mfa_select_info* d_info,
+                     uint8_t* d_out_bytes, uint64_t bytes_capacity, uint64_t* d_out_offsets, uint64_t* d_out_indices,
+                     uint64_t max_selected, int device, void* stream);
+
 /* Same with HOST pointers: copies the batch to the device, matches, copies the
  * results back, synchronises.  Convenience for callers that hold std::strings
  * (the CLI); throughput is then bounded by the host link, not by the kernel. */

@@ -14,6 +14,7 @@
 
 #include "mfa_internal.h"
 #include "text_split_core.h"
+#include "wave_scan.h"
 
 namespace mfa {
 
@@ -107,15 +108,6 @@ __global__ void __launch_bounds__(kSplitThreads) split_count_kernel(const uint8_
 
 // ---- scan ----------------------------------------------------------------------------------------------------------------------------
 static constexpr uint32_t kScanPerThread = 16u;      // consecutive tiles a thread sums: 4096 tiles (64 MiB of text) per round of the workgroup
-
-__device__ __forceinline__ uint64_t wave_scan_incl(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint64_t up = __shfl_up(v, d);
-        if (lane >= d) v += up;
-    }
-    return v;
-}
 
 __global__ void __launch_bounds__(kSplitThreads) split_scan_kernel(const SplitTotals* __restrict__ totals, SplitPrefix* __restrict__ prefix,
                                                                    uint64_t n_tiles, const uint8_t* __restrict__ text, uint64_t n_text,

@@ -314,6 +314,40 @@ void Automata::match_text(const uint8_t* text, size_t n, bool tokens, const char
     if (!results.empty()) match_packed(bytes.data(), offsets.data(), offsets.size() - 1, results.data());
 }
 
+// text_match.cpp: the same with the selection on the device too
+int diploma_select_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n, uint32_t mode, const char* stop, uint64_t longest_allowed,
+                                  int device, bool invert, std::string& out, uint64_t* n_unanswered, uint64_t* longest);
+
+void Automata::select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered) {
+    out.clear();
+    uint64_t unanswered = 0;
+    const char* on_device = getenv("DIPLOMA_DEVICE_SELECT");
+    if (!(on_device && on_device[0] == '0' && on_device[1] == 0)) {
+        mfa_image* img = image_for_match();
+        uint64_t longest = 0;
+        const uint64_t beyond = piece_rule().beyond;
+        int rc = diploma_select_text_on_device(img, text, n, tokens ? MFA_SPLIT_TOKENS : MFA_SPLIT_LINES, stop, beyond, device, invert, out, &unanswered,
+                                               &longest);
+        if (rc != MFA_OK) fail("Automata::select_text", rc);
+        if (longest <= beyond) {
+            if (n_unanswered) *n_unanswered = unanswered;
+            return;
+        }
+    }
+    // the selection on the host: the answers of match_text (which cuts a string beyond what one device call takes) and the split rule again
+    vector<uint8_t> results, bytes;
+    vector<uint64_t> offsets;
+    match_text(text, n, tokens, stop, results);
+    split_on_host(text, n, tokens, stop, bytes, offsets);
+    out.clear();
+    for (size_t k = 0; k + 1 < offsets.size() && k < results.size(); k++) {
+        if ((results[k] == 1) == invert) continue;
+        out.append(reinterpret_cast<const char*>(bytes.data()) + offsets[k], offsets[k + 1] - offsets[k]);
+        out += '\n';
+    }
+    if (n_unanswered) *n_unanswered = 0;
+}
+
 void Automata::match_packed_short(mfa_image* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     // the devices of the node: all of them by default (north_star: "the string batch shards trivially across the 8 GPUs of one node")
     const int count = mfa_device_count();
@@ -457,6 +491,10 @@ vector<bool> MFA::match_batch(const vector<string>& strs) { return Automata::mat
 
 void MFA::match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results) {
     Automata::match_text(text, n, tokens, stop, results);      // image_blob() is virtual, as for match_packed
+}
+
+void MFA::select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered) {
+    Automata::select_text(text, n, tokens, stop, invert, out, n_unanswered);      // image_blob() is virtual, as for match_packed
 }
 
 vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs) {

@@ -152,6 +152,14 @@ public:
     // the first token equal to `stop` (nullptr: none).  results gets one 0/1 byte per string.  If the text holds a string beyond what one
     // device call takes, the text is split on the host instead and goes through match_packed, which knows how to cut such strings.
     void match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results);
+    // The strings of a text that the automaton accepts -- rejects, with `invert` -- as a text of their own in `out`, each with a 0x0a
+    // behind it: what `grep -x` (`grep -vx`) prints.  Split, matched and SELECTED on the device (include/mfa_hip.h, "batch to text"): one
+    // upload of the text, the split, the plain match call, mfa_select_count, one read-back of the 32-byte info record, mfa_select_write
+    // with MFA_SELECT_NEWLINE, one read-back of exactly the kept bytes; no offsets and no result bytes come to the host.  text, tokens
+    // and stop as for match_text.  *n_unanswered (may be nullptr): strings the device answered neither 0 nor 1; they are never kept.  If
+    // the text holds a string beyond what one device call takes, or under DIPLOMA_DEVICE_SELECT=0, the selection is done on the host from
+    // the answers of match_text; the output is the same.
+    void select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered);
 
     // the automaton image handed to the device (include/mfa_image_format.h)
     virtual vector<uint8_t> image_blob() const;
@@ -205,6 +213,7 @@ public:
     vector<bool> match_batch(const vector<string>& strs);
     void match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results);
     void match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results);
+    void select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered);
 
     vector<uint8_t> image_blob() const override;
 };
@@ -345,6 +354,10 @@ void match(string regexp_str, bool reverse, bool bnf, bool ssnf, bool use_log = 
 // `diploma -match-lines FILE`: compile as match() does (the header lines are printed), then one 0/1 line per line of FILE, the file
 // split into lines on the device (Automata::match_text).  false: FILE cannot be read
 bool match_lines(string regexp_str, const string& path, bool reverse, bool bnf, bool ssnf);
+// `diploma -grep-lines FILE [-v]`: compile as match() does (the header lines are printed), then the lines of FILE that match -- with
+// `invert` those that do not -- each followed by a newline, selected on the device (Automata::select_text).  false: FILE cannot be read.
+// *n_unanswered: lines the device answered neither 0 nor 1 (they are not printed)
+bool grep_lines(string regexp_str, const string& path, bool invert, bool reverse, bool bnf, bool ssnf, uint64_t* n_unanswered);
 // matchers/match_mfa.cpp:13,58 counterparts: strings from a file (one per line), one batch, results and
 // timing on stdout
 // The cut points of a batch over `parts` devices: cuts[r] .. cuts[r+1]-1 are the strings of part r (parts + 1 values, cuts[0] = 0,

@@ -3,6 +3,7 @@
 //   diploma -match N                                          timing series over test/example_N (example_runner.cpp)
 //   diploma -match-blocks N [-bnf] [-reverse] [-ssnf] [-all]  as -match for a memory-less regex, every token fed to an Automata::Stream N bytes at a time
 //   diploma -match-lines FILE [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then one 0/1 line per line of FILE, split on the device
+//   diploma -grep-lines FILE [-v] [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then the lines of FILE that match (-v: that do not), selected on the device
 //   diploma -dump  [-thompson|-glushkov|-mfa]                 regex token -> automaton image as text
 //   diploma -match-file <gt|mfa> <file>                       matchers/match_mfa.cpp counterparts
 //   diploma -match-mixed [-bnf|-reverse|-ssnf|-all] FILE...   one regex and its strings per file, all files in ONE device call
@@ -175,6 +176,27 @@ int main(int argc, char* argv[]) {
             string regex;
             cin >> regex;
             if (!match_lines(regex, argv[2], reverse, bnf, ssnf)) { cout << "ERROR\n"; return 1; }
+            return 0;
+        }
+        if (argc > 1 && std::strcmp(argv[1], "-grep-lines") == 0) {
+            // what `-match-lines` prints before its answers, then the lines of FILE it would answer 1 (-v: 0), each followed by a newline; the
+            // file goes to the device whole and only the kept lines come back
+            if (argc < 3) { std::cerr << "diploma: -grep-lines: which file?\n"; return 1; }
+            bool bnf = false, reverse = false, ssnf = false, invert = false;
+            for (int i = 3; i < argc; i++) {
+                const string flag = argv[i];
+                if (flag == "-all") bnf = reverse = ssnf = true;
+                else if (flag == "-bnf") bnf = true;
+                else if (flag == "-reverse") reverse = bnf = true;
+                else if (flag == "-ssnf") ssnf = true;
+                else if (flag == "-v") invert = true;
+                else { std::cerr << "diploma: -grep-lines: unknown flag " << flag << "\n"; return 1; }
+            }
+            string regex;
+            cin >> regex;
+            uint64_t unanswered = 0;
+            if (!grep_lines(regex, argv[2], invert, reverse, bnf, ssnf, &unanswered)) { cout << "ERROR\n"; return 1; }
+            if (unanswered) { std::cerr << "diploma: -grep-lines: " << unanswered << " lines were not answered\n"; return 2; }
             return 0;
         }
         if (argc > 1 && std::strcmp(argv[1], "-match") == 0) {

@@ -1,11 +1,13 @@
 // A whole text against one automaton, split into strings ON THE DEVICE (include/mfa_hip.h, "text to batch"): one upload of the text,
 // count, one read-back of the 32-byte info record, exact allocation, write, the plain match call, results back -- on one device, on
-// its default stream.  The only file of the host mirror that calls the HIP runtime itself (device memory and copies): it does not
+// its default stream.  And the same with the way out on the device too ("batch to text"): the strings that matched come back as a text,
+// no offsets and no result bytes.  The only file of the host mirror that calls the HIP runtime itself (device memory and copies): it does not
 // include diploma_api.h, whose `enum MemoryAction { open, close }` clashes with the system headers the runtime's header pulls in.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/mfa_hip.h"
@@ -60,5 +62,60 @@ int diploma_match_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n
     if (info.max_string_bytes > longest_allowed) return MFA_OK;  // the caller's other way
     back.resize(info.n_strings);
     results.swap(back);
+    return MFA_OK;
+}
+
+// The strings of the text that the automaton accepts (rejects, with `invert`), each with a 0x0a behind it, in `out`: split, matched and
+// selected on the device; what travels back is the 32-byte info record of the selection (with the splitter's behind it) and the kept
+// bytes.  *longest as above: when it passes `longest_allowed`, `out` is empty and the caller takes another way.  *n_unanswered: strings
+// the match call answered neither 0 nor 1; they are not kept.
+int diploma_select_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n, uint32_t mode, const char* stop, uint64_t longest_allowed,
+                                  int device, bool invert, std::string& out, uint64_t* n_unanswered, uint64_t* longest) {
+    out.clear();
+    *longest = 0;
+    *n_unanswered = 0;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return MFA_ERR_HIP;
+    size_t work_bytes = 0;
+    int rc = mfa_split_workspace_bytes(n, &work_bytes);
+    if (rc != MFA_OK) return rc;
+    struct Infos { mfa_select_info select; mfa_split_info split; } infos;      // one record behind the other on the device: one read-back
+    DeviceBuffer d_text, d_work, d_infos, d_bytes, d_offsets, d_results, d_select_work, d_out, d_out_offsets;
+    const size_t room = (n + 15) / 16 * 16;                      // the read rule: whole 16-byte blocks
+    if ((rc = d_text.alloc(room)) != MFA_OK || (rc = d_work.alloc(work_bytes)) != MFA_OK || (rc = d_infos.alloc(sizeof infos)) != MFA_OK) return rc;
+    mfa_select_info* const d_select_info = (mfa_select_info*)d_infos.p;
+    mfa_split_info* const d_split_info = (mfa_split_info*)((uint8_t*)d_infos.p + sizeof(mfa_select_info));
+    if (n && hipMemcpy(d_text.p, text, n, hipMemcpyHostToDevice) != hipSuccess) return MFA_ERR_HIP;      // the one upload
+    rc = mfa_split_text_count(n ? (const uint8_t*)d_text.p : nullptr, n, mode, stop, d_work.p, d_split_info, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    mfa_split_info split;
+    if (hipMemcpy(&split, d_split_info, sizeof split, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;
+    const uint64_t n_strings = split.n_strings, capacity = (split.n_bytes + 15) / 16 * 16;
+    size_t select_work_bytes = 0;
+    if ((rc = mfa_select_workspace_bytes(n_strings, &select_work_bytes)) != MFA_OK) return rc;
+    if ((rc = d_bytes.alloc(capacity)) != MFA_OK || (rc = d_offsets.alloc((n_strings + 1) * 8)) != MFA_OK || (rc = d_results.alloc(n_strings)) != MFA_OK ||
+        (rc = d_select_work.alloc(select_work_bytes)) != MFA_OK) return rc;
+    rc = mfa_split_text_write(n ? (const uint8_t*)d_text.p : nullptr, n, mode, d_work.p, d_split_info, (uint8_t*)d_bytes.p, capacity,
+                              (uint64_t*)d_offsets.p, n_strings, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    if (n_strings) {
+        rc = mfa_match_batch(img, (const uint8_t*)d_bytes.p, (const uint64_t*)d_offsets.p, n_strings, (uint8_t*)d_results.p, device, nullptr);
+        if (rc != MFA_OK) return rc;
+    }
+    const uint32_t flags = MFA_SELECT_NEWLINE | (invert ? MFA_SELECT_INVERT : 0u);
+    rc = mfa_select_count((const uint8_t*)d_results.p, (const uint64_t*)d_offsets.p, n_strings, flags, d_select_work.p, d_select_info, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    if (hipMemcpy(&infos, d_infos.p, sizeof infos, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;      // the one read-back of the info
+    *longest = infos.split.max_string_bytes;
+    if (infos.split.overflow) return MFA_ERR_INVALID_ARG;        // (exact room was given: cannot happen)
+    if (infos.split.max_string_bytes > longest_allowed) return MFA_OK;      // the caller's other way
+    *n_unanswered = infos.select.n_unanswered;
+    if ((rc = d_out.alloc(infos.select.n_bytes)) != MFA_OK || (rc = d_out_offsets.alloc((infos.select.n_selected + 1) * 8)) != MFA_OK) return rc;
+    rc = mfa_select_write((const uint8_t*)d_bytes.p, (const uint64_t*)d_offsets.p, (const uint8_t*)d_results.p, n_strings, flags, d_select_work.p,
+                          d_select_info, (uint8_t*)d_out.p, infos.select.n_bytes, (uint64_t*)d_out_offsets.p, nullptr, infos.select.n_selected, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    out.resize(infos.select.n_bytes);
+    if (infos.select.n_bytes && hipMemcpy(&out[0], d_out.p, infos.select.n_bytes, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;      // exactly n_bytes
     return MFA_OK;
 }

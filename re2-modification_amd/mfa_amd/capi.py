@@ -22,7 +22,8 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_match_batch_resume", "mfa_match_batch_resume_host", "mfa_last_dfa_spec",
            "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split",
            "mfa_match_batch_resume_set_wide", "mfa_match_batch_resume_set_wide_host", "mfa_image_resume_state_bytes",
-           "mfa_split_tile_bytes", "mfa_split_workspace_bytes", "mfa_split_text_count", "mfa_split_text_write"]
+           "mfa_split_tile_bytes", "mfa_split_workspace_bytes", "mfa_split_text_count", "mfa_split_text_write",
+           "mfa_select_workspace_bytes", "mfa_select_count", "mfa_select_write"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 SET_STATE_WORDS = 12                                                        # a record of mfa_match_batch_resume_set: tag, reserved[3], nodes[8]
@@ -30,6 +31,7 @@ SET_STATE_WIDE_WORDS = 68                                                   # a 
 SET_STATE_START, SET_STATE_LIVE, SET_STATE_INVALID = 0, 1, 0xffffffff       # their tags (records are never stored either)
 REGION_WORDS, REGION_MAX, REGION_OVERFLOW, REGION_MIN_LEN = 16, 15, 0x100, 64
 SPLIT_LINES, SPLIT_TOKENS = 0, 1                                            # modes of the text splitter
+SELECT_INVERT, SELECT_NEWLINE = 1, 2                                        # flags of the selection
 
 
 class MfaError(RuntimeError):
@@ -50,6 +52,12 @@ class SplitInfo(ctypes.Structure):
     """mfa_split_info: 32 bytes of device memory"""
     _fields_ = [("n_strings", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("max_string_bytes", ctypes.c_uint64),
                 ("stopped", ctypes.c_uint32), ("overflow", ctypes.c_uint32)]
+
+
+class SelectInfo(ctypes.Structure):
+    """mfa_select_info: 32 bytes of device memory"""
+    _fields_ = [("n_selected", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("n_unanswered", ctypes.c_uint64),
+                ("overflow", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 _lib = None
@@ -115,6 +123,10 @@ def lib():
             L.mfa_split_workspace_bytes.argtypes = [u64, ctypes.POINTER(ctypes.c_size_t)]
             L.mfa_split_text_count.argtypes = [vp, u64, ctypes.c_uint32, ctypes.c_char_p, vp, vp, i32, vp]
             L.mfa_split_text_write.argtypes = [vp, u64, ctypes.c_uint32, vp, vp, vp, u64, vp, u64, i32, vp]
+        if hasattr(L, "mfa_select_count"):                # (as above: an older build)
+            L.mfa_select_workspace_bytes.argtypes = [u64, ctypes.POINTER(ctypes.c_size_t)]
+            L.mfa_select_count.argtypes = [vp, vp, u64, ctypes.c_uint32, vp, vp, i32, vp]
+            L.mfa_select_write.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, u64, vp, vp, u64, i32, vp]
         L.mfa_strerror.argtypes = [i32]
         L.mfa_strerror.restype = ctypes.c_char_p
         L.mfa_version.restype = ctypes.c_char_p
@@ -449,6 +461,55 @@ def split_text(text, mode, stop=None, stream=None):
         d_offsets = torch.empty(n + 1, dtype=torch.int64, device=text.device)
         split_text_write(ptr, n_text, mode, work.data_ptr(), d_info.data_ptr(), d_bytes.data_ptr(), d_bytes.numel(), d_offsets.data_ptr(), n, dev, s)
     return d_bytes, d_offsets, n, {"n_strings": n, "n_bytes": n_bytes, "stopped": head[3] & 0xffffffff, "d_info": d_info}
+
+
+def select_workspace_bytes(n_strings):
+    out = ctypes.c_size_t()
+    _check(lib().mfa_select_workspace_bytes(n_strings, ctypes.byref(out)), "mfa_select_workspace_bytes")
+    return out.value
+
+
+def select_count(d_results_ptr, d_offsets_ptr, n, flags, d_workspace_ptr, d_info_ptr, device=0, stream=0):
+    """mfa_select_count on raw device pointers (ints).  Asynchronous on `stream` (a hipStream_t value)."""
+    _check(lib().mfa_select_count(d_results_ptr, d_offsets_ptr, n, flags, d_workspace_ptr, d_info_ptr, device, ctypes.c_void_p(stream)),
+           "mfa_select_count")
+
+
+def select_write(d_bytes_ptr, d_offsets_ptr, d_results_ptr, n, flags, d_workspace_ptr, d_info_ptr, d_out_bytes_ptr, bytes_capacity,
+                 d_out_offsets_ptr, d_out_indices_ptr, max_selected, device=0, stream=0):
+    """mfa_select_write on raw device pointers (ints; d_out_indices_ptr and, with no capacity, d_out_bytes_ptr may be None).  Asynchronous
+    on `stream` (a hipStream_t value)."""
+    _check(lib().mfa_select_write(d_bytes_ptr, d_offsets_ptr, d_results_ptr, n, flags, d_workspace_ptr, d_info_ptr, d_out_bytes_ptr,
+                                  bytes_capacity, d_out_offsets_ptr, d_out_indices_ptr, max_selected, device, ctypes.c_void_p(stream)),
+           "mfa_select_write")
+
+
+def select(d_bytes, d_offsets, d_results, flags=0, stream=None):
+    """The strings of a batch that a match call answered 1 (0 with SELECT_INVERT), compacted on the device.  d_bytes, d_offsets: the batch
+    as the match calls take it (torch CUDA uint8 and int64 tensors, n + 1 offsets); d_results: its n result bytes; flags: SELECT_INVERT,
+    SELECT_NEWLINE.  Count, ONE read-back of the 32 bytes of the info record, exact allocation, write -- all on `stream` (default: the
+    current one).  Returns (out_bytes, out_offsets, out_indices, info): a uint8 tensor of n_bytes rounded up to 16 (at least 16) bytes, of
+    which the first n_bytes are the output; int64 tensors of n_selected + 1 offsets and n_selected indices; and info = {"n_selected",
+    "n_bytes", "n_unanswered"} as read back, plus "d_info": the device record (int64[4]), where the write call leaves overflow."""
+    import torch
+    assert d_bytes.dtype == torch.uint8 and d_results.dtype == torch.uint8 and d_offsets.dtype == torch.int64
+    assert d_bytes.is_cuda and d_offsets.is_contiguous() and d_results.is_contiguous() and d_bytes.is_contiguous()
+    n = d_offsets.numel() - 1
+    assert n >= 0 and d_results.numel() >= n
+    dev = d_bytes.device.index or 0
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(d_bytes.device)):      # (allocations belong to that stream too)
+        s = torch.cuda.current_stream(d_bytes.device).cuda_stream
+        work = torch.empty(max(select_workspace_bytes(n), 16), dtype=torch.uint8, device=d_bytes.device)
+        d_info = torch.zeros(4, dtype=torch.int64, device=d_bytes.device)
+        select_count(d_results.data_ptr(), d_offsets.data_ptr(), n, flags, work.data_ptr(), d_info.data_ptr(), dev, s)
+        head = [int(x) for x in d_info.cpu()]                 # the one read-back (it waits for the count)
+        n_selected, n_bytes = head[0], head[1]
+        out_bytes = torch.empty(max((n_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=d_bytes.device)
+        out_offsets = torch.empty(n_selected + 1, dtype=torch.int64, device=d_bytes.device)
+        out_indices = torch.empty(n_selected, dtype=torch.int64, device=d_bytes.device)
+        select_write(d_bytes.data_ptr(), d_offsets.data_ptr(), d_results.data_ptr(), n, flags, work.data_ptr(), d_info.data_ptr(),
+                     out_bytes.data_ptr(), out_bytes.numel(), out_offsets.data_ptr(), out_indices.data_ptr() if n_selected else None, n_selected, dev, s)
+    return out_bytes, out_offsets, out_indices, {"n_selected": n_selected, "n_bytes": n_bytes, "n_unanswered": head[2], "d_info": d_info}
 
 
 def device_count():

@@ -17,12 +17,12 @@
 #include "nfa_set_split_core.h"
 
 using namespace mfa;
+using emul::fail;
+using emul::list_of;
 
 struct Counts { uint64_t rewalked = 0, serial_strings = 0, serial_bytes = 0, home_guesses = 0; };
 
 static const SetRec kStartRec = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-
-static void fail(const char* what) { fprintf(stderr, "%s\n", what); exit(5); }
 
 // one queued string [b, e) from the record `first`, as the kernels treat it: its final record
 template <bool REV, int W>
@@ -106,18 +106,6 @@ static int run(const HostImage& set, const std::vector<SetRec>& starts, const st
            (unsigned long long)cnt.serial_bytes, home_nodes, (unsigned long long)cnt.home_guesses, results.c_str());
     free(batch.bytes);
     return 0;
-}
-
-// "16,32,64" -> the numbers
-static std::vector<uint64_t> list_of(const char* arg) {
-    std::vector<uint64_t> out;
-    for (const char* p = arg; *p;) {
-        char* end = nullptr;
-        out.push_back(strtoull(p, &end, 10));
-        if (end == p) { fprintf(stderr, "bad list %s\n", arg); exit(2); }
-        p = *end == ',' ? end + 1 : end;
-    }
-    return out;
 }
 
 int main(int argc, char** argv) {

@@ -12,8 +12,7 @@
 //   Exit code 3: the image gets no wave tables (an epsilon cycle, more than 2048 nodes).
 #include <string>
 
-#include "emul_common.h"
-#include "nfa_set_wave_core.h"
+#include "emul_wave.h"
 #include "wave_lanes.h"
 
 using namespace mfa;
@@ -67,13 +66,8 @@ static int run_match(const HostImage& set, const std::vector<uint8_t>& file) {
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: nfa_set_wave_emul step IMAGE.blob | match IMAGE.blob BATCH.bin\n"); return 2; }
     const std::string mode = argv[1];
-    const std::vector<uint8_t> blob = emul::slurp(argv[2]);
     HostImage tab, set;
-    if (parse_blob(blob.data(), blob.size(), tab) != MFA_OK || tab.h.kind != MFA_KIND_NFA) { fprintf(stderr, "not a memory-less image\n"); return 2; }
-    set = tab;
-    const int rc = nfa_set_wave_build(set);
-    if (rc != MFA_OK) { fprintf(stderr, "no wave tables: %d\n", rc); return 3; }
-    if (!set.set_wave || set.set_tables[SET_H_WORDS] != wave_words_of(set.h.n_nodes)) { fprintf(stderr, "not wave tables\n"); return 5; }
+    emul::load_wave(argv[2], set, &tab);
     if (mode == "step") {
         std::vector<std::string> sets;
         if (tabulate_nfa(tab, MFA_MAX_DFA_STATES, &sets) != MFA_OK) { fprintf(stderr, "not tabulated\n"); return 2; }

@@ -19,20 +19,14 @@
 //   Exit code 3: the image gets no wave tables (an epsilon cycle, more than 2048 nodes).
 #include <string>
 
-#include "emul_common.h"
-#include "nfa_set_wave_core.h"
+#include "emul_wave.h"
 #include "wave_lanes_resume.h"
 
 using namespace mfa;
 typedef emul::WaveHostResume P;
 
-// n records in exactly n * 272 bytes, 16-byte aligned (at least one record's room, so that n == 0 allocates something)
-static uint32_t* new_records(uint64_t n) {
-    const size_t bytes = (size_t)(n ? n : 1) * kWaveStateWords * 4u;
-    uint32_t* rec = (uint32_t*)aligned_alloc(16, bytes);
-    memset(rec, 0, bytes);
-    return rec;
-}
+// n zeroed records in exactly n * 272 bytes
+static uint32_t* new_records(uint64_t n) { return emul::new_records(n, kWaveStateWords, 0); }
 
 template <bool REV>
 static int run_pieces(const HostImage& set, const std::vector<uint8_t>& states, int n_rounds, char** round_files) {
@@ -42,27 +36,18 @@ static int run_pieces(const HostImage& set, const std::vector<uint8_t>& states, 
     uint64_t n = 0;
     uint32_t* rec = nullptr;
     for (int r = 0; r < n_rounds; r++) {
-        const std::vector<uint8_t> file = emul::slurp(round_files[r]);
-        uint64_t n_here, total;
-        if (file.size() < 16) { fprintf(stderr, "%s: not a round\n", round_files[r]); return 2; }
-        memcpy(&n_here, file.data(), 8); memcpy(&total, file.data() + 8, 8);
-        if (file.size() != 16 + (n_here + 1) * 8 + total || (r > 0 && n_here != n)) { fprintf(stderr, "%s: does not fit the batch\n", round_files[r]); return 2; }
+        const emul::Round round = emul::read_round(round_files[r], r == 0, n);      // exactly the library's read rule: ASan sees a byte beyond it
+        const std::vector<uint64_t>& off = round.off;
         if (r == 0) {
-            n = n_here;
             if (!states.empty() && states.size() != n * kWaveStateWords * 4u) { fprintf(stderr, "the states do not fit the batch\n"); return 2; }
             rec = new_records(n);
             if (!states.empty()) memcpy(rec, states.data(), states.size());
         }
-        std::vector<uint64_t> off(n + 1);
-        memcpy(off.data(), file.data() + 16, (n + 1) * 8);
-        uint8_t* bytes = emul::padded(file.data() + 16 + (n + 1) * 8, (size_t)total);      // exactly the library's read rule: ASan sees a byte beyond it
         std::string out;
-        for (uint64_t k = 0; k < n; k++) {
-            if (off[k + 1] < off[k]) { fprintf(stderr, "round %d, string %llu: offsets go down\n", r, (unsigned long long)k); return 2; }
-            out.push_back((char)('0' + nfa_wave_resume_piece<REV, P>(t, n_nodes, W, stack.data(), bytes, off[k], off[k + 1], rec + k * kWaveStateWords)));
-        }
+        for (uint64_t k = 0; k < n; k++)
+            out.push_back((char)('0' + nfa_wave_resume_piece<REV, P>(t, n_nodes, W, stack.data(), round.bytes, off[k], off[k + 1], rec + k * kWaveStateWords)));
         puts(out.c_str());
-        free(bytes);
+        free(round.bytes);
     }
     for (uint64_t k = 0; k < n; k++)
         for (uint32_t j = 0; j < kWaveStateWords; j++) printf("%08x%c", rec[k * kWaveStateWords + j], j + 1u == kWaveStateWords ? '\n' : ' ');
@@ -104,15 +89,10 @@ static int run_table(const HostImage& tab, const HostImage& set, const std::vect
 int main(int argc, char** argv) {
     if (argc < 4) { fprintf(stderr, "usage: nfa_set_wave_resume_emul pieces IMAGE.blob STATES.bin|- ROUND.bin... | table IMAGE.blob BATCH.bin\n"); return 2; }
     const std::string mode = argv[1];
-    const std::vector<uint8_t> blob = emul::slurp(argv[2]);
     HostImage tab, set;
-    if (parse_blob(blob.data(), blob.size(), tab) != MFA_OK || tab.h.kind != MFA_KIND_NFA) { fprintf(stderr, "not a memory-less image\n"); return 2; }
-    set = tab;
-    const int rc = nfa_set_wave_build(set);
-    if (rc != MFA_OK) { fprintf(stderr, "no wave tables: %d\n", rc); return 3; }
-    if (!set.set_wave || set.set_tables[SET_H_WORDS] != wave_words_of(set.h.n_nodes)) { fprintf(stderr, "not wave tables\n"); return 5; }
+    emul::load_wave(argv[2], set, &tab);
     const bool rev = set.h.is_reversed != 0;
-    printf("tables %zu %u %u\n", set.set_tables.size(), set.set_tables[SET_H_WORDS], set.set_tables[SET_H_DEPTH]);
+    emul::print_tables(set);
     if (mode == "pieces" && argc >= 5) {
         const std::vector<uint8_t> states = std::string(argv[3]) == "-" ? std::vector<uint8_t>() : emul::slurp(argv[3]);
         return rev ? run_pieces<true>(set, states, argc - 4, argv + 4) : run_pieces<false>(set, states, argc - 4, argv + 4);

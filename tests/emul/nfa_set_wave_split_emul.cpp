@@ -22,25 +22,20 @@
 //   Exit code 3: the image gets no wave tables.
 #include <string>
 
-#include "emul_common.h"
+#include "emul_wave.h"
 #include "nfa_set_wave_split_core.h"
 #include "wave_lanes_resume.h"
 
 using namespace mfa;
 typedef emul::WaveHostResume P;
 typedef WaveRec<P> Rec;
+using emul::fail;
+using emul::list_of;
 
 struct Counts { uint64_t rewalked = 0, serial_strings = 0, serial_bytes = 0, home_guesses = 0, invalid_ends = 0; };
 
-static void fail(const char* what) { fprintf(stderr, "%s\n", what); exit(5); }
-
-// n records in exactly n * 272 bytes, 16-byte aligned
-static uint32_t* new_records(uint64_t n) {
-    const size_t bytes = (size_t)(n ? n : 1) * kWaveStateWords * 4u;
-    uint32_t* rec = (uint32_t*)aligned_alloc(16, bytes);
-    memset(rec, 0xa5, bytes);                                             // (a record that is read before it is written does not look like one)
-    return rec;
-}
+// n records in exactly n * 272 bytes; a record that is read before it is written does not look like one
+static uint32_t* new_records(uint64_t n) { return emul::new_records(n, kWaveStateWords, 0xa5); }
 
 struct Ctx {
     NfaSetView t;
@@ -137,25 +132,17 @@ static int run_pieces(const Ctx& x, const std::vector<uint8_t>& states, uint64_t
     uint32_t* whole = new_records(1);
     Counts cnt;
     for (int r = 0; r < n_rounds; r++) {
-        const std::vector<uint8_t> file = emul::slurp(round_files[r]);
-        uint64_t n_here, total;
-        if (file.size() < 16) { fprintf(stderr, "%s: not a round\n", round_files[r]); return 2; }
-        memcpy(&n_here, file.data(), 8); memcpy(&total, file.data() + 8, 8);
-        if (file.size() != 16 + (n_here + 1) * 8 + total || (r > 0 && n_here != n)) { fprintf(stderr, "%s: does not fit the batch\n", round_files[r]); return 2; }
+        const emul::Round round = emul::read_round(round_files[r], r == 0, n);
+        const std::vector<uint64_t>& off = round.off;
+        const uint8_t* bytes = round.bytes;
         if (r == 0) {
-            n = n_here;
             if (!states.empty() && states.size() != n * kWaveStateWords * 4u) { fprintf(stderr, "the states do not fit the batch\n"); return 2; }
-            rec = new_records(n);
-            memset(rec, 0, (size_t)(n ? n : 1) * kWaveStateWords * 4u);
+            rec = emul::new_records(n, kWaveStateWords, 0);                // (the caller's records: every string at its start)
             if (!states.empty()) memcpy(rec, states.data(), states.size());
         }
-        std::vector<uint64_t> off(n + 1);
-        memcpy(off.data(), file.data() + 16, (n + 1) * 8);
-        uint8_t* bytes = emul::padded(file.data() + 16 + (n + 1) * 8, (size_t)total);
         std::string out;
         uint64_t queued = 0;
         for (uint64_t k = 0; k < n; k++) {
-            if (off[k + 1] < off[k]) { fprintf(stderr, "round %d, string %llu: offsets go down\n", r, (unsigned long long)k); return 2; }
             const uint64_t b = off[k], e = off[k + 1];
             uint32_t* mine = rec + k * kWaveStateWords;
             memcpy(whole, mine, kWaveStateWords * 4u);
@@ -177,7 +164,7 @@ static int run_pieces(const Ctx& x, const std::vector<uint8_t>& states, uint64_t
             out.push_back((char)('0' + res));
         }
         printf("%s %llu\n", out.c_str(), (unsigned long long)queued);
-        free(bytes);
+        free(round.bytes);
     }
     for (uint64_t k = 0; k < n; k++)
         for (uint32_t j = 0; j < kWaveStateWords; j++) printf("%08x%c", rec[k * kWaveStateWords + j], j + 1u == kWaveStateWords ? '\n' : ' ');
@@ -186,30 +173,14 @@ static int run_pieces(const Ctx& x, const std::vector<uint8_t>& states, uint64_t
     return 0;
 }
 
-// "16,32,64" -> the numbers
-static std::vector<uint64_t> list_of(const char* arg) {
-    std::vector<uint64_t> out;
-    for (const char* p = arg; *p;) {
-        char* end = nullptr;
-        out.push_back(strtoull(p, &end, 10));
-        if (end == p) { fprintf(stderr, "bad list %s\n", arg); exit(2); }
-        p = *end == ',' ? end + 1 : end;
-    }
-    return out;
-}
-
 int main(int argc, char** argv) {
     const char* usage = "usage: nfa_set_wave_split_emul split IMAGE.blob BATCH.bin CHUNK LOOKBACK ROUNDS [DEPTH] | pieces IMAGE.blob STATES.bin|- CHUNK LOOKBACK ROUNDS SPLIT_MIN ROUND.bin...\n";
     if (argc < 7) { fputs(usage, stderr); return 2; }
     const std::string mode = argv[1];
     const bool pieces = mode == "pieces";
     if ((!pieces && mode != "split") || (pieces && argc < 9)) { fputs(usage, stderr); return 2; }
-    const std::vector<uint8_t> blob = emul::slurp(argv[2]);
     HostImage set;
-    if (parse_blob(blob.data(), blob.size(), set) != MFA_OK || set.h.kind != MFA_KIND_NFA) { fprintf(stderr, "not a memory-less image\n"); return 2; }
-    const int rc = nfa_set_wave_build(set);
-    if (rc != MFA_OK) { fprintf(stderr, "no wave tables: %d\n", rc); return 3; }
-    if (!set.set_wave || set.set_tables[SET_H_WORDS] != wave_words_of(set.h.n_nodes)) { fprintf(stderr, "not wave tables\n"); return 5; }
+    emul::load_wave(argv[2], set);
     const std::vector<uint64_t> chunks = list_of(argv[4]), lookbacks = list_of(argv[5]), round_counts = list_of(argv[6]);
     for (uint64_t chunk : chunks)
         if (chunk < 16 || (chunk & 15u)) { fprintf(stderr, "bad chunk\n"); return 2; }
@@ -229,7 +200,7 @@ int main(int argc, char** argv) {
         if (chunks.size() != 1 || lookbacks.size() != 1 || round_counts.size() != 1) { fprintf(stderr, "pieces: one chunk, one lookback, one round count\n"); return 2; }
         const std::vector<uint8_t> states = std::string(argv[3]) == "-" ? std::vector<uint8_t>() : emul::slurp(argv[3]);
         const uint64_t split_min = strtoull(argv[7], nullptr, 10);
-        printf("tables %zu %u %u\n", set.set_tables.size(), set.set_tables[SET_H_WORDS], set.set_tables[SET_H_DEPTH]);
+        emul::print_tables(set);
         const int r = rev ? run_pieces<true>(x, states, chunks[0], (uint32_t)lookbacks[0], (uint32_t)round_counts[0], split_min, argc - 8, argv + 8)
                           : run_pieces<false>(x, states, chunks[0], (uint32_t)lookbacks[0], (uint32_t)round_counts[0], split_min, argc - 8, argv + 8);
         free(home);

@@ -1,41 +1,18 @@
-"""What tests/test_select_cpu.py and tests/test_select_gpu.py share: the rule of the selection in Python, the host harness
-tests/emul/select_emul.cpp built once per session, its case files and its output, the edge cases and the seeded random ones --
+"""What tests/test_select_cpu.py and tests/test_select_gpu.py share: the rule of the selection in Python, the case files of the host harness
+tests/emul/select_emul.cpp (built by testlib.emul_exe) and its output, the edge cases and the seeded random ones --
 TEST INFRASTRUCTURE ONLY: no tests, no fixtures, no marks in here."""
-import atexit
 import collections
 import os
 import re
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
-import oracle_lib
-from testlib import EMUL_DIR
+from testlib import CSRC
 
-CSRC = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "csrc")
 INVERT, NEWLINE = 1, 2
 ALL_FLAGS = (0, INVERT, NEWLINE, INVERT | NEWLINE)
-
-_built = {}
-
-
-def select_emul_exe(flags=""):
-    """tests/emul/select_emul.cpp through the HIP shim, with `flags` behind the caller's EMUL_FLAGS, once per session, in a temporary
-    directory of its own; the compiler is heard only when it fails"""
-    if flags not in _built:
-        folder = tempfile.mkdtemp(prefix="select_emul_")
-        atexit.register(shutil.rmtree, folder, ignore_errors=True)
-        exe = os.path.join(folder, "select_emul")
-        cmd = (["g++", "-O2", "-g", "-std=c++17"] + (os.environ.get("EMUL_FLAGS", "") + " " + flags).split()
-               + ["-Wall", "-Ishim", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-unused-variable", "-I" + CSRC,
-                  "-I" + os.path.join(oracle_lib.ROOT, "include"), "-o", exe, "select_emul.cpp"])
-        p = subprocess.run(cmd, cwd=EMUL_DIR, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, "building select_emul failed:\n%s" % p.stdout
-        _built[flags] = exe
-    return _built[flags]
 
 
 def geometry():

@@ -8,8 +8,7 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
-
-CSRC = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "csrc")
+from testlib import CSRC
 
 
 @pytest.fixture(scope="module")

@@ -15,10 +15,7 @@ import pytest
 
 import nfa_fuzz
 import oracle_lib
-import setresume_lib
-import setsplit_lib
-import setwave_lib
-import setwavesplit_lib
+import setwalk_lib
 from mfa_amd import capi
 from test_dfa_resume_cpu import run_pieces
 from test_dfa_spec_cpu import run_emul as run_spec
@@ -190,22 +187,22 @@ def test_mixed_core(seed, tmp_path):
 def test_set_resume_core(seed, tmp_path):
     """the nfa_set_resume harness on one image per mask width and direction: pieces in ROUNDS rounds against the oracle, the final
     records against those of the whole strings"""
-    exe = setresume_lib.resume_emul_exe()
+    exe = emul_exe("nfa_set_resume")
     c = nfa_fuzz.cpu_corpus(seed)
     for w in (1, 2, 4, 8):
         for rev in (0, 1):
             im = next(i for i in c if nfa_fuzz.mask_words(i["info"]) == w and i["info"]["is_reversed"] == rev)
-            rounds, is_rev = setresume_lib.piece_rounds(im["blob"], im["strings"], np.random.default_rng(8 * w + rev))
+            rounds, is_rev = setwalk_lib.piece_rounds(im["blob"], im["strings"], np.random.default_rng(8 * w + rev))
             assert is_rev == rev
-            digits, recs = setresume_lib.run_pieces(exe, tmp_path, im["blob"], im["strings"], rounds)
+            digits, recs = setwalk_lib.run_lane_pieces(exe, tmp_path, im["blob"], im["strings"], rounds)
             ora = oracle_lib.OracleImage(im["blob"])
             for r in range(ROUNDS - 1):
                 assert np.array_equal(digits[r], ora.match(seen_so_far(im["strings"], rounds, r, rev))), (im["what"], r)
             differ(digits[-1], im, "nfa_set_resume_emul pieces")
-            whole_digits, whole_recs = setresume_lib.run_pieces(exe, tmp_path, im["blob"], im["strings"], setresume_lib.whole(im["strings"]))
+            whole_digits, whole_recs = setwalk_lib.run_lane_pieces(exe, tmp_path, im["blob"], im["strings"], setwalk_lib.whole(im["strings"]))
             differ(whole_digits[0], im, "nfa_set_resume_emul whole")
             assert np.array_equal(recs, whole_recs), im["what"]
-            setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+            setwalk_lib.check_records_are_clean(recs, im["info"]["n_nodes"], setwalk_lib.LANE_WORDS)
 
 
 # ---- the set walk's split, resume and wave cores: every image of the set corpus -------------------------------------------------------------
@@ -233,11 +230,11 @@ def test_set_split_core(seed, tmp_path):
     Measured, each seed 36 images (34 and the direction twins of those beyond LDS), images with chunks walked again / strings resolved
     serially / home guesses at (16, 64, 3): seed 0: 31, 29, 28; seed 1: 27, 25, 30; seed 2: 28, 24, 25; seed 3: 28, 25, 27.  Tables beyond LDS, in words: seed 0: 30 237 (W 4, 119 classes) and 188 546 (W 8, 201
     classes); seed 1: 29 699 and 190 144; seed 2: 38 123 and 186 916; seed 3: 172 437.  No run refused."""
-    emul = setsplit_lib.split_emul_exe()
+    emul = emul_exe("nfa_set_split")
     c = nfa_fuzz.set_corpus(seed)
     done = rewalked = serial = home = 0
     for im in c:
-        runs = setsplit_lib.run_split(emul, tmp_path, im["blob"], im["strings"], SPLIT_CHUNKS, SPLIT_LOOKBACKS, SPLIT_ROUNDS, run=harness)
+        runs = setwalk_lib.run_lane_split(emul, tmp_path, im["blob"], im["strings"], SPLIT_CHUNKS, SPLIT_LOOKBACKS, SPLIT_ROUNDS, run=harness)
         if runs is None:
             continue
         done += 1
@@ -261,13 +258,13 @@ def test_set_split_core_from_every_set(seed, tmp_path):
     """the resume form: nfa_set_split_emul `every` on the images of 2 to 60 state sets -- every string from {start}, from every tabulated
     node set and from the empty set, every final record held to the whole walk's from the same set -- at (16, 64, 3) and (48, 0, 0).
     Measured: seed 0, 24 images and 69 233 records per setting; seed 1, 24 and 59 153; seed 2, 25 and 72 500; seed 3, 22 and 37 950."""
-    emul = setsplit_lib.split_emul_exe()
+    emul = emul_exe("nfa_set_split")
     done = checks = 0
     for im in nfa_fuzz.set_corpus(seed):
         if not 2 <= states(im) <= 60:
             continue
         for combo in ((16, 64, 3), (48, 0, 0)):
-            runs = setsplit_lib.run_split(emul, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], mode="every", run=harness)
+            runs = setwalk_lib.run_lane_split(emul, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], mode="every", run=harness)
             if runs is None:
                 continue
             (_, counts, digits), = runs
@@ -284,18 +281,18 @@ def test_set_wave_cores(seed, tmp_path):
     """the wave kernels' cores on images they were not made for -- up to 200 byte classes, labels of 0x80 and above, 2 to 130 nodes:
     nfa_set_wave_emul match on every image of the set corpus, nfa_set_wave_split_emul (every string cut, every record held to the whole
     walk's) at (16, 64, 3) and (48, 0, 0), all against the oracle.  Measured: seeds 0 to 3, 36 images each, none refused."""
-    wave, split = setwave_lib.wave_emul_exe(), setwavesplit_lib.wave_split_emul_exe()
+    wave, split = emul_exe("nfa_set_wave"), emul_exe("nfa_set_wave_split")
     done = 0
     for im in nfa_fuzz.set_corpus(seed):
-        got = setwave_lib.run_match(wave, tmp_path, im["blob"], im["strings"], run=harness)
+        got = setwalk_lib.run_match(wave, tmp_path, im["blob"], im["strings"], run=harness)
         if got is not None:
             differ(got, im, "nfa_set_wave_emul match")
             done += 1
         for combo in ((16, 64, 3), (48, 0, 0)):
-            runs = setwavesplit_lib.run_wave_split(split, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], run=harness)
+            runs = setwalk_lib.run_wave_split(split, tmp_path, im["blob"], im["strings"], combo[:1], combo[1:2], combo[2:], run=harness)
             if runs is not None:
                 (_, counts, digits), = runs
-                assert counts["checks"] == len(im["strings"]) and counts["W"] == setwave_lib.words_of(im["info"]["n_nodes"]), (im["what"], combo, counts)
+                assert counts["checks"] == len(im["strings"]) and counts["W"] == setwalk_lib.words_of(im["info"]["n_nodes"]), (im["what"], combo, counts)
                 differ(digits, im, "nfa_set_wave_split_emul, chunk %d lookback %d rounds %d" % combo)
     print("wave harnesses seed %d: %d images" % (seed, done))
 

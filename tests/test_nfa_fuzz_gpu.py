@@ -14,15 +14,12 @@ import numpy as np
 import pytest
 
 import nfa_fuzz
-import setresume_lib
-import setsplit_lib
-import setwaveresume_lib
-import setwavesplit_lib
+import setwalk_lib
 import testlib
 from mfa_amd import capi
 from test_dfa_spec_gpu import prime
 from test_walk_fuzz_gpu import GUARD, answers, guarded, segment_sizes
-from testlib import ROUNDS, cuts_for, expected_split, feed, new_states, pieces_against_whole, rounds_of, states_of
+from testlib import ROUNDS, cuts_for, emul_exe, expected_split, feed, new_states, pieces_against_whole, rounds_of, states_of
 
 pytestmark = pytest.mark.gpu
 
@@ -205,16 +202,16 @@ def test_set_walk(k, im, env):
     d_bytes, d_off, _ = upload(strings)
     compare(call(img, d_bytes, d_off, n, "set walk"), im, "set walk")
     assert img.info()["last_kernel"] == capi.KERNEL_NODESET
-    rounds, is_rev = setresume_lib.piece_rounds(im["blob"], strings, np.random.default_rng(2000 + k))
-    d_states = setresume_lib.new_records(n)
+    rounds, is_rev = setwalk_lib.piece_rounds(im["blob"], strings, np.random.default_rng(2000 + k))
+    d_states = setwalk_lib.new_records(n, setwalk_lib.LANE_WORDS)
     for r in range(ROUNDS):
-        got = setresume_lib.feed_set(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states)
+        got = setwalk_lib.feed_records(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states, setwalk_lib.LANE_WORDS)
     compare(got, im, "set walk in pieces")
-    d_whole = setresume_lib.new_records(n)
-    compare(setresume_lib.feed_set(img, strings, d_whole), im, "set walk, whole strings through the resume call")
-    recs = setresume_lib.records_of(d_states, n)
-    assert np.array_equal(recs, setresume_lib.records_of(d_whole, n))
-    setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+    d_whole = setwalk_lib.new_records(n, setwalk_lib.LANE_WORDS)
+    compare(setwalk_lib.feed_records(img, strings, d_whole, setwalk_lib.LANE_WORDS), im, "set walk, whole strings through the resume call")
+    recs = setwalk_lib.records_of(d_states, n, setwalk_lib.LANE_WORDS)
+    assert np.array_equal(recs, setwalk_lib.records_of(d_whole, n, setwalk_lib.LANE_WORDS))
+    setwalk_lib.check_records_are_clean(recs, im["info"]["n_nodes"], setwalk_lib.LANE_WORDS)
     assert img.info()["last_kernel"] == capi.KERNEL_NODESET
     img.close()
 
@@ -274,7 +271,7 @@ def test_set_split(k, im, chunk, env, tmp_path):
         compare_long(call(img, d_bytes, d_off, len(longs), what), want, longs, im, what)
         report = img.last_set_split()
         assert report[:3] == cut, (what, report)
-        (_, host, digits), = setsplit_lib.run_split(setsplit_lib.split_emul_exe(), tmp_path, im["blob"], longs, (chunk,), (lookback,), (rounds,))
+        (_, host, digits), = setwalk_lib.run_lane_split(emul_exe("nfa_set_split"), tmp_path, im["blob"], longs, (chunk,), (lookback,), (rounds,))
         assert np.array_equal(digits, want), what
         assert report[3:] == (host["rewalked"], host["serial_strings"], host["serial_bytes"]), (im["what"], what, report, host)
     img.close()
@@ -291,26 +288,26 @@ def test_set_split_in_pieces(k, im, env, tmp_path):
     env.setenv("MFA_DFA_CHUNK", "16")
     img = forced(im, env)
     strings, n = im["strings"], len(im["strings"])
-    rounds, is_rev = setresume_lib.piece_rounds(im["blob"], strings, np.random.default_rng(3000 + k))
+    rounds, is_rev = setwalk_lib.piece_rounds(im["blob"], strings, np.random.default_rng(3000 + k))
     assert is_rev == im["info"]["is_reversed"]
-    d_states = setresume_lib.new_records(n)
+    d_states = setwalk_lib.new_records(n, setwalk_lib.LANE_WORDS)
     queued = []
     for r in range(ROUNDS):
         pieces = [s[b:e] for s, (b, e) in zip(strings, rounds[r])]
-        got = setresume_lib.feed_set(img, pieces, d_states, results=not (r % 2 == 1 and r < ROUNDS - 1 and k % 2 == 1))
+        got = setwalk_lib.feed_records(img, pieces, d_states, setwalk_lib.LANE_WORDS, results=not (r % 2 == 1 and r < ROUNDS - 1 and k % 2 == 1))
         queued.append(img.last_set_split()[0])
         assert queued[-1] <= sum(1 for p in pieces if len(p) >= SPLIT_MIN) and img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
     compare(got, im, "split path, strings in pieces")
     assert max(queued) > 0, queued
-    recs = setresume_lib.records_of(d_states, n)
+    recs = setwalk_lib.records_of(d_states, n, setwalk_lib.LANE_WORDS)
     env.setenv("MFA_SET_SPLIT", "0")
-    d_whole = setresume_lib.new_records(n)
-    compare(setresume_lib.feed_set(img, strings, d_whole), im, "MFA_SET_SPLIT=0, whole strings through the resume call")
+    d_whole = setwalk_lib.new_records(n, setwalk_lib.LANE_WORDS)
+    compare(setwalk_lib.feed_records(img, strings, d_whole, setwalk_lib.LANE_WORDS), im, "MFA_SET_SPLIT=0, whole strings through the resume call")
     assert img.last_set_split() == ZEROS
-    assert np.array_equal(recs, setresume_lib.records_of(d_whole, n))
-    digits, recs_host = setresume_lib.run_pieces(setresume_lib.resume_emul_exe(), tmp_path, im["blob"], strings, setresume_lib.whole(strings))
+    assert np.array_equal(recs, setwalk_lib.records_of(d_whole, n, setwalk_lib.LANE_WORDS))
+    digits, recs_host = setwalk_lib.run_lane_pieces(emul_exe("nfa_set_resume"), tmp_path, im["blob"], strings, setwalk_lib.whole(strings))
     assert np.array_equal(digits[0], im["want"]) and np.array_equal(recs, recs_host)
-    setresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+    setwalk_lib.check_records_are_clean(recs, im["info"]["n_nodes"], setwalk_lib.LANE_WORDS)
     assert img.info()["last_kernel"] == capi.KERNEL_NODESET
     img.close()
 
@@ -319,7 +316,7 @@ def forced_wave(im, env):
     env.setenv("MFA_SET_WAVE", "1")
     img = forced(im, env)
     env.delenv("MFA_SET_WAVE")
-    assert img.resume_state_bytes() == 4 * setwaveresume_lib.WORDS
+    assert img.resume_state_bytes() == 4 * setwalk_lib.WIDE_WORDS
     return img
 
 
@@ -332,7 +329,7 @@ def test_wave_kernels_on_the_corpus(k, im, env, tmp_path):
     answers, the header's formulas with the wave arena of 32 768 chunks, and on the long strings alone at 3 rounds and a lookback of 64
     the counts of the host harness"""
     lane, img = forced(im, env), forced_wave(im, env)
-    assert lane.resume_state_bytes() == 4 * setresume_lib.WORDS
+    assert lane.resume_state_bytes() == 4 * setwalk_lib.LANE_WORDS
     strings, n = im["strings"], len(im["strings"])
     d_bytes, d_off, off = upload(strings)
     got = call(img, d_bytes, d_off, n, "wave")
@@ -340,17 +337,17 @@ def test_wave_kernels_on_the_corpus(k, im, env, tmp_path):
     assert np.array_equal(got, call(lane, d_bytes, d_off, n, "lane")) and img.last_set_split() == ZEROS and img.info()["last_kernel"] == capi.KERNEL_NODESET
     lane.close()
     # strings in pieces
-    rounds, is_rev = setwaveresume_lib.three_rounds(im["blob"], strings, np.random.default_rng(4000 + k))
+    rounds, is_rev = setwalk_lib.three_rounds(im["blob"], strings, np.random.default_rng(4000 + k))
     assert is_rev == im["info"]["is_reversed"]
-    buf = setwaveresume_lib.new_records(n)
-    for r in range(setwaveresume_lib.N_ROUNDS):
-        got = setwaveresume_lib.feed_wide(img, setwaveresume_lib.pieces_of(strings, rounds[r]), buf)
+    buf = setwalk_lib.new_records(n, setwalk_lib.WIDE_WORDS)
+    for r in range(setwalk_lib.N_ROUNDS):
+        got = setwalk_lib.feed_records(img, setwalk_lib.pieces_of(strings, rounds[r]), buf, setwalk_lib.WIDE_WORDS)
     compare(got, im, "MFA_SET_WAVE=1, strings in pieces")
-    whole = setwaveresume_lib.new_records(n)
-    compare(setwaveresume_lib.feed_wide(img, strings, whole), im, "MFA_SET_WAVE=1, whole strings through the wide call")
-    recs = setwaveresume_lib.records_of(buf, n)
-    assert np.array_equal(recs, setwaveresume_lib.records_of(whole, n))
-    setwaveresume_lib.check_records_are_clean(recs, im["info"]["n_nodes"])
+    whole = setwalk_lib.new_records(n, setwalk_lib.WIDE_WORDS)
+    compare(setwalk_lib.feed_records(img, strings, whole, setwalk_lib.WIDE_WORDS), im, "MFA_SET_WAVE=1, whole strings through the wide call")
+    recs = setwalk_lib.records_of(buf, n, setwalk_lib.WIDE_WORDS)
+    assert np.array_equal(recs, setwalk_lib.records_of(whole, n, setwalk_lib.WIDE_WORDS))
+    setwalk_lib.check_records_are_clean(recs, im["info"]["n_nodes"], setwalk_lib.WIDE_WORDS)
     # long strings cut
     env.setenv("MFA_DFA_SPLIT_MIN", str(SPLIT_MIN))
     env.setenv("MFA_DFA_CHUNK", "48")
@@ -365,9 +362,9 @@ def test_wave_kernels_on_the_corpus(k, im, env, tmp_path):
     compare_long(call(img, d_bytes, d_off, len(longs), "wave, long only"), want, longs, im, "MFA_SET_WAVE=1, long strings only")
     report = img.last_set_split()
     assert report[:3] == expected_split(off, SPLIT_MIN, 48, WAVE_ARENA) and report[0] == len(longs)
-    (_, host, digits), = setwavesplit_lib.run_wave_split(setwavesplit_lib.wave_split_emul_exe(), tmp_path, im["blob"], longs, (48,), (64,), (3,))
+    (_, host, digits), = setwalk_lib.run_wave_split(emul_exe("nfa_set_wave_split"), tmp_path, im["blob"], longs, (48,), (64,), (3,))
     assert np.array_equal(digits, want)
-    assert report[3:] == tuple(host[key] for key in setwavesplit_lib.COUNT_KEYS), (im["what"], report, host)
+    assert report[3:] == tuple(host[key] for key in setwalk_lib.COUNT_KEYS), (im["what"], report, host)
     img.close()
 
 

@@ -1,14 +1,15 @@
 """Set-walk images on strings given in pieces, on the GPU: mfa_match_batch_resume_set (nfa_set_resume_kernel, csrc/nfa_set.hip) against the CPU
 restatement, against the plain batch call and, record for record, against the host harness that runs the same core
 (tests/emul/nfa_set_resume_emul.cpp), on the corpus and the cuts of tests/test_nfa_set_resume_cpu.py (tests/testlib.py,
-tests/setresume_lib.py); every mask width; the sticky errors; no result bytes; streams and capture; the host entry point."""
+tests/setwalk_lib.py); every mask width; the sticky errors; no result bytes; streams and capture; the host entry point."""
 import numpy as np
 import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setresume_lib import INVALID, LIVE, START, WORDS, check_records_are_clean, feed_set, new_records, piece_rounds, record, records_of, resume_emul_exe, run_pieces, whole
-from testlib import MAX_BYTES, NFA_NAMES, ROUNDS, blob_of, expected, filled, front_end_blob, k_regex, match_on_gpu, rnd, seen_so_far, setwalk_corpus, upload, wide_images, wide_strings
+from setwalk_lib import (INVALID, LANE_WORDS, LIVE, START, check_records_are_clean, feed_records, new_records, piece_rounds, record, records_of, records_view,
+                         run_lane_pieces, whole)
+from testlib import MAX_BYTES, NFA_NAMES, ROUNDS, blob_of, emul_exe, expected, filled, front_end_blob, k_regex, match_on_gpu, rnd, seen_so_far, setwalk_corpus, upload, wide_images, wide_strings
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,7 @@ def env(monkeypatch):
 
 @pytest.fixture(scope="module")
 def emul():
-    return resume_emul_exe()
+    return emul_exe("nfa_set_resume")
 
 
 def forced(env, blob):
@@ -52,17 +53,17 @@ def pieces_against_whole(img, emul, tmp_path, blob, strings, want, rng, what):
     n_nodes = image.blob_info(blob)["n_nodes"]
     rounds, is_rev = piece_rounds(blob, strings, rng)
     ora = oracle_lib.OracleImage(blob)
-    d_states = new_records(n)
+    d_states = new_records(n, LANE_WORDS)
     for r in range(ROUNDS):
-        got = feed_set(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states)
+        got = feed_records(img, [s[b:e] for s, (b, e) in zip(strings, rounds[r])], d_states, LANE_WORDS)
         mismatch(got, want if r == ROUNDS - 1 else ora.match(seen_so_far(strings, rounds, r, is_rev)), strings, "%s round %d" % (what, r))
     bookkeeping(img)
-    d_whole = new_records(n)
-    res_whole = feed_set(img, strings, d_whole)
-    recs, recs_whole = records_of(d_states, n), records_of(d_whole, n)
-    _, recs_host = run_pieces(emul, tmp_path, blob, strings, whole(strings))
+    d_whole = new_records(n, LANE_WORDS)
+    res_whole = feed_records(img, strings, d_whole, LANE_WORDS)
+    recs, recs_whole = records_of(d_states, n, LANE_WORDS), records_of(d_whole, n, LANE_WORDS)
+    _, recs_host = run_lane_pieces(emul, tmp_path, blob, strings, whole(strings))
     assert np.array_equal(recs, recs_whole) and np.array_equal(recs_whole, recs_host), what
-    check_records_are_clean(recs, n_nodes)
+    check_records_are_clean(recs, n_nodes, LANE_WORDS)
     assert (recs[:, 0] == LIVE).all()
     assert np.array_equal(res_whole, match_on_gpu(img, strings, exact=True)[0]) and np.array_equal(res_whole, want), what
     bookkeeping(img)
@@ -74,11 +75,11 @@ def fewer_than_a_wave(img, strings, want, recs_whole, what):
     few = list(range(len(strings) - 45, len(strings)))
     is_rev = img.info()["is_reversed"]
     halves = [[strings[k][:len(strings[k]) // 2] for k in few], [strings[k][len(strings[k]) // 2:] for k in few]]
-    d_states = new_records(45)
+    d_states = new_records(45, LANE_WORDS)
     for pieces in (halves[::-1] if is_rev else halves):
-        got = feed_set(img, pieces, d_states)
+        got = feed_records(img, pieces, d_states, LANE_WORDS)
     mismatch(got, want[few], [strings[k] for k in few], what + " (45 strings)")
-    assert np.array_equal(records_of(d_states, 45), recs_whole[few]), what
+    assert np.array_equal(records_of(d_states, 45, LANE_WORDS), recs_whole[few]), what
 
 
 @pytest.mark.parametrize("rev", [0, 1], ids=["forward", "reversed"])
@@ -130,24 +131,25 @@ def test_sticky_errors_and_dead_on_entry(env):
     tail = b"abb" + b"abb" + b"aa"                                                 # strings 6, 7, 8
     big[e:e + len(tail)] = torch.tensor(list(tail), dtype=torch.uint8)
     off = torch.tensor([0, 4, 8, 12, 16, 20, e, e + 3, e + 6, e + 8], dtype=torch.int64, device="cuda")
-    rows = np.stack([record(2), record(INVALID), record(LIVE, [1 << n_nodes]), record(LIVE, [1, 0, 0, 0, 0, 0, 0, 1]), record(START, [], (0, 0, 9)), record(START),
-                     record(LIVE), record(START), record(START, [0xdeadbeef] * 8)])
+    rows = np.stack([record(LANE_WORDS, 2), record(LANE_WORDS, INVALID), record(LANE_WORDS, LIVE, [1 << n_nodes]), record(LANE_WORDS, LIVE, [1, 0, 0, 0, 0, 0, 0, 1]),
+                     record(LANE_WORDS, START, [], (0, 0, 9)), record(LANE_WORDS, START), record(LANE_WORDS, LIVE), record(LANE_WORDS, START),
+                     record(LANE_WORDS, START, [0xdeadbeef] * 8)])
     n = len(rows)
-    d_states = new_records(n, rows)
+    d_states = new_records(n, LANE_WORDS, rows)
     res = filled(n)
-    img.match_tensors_resume_set(big, off, d_states, res)
+    img.match_tensors_resume_set(big, off, records_view(d_states, n, LANE_WORDS), res)
     torch.cuda.synchronize()
-    recs = records_of(d_states, n)
+    recs = records_of(d_states, n, LANE_WORDS)
     assert list(res.cpu().numpy()) == [2] * 6 + [0, 1, 0]
     assert (recs[:6, 0] == INVALID).all() and not recs[:6, 1:].any() and list(recs[6]) == [LIVE] + [0] * 11
     assert recs[7, 0] == LIVE and recs[8, 0] == LIVE and recs[7, 4] != 0 and recs[8, 4] != 0
-    check_records_are_clean(recs, n_nodes)
+    check_records_are_clean(recs, n_nodes, LANE_WORDS)
     # a valid piece for every string: the errors stay, the dead stays, the others go on ("abb" + "abb" is accepted, "aa" + "ab" is not)
-    got = feed_set(img, [b"abb"] * 8 + [b"ab"], d_states)
-    recs = records_of(d_states, n)
+    got = feed_records(img, [b"abb"] * 8 + [b"ab"], d_states, LANE_WORDS)
+    recs = records_of(d_states, n, LANE_WORDS)
     assert list(got) == [2] * 6 + [0, 1, 0]
     assert (recs[:6, 0] == INVALID).all() and not recs[:6, 1:].any() and list(recs[6]) == [LIVE] + [0] * 11 and recs[8, 4] != 0
-    check_records_are_clean(recs, n_nodes)
+    check_records_are_clean(recs, n_nodes, LANE_WORDS)
     del big
     torch.cuda.empty_cache()
 
@@ -161,10 +163,10 @@ def test_no_result_bytes_on_intermediate_rounds(env):
     thirds = [[s[k * len(s) // 3:(k + 1) * len(s) // 3] for s in strings] for k in range(3)]
     if img.info()["is_reversed"]:
         thirds = thirds[::-1]
-    d_states = new_records(len(strings))
-    assert feed_set(img, thirds[0], d_states, results=False) is None
-    assert feed_set(img, thirds[1], d_states, results=False) is None
-    got = feed_set(img, thirds[2], d_states)
+    d_states = new_records(len(strings), LANE_WORDS)
+    assert feed_records(img, thirds[0], d_states, LANE_WORDS, results=False) is None
+    assert feed_records(img, thirds[1], d_states, LANE_WORDS, results=False) is None
+    got = feed_records(img, thirds[2], d_states, LANE_WORDS)
     want = oracle_lib.OracleImage(blob).match(strings)
     assert 0 < int(want.sum()) < len(strings)
     mismatch(got, want, strings, "no result bytes")
@@ -185,13 +187,13 @@ def test_two_streams_one_image(env):
         strings = [rnd(b"ab", ln, rng) for ln in lens]
         strings = [s[:-3] + b"abb" if (k + v) % 2 and len(s) >= 3 else s for k, s in enumerate(strings)]
         rounds = [upload([s[r * len(s) // 3:(r + 1) * len(s) // 3] for s in strings], exact=True) for r in range(3)]
-        work.append((rounds, new_records(len(lens)), filled(len(lens)), ora.match(strings)))
+        work.append((rounds, new_records(len(lens), LANE_WORDS), filled(len(lens)), ora.match(strings)))
     assert not np.array_equal(work[0][3], work[1][3])
     torch.cuda.synchronize()
     for r in range(3):
         for v in range(2):
             rounds, d_states, res, _ = work[v]
-            img.match_tensors_resume_set(rounds[r][0], rounds[r][1], d_states, res if r == 2 else None, stream=streams[v])
+            img.match_tensors_resume_set(rounds[r][0], rounds[r][1], records_view(d_states, len(lens), LANE_WORDS), res if r == 2 else None, stream=streams[v])
     torch.cuda.synchronize()
     for rounds, d_states, res, want in work:
         assert np.array_equal(res.cpu().numpy(), want)
@@ -215,7 +217,7 @@ def test_resume_set_call_is_capturable(env):
     want_first, want_joined = ora.match(first), ora.match(joined)
     assert 0 < int(want_first.sum()) < len(first) and 0 < int(want_joined.sum()) < len(first) and not np.array_equal(want_first, want_joined)
     d_bytes, d_off, _ = upload(first, exact=True)
-    d_states = new_records(len(first))
+    d_states = records_view(new_records(len(first), LANE_WORDS), len(first), LANE_WORDS)
     res = filled(len(first))
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -244,13 +246,13 @@ def test_host_entry_point(env):
     strings = [b"ab" * 50 + b"abb", b"abb", b"", b"abz" * 9, b"b" * 700 + b"abb"]
     img = forced(env, blob)
     assert not img.info()["is_reversed"]
-    states = np.zeros(len(strings) * WORDS, dtype=np.uint32)
+    states = np.zeros(len(strings) * LANE_WORDS, dtype=np.uint32)
     d1, o1 = oracle_lib.pack([s[:len(s) // 2] for s in strings])
     d2, o2 = oracle_lib.pack([s[len(s) // 2:] for s in strings])
     assert img.match_host_resume_set(np.concatenate([d1, np.zeros(16, np.uint8)]), o1, states, want_results=False) is None
     got = img.match_host_resume_set(np.concatenate([d2, np.zeros(16, np.uint8)]), o2, states)
     assert list(got) == list(oracle_lib.OracleImage(blob).match(strings)) == [1, 1, 0, 0, 1]
-    recs = states.reshape(len(strings), WORDS)
-    check_records_are_clean(recs, img.info()["n_nodes"])
+    recs = states.reshape(len(strings), LANE_WORDS)
+    check_records_are_clean(recs, img.info()["n_nodes"], LANE_WORDS)
     assert list(recs[:, 0]) == [LIVE] * 5 and list(recs[3]) == [LIVE] + [0] * 11      # "abz...": dead
     bookkeeping(img)

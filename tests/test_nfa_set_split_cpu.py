@@ -8,14 +8,13 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
-from setresume_lib import mask_words
-from setsplit_lib import CHUNKS, COUNTER, LOOKBACKS, PREFIX, ROUNDS, ab_strings, fixture_corpus, k_blob, run_split, split_emul_exe
-from testlib import NFA_NAMES, front_end_blob, out_offsets, wide_images, wide_strings
+from setwalk_lib import CHUNKS, COUNTER, LOOKBACKS, PREFIX, REPAIR_ROUNDS, ab_strings, fixture_corpus, k_blob, mask_words, run_lane_split
+from testlib import NFA_NAMES, emul_exe, front_end_blob, out_offsets, wide_images, wide_strings
 
 
 @pytest.fixture(scope="module")
 def emul():
-    return split_emul_exe()
+    return emul_exe("nfa_set_split")
 
 
 def check_all(runs, want, strings, what):
@@ -38,7 +37,7 @@ def test_fixtures_forced_onto_the_set_walk(emul, name, rev, tmp_path):
     want = oracle_lib.OracleImage(blob).match(strings)
     if not name.startswith("nfa_dot"):
         assert 0 < int(want.sum()) < len(strings)
-    runs = run_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, ROUNDS)
+    runs = run_lane_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS)
     assert len(runs) == 36 and runs[0][1]["W"] == mask_words(image.blob_info(blob)["n_nodes"])
     check_all(runs, want, strings, "%s rev %d" % (name, rev))
 
@@ -51,7 +50,7 @@ def test_wider_masks_and_deep_chains(emul, tmp_path):
         strings = wide_strings(rng, n=120)
         want = oracle_lib.OracleImage(blob).match(strings)
         assert 0 < int(want.sum()) < len(strings), key
-        runs = run_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, ROUNDS)
+        runs = run_lane_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS)
         check_all(runs, want, strings, key)
         seen_w.add(runs[0][1]["W"])
     assert {2, 4, 8} <= seen_w
@@ -63,7 +62,7 @@ def test_resume_form_from_every_node_set(emul, name, rev, tmp_path):
     """entered from every node set tabulate_nfa hands out for the image, and from the empty set, as mfa_match_batch_resume_set enters a piece"""
     blob, strings = fixture_corpus(name, rev)
     want = oracle_lib.OracleImage(blob).match(strings)
-    runs = run_split(emul, tmp_path, blob, strings, (16, 64), (0, 256), (0, 3), mode="every")
+    runs = run_lane_split(emul, tmp_path, blob, strings, (16, 64), (0, 256), (0, 3), mode="every")
     for _, got, res in runs:
         assert got["checks"] % len(strings) == 0 and got["checks"] // len(strings) >= 4      # START, the empty set, {start}, and more
         assert np.array_equal(res, want)
@@ -78,7 +77,7 @@ def test_counter_is_resolved_serially(emul, tmp_path):
     strings = [b"a" * ln for ln in (1000, 1250, 1500, 2047, 2500)] + [b"a" * 600 + b"b" + b"a" * 600]
     want = oracle_lib.OracleImage(blob).match(strings)
     assert list(want) == [1, 1, 1, 0, 1, 0]
-    (_, got0, res0), (_, got3, res3) = run_split(emul, tmp_path, blob, strings, (64,), (8,), (0, 3))
+    (_, got0, res0), (_, got3, res3) = run_lane_split(emul, tmp_path, blob, strings, (64,), (8,), (0, 3))
     assert np.array_equal(res0, want) and np.array_equal(res3, want)
     assert got0["W"] == 8 and got0["serial_strings"] == len(strings) and got3["serial_strings"] == len(strings)
     assert got3["rewalked"] > 0 and 0 < got3["serial_bytes"] < got0["serial_bytes"]
@@ -93,12 +92,12 @@ def test_literal_prefix_guesses_the_home_set(emul, tmp_path):
     strings = [b"xyz" + s for s in body] + [b"xyz" + body[0][:100] + b"z" * 80 + body[0][100:], body[1]]
     want = oracle_lib.OracleImage(blob).match(strings)
     assert list(want) == [1, 1, 1, 0, 0]
-    runs = run_split(emul, tmp_path, blob, strings, (64,), (8, 256), (0, 3))
+    runs = run_lane_split(emul, tmp_path, blob, strings, (64,), (8, 256), (0, 3))
     check_all(runs, want, strings, "prefix")
     # string 3 holds 80 z: a chunk begins behind 8 of them, and both seeds die on those
     assert all(got["home_guesses"] > 0 for _, got, _ in runs)
     # the home set lies inside the loop: 8 bytes in front of a chunk fix the set, and nothing of the accepted strings is left to the serial walk
-    three, _ = run_split(emul, tmp_path, blob, strings[:3], (64,), (8,), (0,))[0][1:]
+    three, _ = run_lane_split(emul, tmp_path, blob, strings[:3], (64,), (8,), (0,))[0][1:]
     assert (three["serial_strings"], three["rewalked"], three["home_guesses"]) == (0, 0, 0)
 
 
@@ -113,7 +112,7 @@ def test_k_images_need_no_repair(emul, k, tmp_path):
         want = oracle_lib.OracleImage(blob).match(strings)
         assert 0 < int(want.sum()) < len(strings)
         for rounds in (0, 3):
-            (_, got, res), = run_split(emul, tmp_path, blob, strings, (64,), (256,), (rounds,))
+            (_, got, res), = run_lane_split(emul, tmp_path, blob, strings, (64,), (256,), (rounds,))
             assert np.array_equal(res, want)
             assert (got["rewalked"], got["serial_strings"], got["serial_bytes"]) == (0, 0, 0)
 
@@ -121,15 +120,15 @@ def test_k_images_need_no_repair(emul, k, tmp_path):
 def test_harness_under_sanitizers(tmp_path):
     """the harness once more with -fsanitize=address,undefined, a stand-alone program: one fixture in each direction in the room the read
     rule gives and not a byte more, the resume form, a wide image and the counter"""
-    exe = split_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("nfa_set_split", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     for rev in (0, 1):
         blob, strings = fixture_corpus("nfa_star4_ssnf", rev)
         want = oracle_lib.OracleImage(blob).match(strings)
-        check_all(run_split(exe, tmp_path, blob, strings, CHUNKS, (0, 8), (0, 3)), want, strings, "nfa_star4_ssnf under sanitizers")
-    run_split(exe, tmp_path, blob, strings, (16,), (8,), (1,), mode="every")
+        check_all(run_lane_split(exe, tmp_path, blob, strings, CHUNKS, (0, 8), (0, 3)), want, strings, "nfa_star4_ssnf under sanitizers")
+    run_lane_split(exe, tmp_path, blob, strings, (16,), (8,), (1,), mode="every")
     blob = wide_images(tmp_path)["deep"]
     strings = wide_strings(np.random.default_rng(1), n=40)
-    check_all(run_split(exe, tmp_path, blob, strings, (16, 64), (8,), (0, 3)), oracle_lib.OracleImage(blob).match(strings), strings, "deep under sanitizers")
+    check_all(run_lane_split(exe, tmp_path, blob, strings, (16, 64), (8,), (0, 3)), oracle_lib.OracleImage(blob).match(strings), strings, "deep under sanitizers")
     blob = front_end_blob(COUNTER, tmp_path)
     strings = [b"a" * 1000, b"a" * 999]
-    check_all(run_split(exe, tmp_path, blob, strings, (64,), (8,), (3,)), np.array([1, 0], dtype=np.uint8), strings, "counter under sanitizers")
+    check_all(run_lane_split(exe, tmp_path, blob, strings, (64,), (8,), (3,)), np.array([1, 0], dtype=np.uint8), strings, "counter under sanitizers")

@@ -10,9 +10,9 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setresume_lib import INVALID, LIVE, feed_set, new_records, record, records_of, resume_emul_exe, run_pieces
-from setsplit_lib import COUNTER, PREFIX, ab_strings, k_blob, run_split, split_emul_exe
-from testlib import DIPLOMA, MAX_BYTES, blob_of, expected_split, filled, front_end_blob, manifest_entry, match_on_gpu, mixed_match, rnd, upload, wide_images
+from setwalk_lib import (COUNTER, INVALID, LANE_WORDS, LIVE, PREFIX, ab_strings, feed_records, k_blob, new_records, record, records_of, records_view, run_lane_pieces,
+                         run_lane_split)
+from testlib import DIPLOMA, MAX_BYTES, blob_of, emul_exe, expected_split, filled, front_end_blob, manifest_entry, match_on_gpu, mixed_match, rnd, upload, wide_images
 
 pytestmark = pytest.mark.gpu
 
@@ -96,7 +96,7 @@ def test_every_width_and_both_directions(env, tmp_path):
 def test_resume_form(env, rev, tmp_path):
     """pieces in three rounds, long pieces cut: each round the records equal the whole-walk harness's word for word and the results the
     oracle's.  Dead and INVALID records are not queued and keep their answers"""
-    emul = resume_emul_exe()
+    emul = emul_exe("nfa_set_resume")
     rng = np.random.default_rng(17 + rev)
     blob = front_end_blob("(a|b)*a" + "(a|b)" * 4 + "(c|(a|b))*", tmp_path, rev)      # W = 2
     img = forced(env, blob)
@@ -116,20 +116,20 @@ def test_resume_form(env, rev, tmp_path):
             else:
                 row.append((cuts[r], cuts[r + 1]))
         rounds.append(row)
-    d_states = new_records(len(strings))
+    d_states = new_records(len(strings), LANE_WORDS)
     for r in range(3):
         pieces = [s[b:e] for s, (b, e) in zip(strings, rounds[r])]
-        got = feed_set(img, pieces, d_states)
+        got = feed_records(img, pieces, d_states, LANE_WORDS)
         seen = [s[rounds[r][k][0]:] if rev else s[:rounds[r][k][1]] for k, s in enumerate(strings)]
         mismatch(got, ora.match(seen), seen, "round %d" % r)
-        _, recs_host = run_pieces(emul, tmp_path, blob, strings, rounds[:r + 1])
-        assert np.array_equal(records_of(d_states, len(strings)), recs_host), "round %d" % r
+        _, recs_host = run_lane_pieces(emul, tmp_path, blob, strings, rounds[:r + 1])
+        assert np.array_equal(records_of(d_states, len(strings), LANE_WORDS), recs_host), "round %d" % r
         assert img.last_set_split()[0] == sum(1 for p in pieces if len(p) >= SPLIT_MIN) and img.last_dfa_split() == (0, 0, 0)
     # dead, INVALID and a live neighbour, each with a long piece: only the neighbour is queued
-    rows = np.stack([record(LIVE), record(INVALID), record(0)])
-    d_states = new_records(3, rows)
-    got = feed_set(img, [strings[1]] * 3, d_states)
-    recs = records_of(d_states, 3)
+    rows = np.stack([record(LANE_WORDS, LIVE), record(LANE_WORDS, INVALID), record(LANE_WORDS, 0)])
+    d_states = new_records(3, LANE_WORDS, rows)
+    got = feed_records(img, [strings[1]] * 3, d_states, LANE_WORDS)
+    recs = records_of(d_states, 3, LANE_WORDS)
     assert list(got[:2]) == [0, 2] and got[2] == ora.match([strings[1]])[0]
     assert list(recs[0]) == [LIVE] + [0] * 11 and list(recs[1]) == [INVALID] + [0] * 11 and recs[2, 0] == LIVE
     assert img.last_set_split()[0] == 1
@@ -142,11 +142,11 @@ def test_over_long_piece_is_not_queued(env):
     big = torch.full((MAX_BYTES + 1 + 2000 + 64,), ord("a"), dtype=torch.uint8, device="cuda")
     big[MAX_BYTES + 1 + 1997:MAX_BYTES + 1 + 2000] = torch.tensor(list(b"abb"), dtype=torch.uint8, device="cuda")
     d_off = torch.tensor([0, MAX_BYTES + 1, MAX_BYTES + 1 + 2000], dtype=torch.int64, device="cuda")
-    d_states = new_records(2)
+    d_states = new_records(2, LANE_WORDS)
     res = filled(2)
-    img.match_tensors_resume_set(big, d_off, d_states, res)
+    img.match_tensors_resume_set(big, d_off, records_view(d_states, 2, LANE_WORDS), res)
     torch.cuda.synchronize()
-    recs = records_of(d_states, 2)
+    recs = records_of(d_states, 2, LANE_WORDS)
     assert list(res.cpu().numpy()) == [2, 1] and list(recs[0]) == [INVALID] + [0] * 11 and recs[1, 0] == LIVE
     assert img.last_set_split()[0] == 1
 
@@ -180,7 +180,7 @@ def counts_against_the_harness(env, tmp_path, img, blob, strings, rounds, lookba
     got, off = match_on_gpu(img, strings, exact=True)
     mismatch(got, oracle_lib.OracleImage(blob).match(strings), strings, "rounds %d" % rounds)
     report = check_split_report(img, off, "rounds %d" % rounds)
-    (_, host, _), = run_split(split_emul_exe(), tmp_path, blob, strings, (CHUNK,), (lookback,), (rounds,))
+    (_, host, _), = run_lane_split(emul_exe("nfa_set_split"), tmp_path, blob, strings, (CHUNK,), (lookback,), (rounds,))
     assert report[3:] == (host["rewalked"], host["serial_strings"], host["serial_bytes"]), (report, host)
     return report, host
 
@@ -240,8 +240,8 @@ def test_turned_off(env, knob):
     mismatch(on, want, strings, "on")
     mismatch(off, want, strings, knob + "=0")
     assert img.last_set_split() == (0, 0, 0, 0, 0, 0) and img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
-    d_states = new_records(len(strings))
-    mismatch(feed_set(img, strings, d_states), want, strings, knob + "=0, resume form")
+    d_states = new_records(len(strings), LANE_WORDS)
+    mismatch(feed_records(img, strings, d_states, LANE_WORDS), want, strings, knob + "=0, resume form")
     assert img.last_set_split() == (0, 0, 0, 0, 0, 0)
 
 

@@ -3,7 +3,7 @@ that can be wrong without a GPU -- csrc/nfa_set_wave_core.h: the reference's ste
 string through rounds of 64 blocks; csrc/image_host.cpp: the wave tables and which image gets them -- compiled for the host
 (tests/emul/nfa_set_wave_emul.cpp with the 64-lane primitives of tests/emul/wave_lanes.h) and run against the tabulated step function
 and the CPU restatement; and what the C-ABI answers before it touches a device.  The kernel around it is checked by
-tests/test_nfa_set_wave_gpu.py, on the same images and strings (tests/setwave_lib.py)."""
+tests/test_nfa_set_wave_gpu.py, on the same images and strings (tests/setwalk_lib.py)."""
 import ctypes
 import random
 import subprocess
@@ -14,16 +14,16 @@ import pytest
 import nfa_fuzz
 import oracle_lib
 from mfa_amd import capi, image
-from setwave_lib import (COUNTER300, EDGE_LENGTHS, LANE_MAX_NODES, RAW_NODES, WAVE_MAX_NODES, eps_chain, raw_corpus_once, regex_strings, run_match, run_step,
-                         wave_emul_exe, wide_regex_images, words_of)
-from testlib import DIPLOMA, LENGTHS, NFA_NAMES, blob_of, front_end_blob, k_regex, out_offsets, table_127
+from setwalk_lib import (COUNTER300, EDGE_LENGTHS, LANE_MAX_NODES, RAW_NODES, WAVE_MAX_NODES, eps_chain, raw_corpus_once, regex_strings, run_match, run_step,
+                         wide_regex_images, words_of)
+from testlib import DIPLOMA, LENGTHS, NFA_NAMES, blob_of, emul_exe, front_end_blob, k_regex, out_offsets, table_127
 
 WORDS = capi.SET_STATE_WORDS
 
 
 @pytest.fixture(scope="module")
 def emul():
-    return wave_emul_exe()
+    return emul_exe("nfa_set_wave")
 
 
 @pytest.fixture()
@@ -198,7 +198,7 @@ def test_under_sanitizers(tmp_path):
     """the harness as a stand-alone program under ASan and UBSan: a wide image on the edge lengths (emul::read_batch gives the batch
     exactly the room the read rule makes readable, the stack exactly its slots, a mask row exactly its words), both scan directions,
     and the step of the 303-node counter"""
-    exe = wave_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("nfa_set_wave", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     images = wide_regex_images(tmp_path)
     for name in ("k_512", "deep"):
         blob, alphabet, min_len = images[name]

@@ -2,7 +2,7 @@
 lanes): images of 257 to 2048 nodes against the CPU restatement, batch shapes that leave waves idle and that make the persistent loop
 run, the forced form (MFA_SET_WAVE=1) on the narrow corpus against the oracle AND the lane kernel, a mixed object that holds a wide
 image, the command line, and the refusal of strings in pieces.  Images and strings are those of tests/test_nfa_set_wave_cpu.py
-(tests/setwave_lib.py)."""
+(tests/setwalk_lib.py)."""
 import ctypes
 import os
 import subprocess
@@ -12,7 +12,7 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setwave_lib import COUNTER300, LANE_MAX_NODES, WAVE_MAX_NODES, raw_corpus_once, regex_strings, wide_regex_images
+from setwalk_lib import COUNTER300, LANE_MAX_NODES, WAVE_MAX_NODES, raw_corpus_once, regex_strings, wide_regex_images
 from testlib import DIPLOMA, NFA_NAMES, expected, filled, setwalk_corpus, upload
 
 pytestmark = pytest.mark.gpu

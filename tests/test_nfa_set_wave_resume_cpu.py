@@ -3,7 +3,7 @@ carries a string's node set, across the lanes, from call to call; its decode and
 encode), compiled for the host (tests/emul/nfa_set_wave_resume_emul.cpp with the 64-lane primitives of tests/emul/wave_lanes.h and
 wave_lanes_resume.h) and run against the CPU restatement, against whole walks and against the tabulated step function; and what
 mfa_match_batch_resume_set_wide and mfa_image_resume_state_bytes answer before they touch a device.  The kernel around it is checked by
-tests/test_nfa_set_wave_resume_gpu.py, on the same images, strings and cuts (tests/setwave_lib.py, tests/setwaveresume_lib.py)."""
+tests/test_nfa_set_wave_resume_gpu.py, on the same images, strings and cuts (tests/setwalk_lib.py)."""
 import ctypes
 import os
 import re
@@ -14,17 +14,16 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setwave_lib import COUNTER300, RAW_NODES, WAVE_MAX_NODES, raw_corpus_once, regex_strings, wide_regex_images, words_of
-from setwaveresume_lib import (GUARD, LIVE, N_ROUNDS, WORDS, check_records_are_clean, check_sticky, fixed_cuts, pieces_of, resume_emul_exe, run_pieces, run_table,
-                               sticky_case, three_rounds)
-from testlib import blob_of, front_end_blob, seen_so_far
+from setwalk_lib import (COUNTER300, GUARD, LIVE, N_ROUNDS, RAW_NODES, WAVE_MAX_NODES, WIDE_WORDS, check_records_are_clean, check_sticky, fixed_cuts, pieces_of,
+                         raw_corpus_once, regex_strings, run_wide_pieces, run_wide_table, sticky_case, three_rounds, wide_regex_images, words_of)
+from testlib import blob_of, emul_exe, front_end_blob, seen_so_far
 
 REGEX_IMAGES = ("k_512", "k_512_rev", "k_1024", "k_2048", "deep")
 
 
 @pytest.fixture(scope="module")
 def emul():
-    return resume_emul_exe()
+    return emul_exe("nfa_set_wave_resume")
 
 
 @pytest.fixture()
@@ -54,13 +53,13 @@ def test_before_the_device(env, tmp_path):
     env.delenv("MFA_DFA_STATE_LIMIT")
     assert counter.info()["n_nodes"] == 303 and counter.info()["dfa_states"] == 0
     assert [im.resume_state_bytes() for im in (mem, tab, lane, wave, counter)] == [0, 4, 48, 272, 272]
-    assert 272 == 4 * WORDS == 4 * capi.SET_STATE_WIDE_WORDS
+    assert 272 == 4 * WIDE_WORDS == 4 * capi.SET_STATE_WIDE_WORDS
     out = ctypes.c_uint32(77)
     assert L.mfa_image_resume_state_bytes(None, ctypes.byref(out)) == capi.ERR_INVALID_ARG
     assert L.mfa_image_resume_state_bytes(wave._h, None) == capi.ERR_INVALID_ARG and out.value == 77
     buf, off = (ctypes.c_uint8 * 64)(), (ctypes.c_uint64 * 2)(0, 3)
     res = (ctypes.c_uint8 * 4)(7, 7, 7, 7)
-    st = (ctypes.c_uint32 * (WORDS + 8))(*([GUARD] * (WORDS + 8)))
+    st = (ctypes.c_uint32 * (WIDE_WORDS + 8))(*([GUARD] * (WIDE_WORDS + 8)))
     at = ctypes.addressof(st)
     at += -at % 16                                                                  # a 16-byte aligned record inside st, guard words around it
     for img in (wave, counter):
@@ -77,7 +76,7 @@ def test_before_the_device(env, tmp_path):
         assert L.mfa_match_batch_resume_set_wide_host(img._h, buf, off, 1, at, res, 0) == capi.ERR_UNSUPPORTED
         assert L.mfa_match_batch_resume_set_wide(img._h, buf, off, 0, at, res, 0, None) == capi.ERR_UNSUPPORTED          # (refused before n is looked at)
         assert L.mfa_match_batch_resume_set_wide(img._h, buf, off, 1, None, res, 0, None) == capi.ERR_INVALID_ARG
-    assert list(st) == [GUARD] * (WORDS + 8) and list(res) == [7, 7, 7, 7]
+    assert list(st) == [GUARD] * (WIDE_WORDS + 8) and list(res) == [7, 7, 7, 7]
     assert all(im.info()["last_kernel"] == capi.KERNEL_NONE for im in (mem, tab, lane, wave, counter))
 
 
@@ -99,17 +98,17 @@ def pieces_against_whole(emul, tmp_path, blob, strings, rounds, is_rev, want, wh
     """the strings fed in N_ROUNDS rounds in scan order: EVERY round's digits are the oracle's answers on what has been given so far, the
     final records are bit for bit those of the whole strings in one round, and those are clean.  Returns (tables, records)"""
     assert len(rounds) == N_ROUNDS
-    tables, digits, recs = run_pieces(emul, tmp_path, blob, [pieces_of(strings, row) for row in rounds])
+    tables, digits, recs = run_wide_pieces(emul, tmp_path, blob, [pieces_of(strings, row) for row in rounds])
     ora = oracle_lib.OracleImage(blob)
     for r in range(N_ROUNDS):
         ref = want if r == N_ROUNDS - 1 else ora.match(seen_so_far(strings, rounds, r, is_rev))
         bad = np.nonzero(digits[r] != ref)[0]
         assert bad.size == 0, "%s round %d: %d mismatches, first string %d (len %d) want %d got %d" % (what, r, bad.size, bad[0], len(strings[bad[0]]), ref[bad[0]], digits[r][bad[0]])
-    _, whole_digits, whole_recs = run_pieces(emul, tmp_path, blob, [strings])
+    _, whole_digits, whole_recs = run_wide_pieces(emul, tmp_path, blob, [strings])
     assert np.array_equal(whole_digits[0], want), what
     assert np.array_equal(recs, whole_recs), what
     n_nodes = image.blob_info(blob)["n_nodes"]
-    check_records_are_clean(recs, n_nodes)
+    check_records_are_clean(recs, n_nodes, WIDE_WORDS)
     assert (recs[:, 0] == LIVE).all() and tables[1] == words_of(n_nodes)
     assert recs[want == 1, 4:].any(axis=1).all()                                   # an accepted string's set is not empty
     return tables, recs
@@ -153,7 +152,7 @@ def test_sets_equal_the_table(emul, tmp_path):
     rng = np.random.default_rng(5)
     strings = [b"a" * int(x) for x in list(range(0, 40)) + [299, 300, 301, 599, 600, 601, 1023, 1024, 1025, 2049] + [int(v) for v in rng.integers(0, 1200, size=60)]]
     strings += [b"a" * 150 + b"b" + b"a" * 149, b"b", b"a" * 300 + b"b"]           # the dead state
-    tables, n, states = run_table(emul, tmp_path, blob, strings)
+    tables, n, states = run_wide_table(emul, tmp_path, blob, strings)
     assert tables[1] == 10 and n == len(strings) and states >= 300 and states == capi.Image(blob).info()["dfa_states"]
 
 
@@ -166,8 +165,8 @@ def test_record_checks_on_the_harness(emul, tmp_path):
     blob = front_end_blob(COUNTER300, tmp_path)
     assert image.blob_info(blob)["n_nodes"] == 303 and not image.blob_info(blob)["reversed"]
     rows, rounds, _, _, _, _ = sticky_case()
-    _, d1, recs1 = run_pieces(emul, tmp_path, blob, rounds[:1], rows)
-    _, d2, recs2 = run_pieces(emul, tmp_path, blob, rounds, rows)
+    _, d1, recs1 = run_wide_pieces(emul, tmp_path, blob, rounds[:1], rows)
+    _, d2, recs2 = run_wide_pieces(emul, tmp_path, blob, rounds, rows)
     assert np.array_equal(d1[0], d2[0])
     check_sticky(blob, d2, [recs1, recs2], "harness")
 
@@ -178,7 +177,7 @@ def test_under_sanitizers(tmp_path):
     2048-node raw image (lane 63 and the last bit), and the record checks, whose dead and over-long records have offsets outside the
     buffer -- the batch has exactly the room the 16-byte read rule makes readable, the records exactly n * 272 bytes, the stack exactly
     its slots"""
-    exe = resume_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("nfa_set_wave_resume", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     images = wide_regex_images(tmp_path)
     for name in ("k_512", "deep"):
         blob, alphabet, min_len = images[name]
@@ -192,4 +191,4 @@ def test_under_sanitizers(tmp_path):
     rounds, is_rev = three_rounds(blob, strings[:80], np.random.default_rng(2))
     pieces_against_whole(exe, tmp_path, blob, strings[:80], rounds, is_rev, want[:80], name + " under sanitizers")
     test_record_checks_on_the_harness(exe, tmp_path)
-    assert run_table(exe, tmp_path, front_end_blob(COUNTER300, tmp_path), [b"a" * 300, b"a" * 17, b"", b"ab"])[0][1] == 10
+    assert run_wide_table(exe, tmp_path, front_end_blob(COUNTER300, tmp_path), [b"a" * 300, b"a" * 17, b"", b"ab"])[0][1] == 10

@@ -1,8 +1,7 @@
 """Wave images on strings given in pieces, on the GPU: mfa_match_batch_resume_set_wide (nfa_set_wave_resume_kernel, csrc/nfa_set_wave.hip)
 against the CPU restatement, against the plain batch call and, record for record, against the host harness that runs the same core
-(tests/emul/nfa_set_wave_resume_emul.cpp), on the images, strings and cuts of tests/test_nfa_set_wave_resume_cpu.py (tests/setwave_lib.py,
-tests/setwaveresume_lib.py); both placements of the tables; batch shapes that leave waves idle and that make the persistent loop run;
-the sticky errors; no result bytes; the lane kernel's records; streams and capture; the host entry point; the command line."""
+(tests/emul/nfa_set_wave_resume_emul.cpp), on the images, strings and cuts of tests/test_nfa_set_wave_resume_cpu.py (tests/setwalk_lib.py);
+both placements of the tables; batch shapes that leave waves idle and that make the persistent loop run; the sticky errors; no result bytes; the lane kernel's records; streams and capture; the host entry point; the command line."""
 import os
 import subprocess
 
@@ -11,13 +10,10 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setresume_lib import feed_set
-from setresume_lib import new_records as new_lane_records
-from setresume_lib import records_of as lane_records_of
-from setwave_lib import COUNTER300, LANE_MAX_NODES, RAW_NODES, raw_corpus_once, regex_strings, wide_regex_images
-from setwaveresume_lib import (LIVE, N_ROUNDS, WORDS, call_wide, check_records_are_clean, check_sticky, feed_wide, fixed_cuts, new_records, pieces_of, records_of,
-                               results_of, resume_emul_exe, run_pieces, sticky_case, tables_in_lds, three_rounds)
-from testlib import DIPLOMA, blob_of, front_end_blob, match_on_gpu, rnd, seen_so_far, upload, wide_images, wide_strings
+from setwalk_lib import (COUNTER300, LANE_MAX_NODES, LANE_WORDS, LIVE, N_ROUNDS, RAW_NODES, WIDE_WORDS, call_records, check_records_are_clean, check_sticky, feed_records,
+                         fixed_cuts, new_records, pieces_of, raw_corpus_once, records_of, records_view, regex_strings, results_of, run_wide_pieces, sticky_case, tables_in_lds,
+                         three_rounds, wide_regex_images)
+from testlib import DIPLOMA, blob_of, emul_exe, front_end_blob, match_on_gpu, rnd, seen_so_far, upload, wide_images, wide_strings
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +29,7 @@ def env(monkeypatch):
 
 @pytest.fixture(scope="module")
 def emul():
-    return resume_emul_exe()
+    return emul_exe("nfa_set_wave_resume")
 
 
 def regex_image(env, blob):
@@ -41,7 +37,7 @@ def regex_image(env, blob):
     env.setenv("MFA_DFA_STATE_LIMIT", "2")
     img = capi.Image(blob)
     env.delenv("MFA_DFA_STATE_LIMIT")
-    assert img.info()["dfa_states"] == 0 and img.info()["n_nodes"] > LANE_MAX_NODES and img.resume_state_bytes() == 4 * WORDS
+    assert img.info()["dfa_states"] == 0 and img.info()["n_nodes"] > LANE_MAX_NODES and img.resume_state_bytes() == 4 * WIDE_WORDS
     return img
 
 
@@ -86,23 +82,23 @@ def pieces_against_harness(img, emul, tmp_path, blob, strings, rounds, is_rev, w
     results_of).  Returns the harness's "tables" line"""
     n = len(strings)
     ora = oracle_lib.OracleImage(blob)
-    buf = new_records(n)
+    buf = new_records(n, WIDE_WORDS)
     for r in range(N_ROUNDS):
-        got = feed_wide(img, pieces_of(strings, rounds[r]), buf)
+        got = feed_records(img, pieces_of(strings, rounds[r]), buf, WIDE_WORDS)
         mismatch(got, want if r == N_ROUNDS - 1 else ora.match(seen_so_far(strings, rounds, r, is_rev)), strings, "%s round %d" % (what, r))
     bookkeeping(img)
-    recs = records_of(buf, n)
-    tables, digits, recs_host = run_pieces(emul, tmp_path, blob, [strings])
+    recs = records_of(buf, n, WIDE_WORDS)
+    tables, digits, recs_host = run_wide_pieces(emul, tmp_path, blob, [strings])
     assert np.array_equal(digits[0], want), what
     assert np.array_equal(recs, recs_host), what
-    check_records_are_clean(recs, image.blob_info(blob)["n_nodes"])
+    check_records_are_clean(recs, image.blob_info(blob)["n_nodes"], WIDE_WORDS)
     assert (recs[:, 0] == LIVE).all()
     return tables
 
 
 def whole_equals_plain(img, strings, want, what):
     """one round through the wide call from zeroed records: byte for byte what mfa_match_batch answers on the same image"""
-    got = feed_wide(img, strings, new_records(len(strings)))
+    got = feed_records(img, strings, new_records(len(strings), WIDE_WORDS), WIDE_WORDS)
     plain = match_on_gpu(img, strings, exact=True)[0]
     assert np.array_equal(got, plain) and np.array_equal(got, want), what
 
@@ -130,7 +126,7 @@ def test_piecewise_parity_regex_images(env, emul, name, tmp_path):
 def test_piecewise_parity_raw_images(env, emul, n_nodes, tmp_path):
     name, blob, strings, want = raw_by_nodes()[n_nodes]
     img = set_walk_image(env, blob)
-    assert img.info()["n_nodes"] == n_nodes and img.resume_state_bytes() == 4 * WORDS
+    assert img.info()["n_nodes"] == n_nodes and img.resume_state_bytes() == 4 * WIDE_WORDS
     rounds, is_rev = three_rounds(blob, strings, np.random.default_rng(n_nodes))
     pieces_against_harness(img, emul, tmp_path, blob, strings, rounds, is_rev, want, name)
     whole_equals_plain(img, strings, want, name)
@@ -144,7 +140,7 @@ def test_both_table_placements(emul, tmp_path):
     cases = [(name, images[name][0]) for name in REGEX_IMAGES] + [(c[0], c[1]) for c in raw_by_nodes().values()]
     seen = {}
     for name, blob in cases:
-        words, _, depth = run_pieces(emul, tmp_path, blob, [[b"ab"]])[0]
+        words, _, depth = run_wide_pieces(emul, tmp_path, blob, [[b"ab"]])[0]
         seen.setdefault((image.blob_info(blob)["reversed"], (4 * depth + words) * 4 <= 65536), []).append(name)
     assert set(seen) == {(0, True), (0, False), (1, True), (1, False)}, seen
     assert "k_512" in seen[(0, True)] and "k_2048" in seen[(0, False)] and "deep" in seen[(1, True)]
@@ -164,27 +160,27 @@ def test_grid_edges(env, emul, tmp_path):
     order = [acc[0], rej[0], acc[1], rej[1], acc[2]]
     for n in (1, 5):
         pick = [strings[int(k)] for k in order[:n]]
-        buf = new_records(n)
-        feed_wide(img, [s[:len(s) // 2] for s in pick], buf, results=False)
-        got = feed_wide(img, [s[len(s) // 2:] for s in pick], buf)
+        buf = new_records(n, WIDE_WORDS)
+        feed_records(img, [s[:len(s) // 2] for s in pick], buf, WIDE_WORDS, results=False)
+        got = feed_records(img, [s[len(s) // 2:] for s in pick], buf, WIDE_WORDS)
         mismatch(got, want[order[:n]], pick, "%s, %d strings" % (name, n))
-        assert (records_of(buf, n)[:, 0] == LIVE).all()
-    emul_tables = run_pieces(emul, tmp_path, blob, [[b"ab"]])[0]
+        assert (records_of(buf, n, WIDE_WORDS)[:, 0] == LIVE).all()
+    emul_tables = run_wide_pieces(emul, tmp_path, blob, [[b"ab"]])[0]
     lds = (4 * emul_tables[2] + (emul_tables[0] if tables_in_lds(emul_tables) else 0)) * 4
     per_cu = min(8, max(1, (160 * 1024) // max(lds, 1)))
     n = 3 * torch.cuda.get_device_properties(0).multi_processor_count * per_cu * 4 + 1
     short = [strings[k % len(strings)][:(k // len(strings)) % 9] for k in range(n)]      # prefixes: the image scans forward
     assert max(len(s) for s in short) == 8 and min(len(s) for s in short) == 0
-    buf = new_records(n)
-    first = feed_wide(img, [s[:len(s) // 2] for s in short], buf)
+    buf = new_records(n, WIDE_WORDS)
+    first = feed_records(img, [s[:len(s) // 2] for s in short], buf, WIDE_WORDS)
     mismatch(first, ora.match([s[:len(s) // 2] for s in short]), short, name + ", many short strings, round 0")
-    got = feed_wide(img, [s[len(s) // 2:] for s in short], buf)
+    got = feed_records(img, [s[len(s) // 2:] for s in short], buf, WIDE_WORDS)
     mismatch(got, ora.match(short), short, name + ", many short strings")
-    recs = records_of(buf, n)
-    check_records_are_clean(recs, 257)
-    whole = new_records(n)
-    feed_wide(img, short, whole)
-    assert np.array_equal(recs, records_of(whole, n))
+    recs = records_of(buf, n, WIDE_WORDS)
+    check_records_are_clean(recs, 257, WIDE_WORDS)
+    whole = new_records(n, WIDE_WORDS)
+    feed_records(img, short, whole, WIDE_WORDS)
+    assert np.array_equal(recs, records_of(whole, n, WIDE_WORDS))
     bookkeeping(img)
 
 
@@ -201,16 +197,16 @@ def test_sticky_errors_and_dead_on_entry(env, tmp_path):
     assert img.info()["n_nodes"] == 303 and img.info()["dfa_states"] == 0 and not img.info()["is_reversed"]
     rows, rounds, _, _, _, _ = sticky_case()
     n = len(rows)
-    buf = new_records(n, rows)
+    buf = new_records(n, WIDE_WORDS, rows)
     digits, recs = [], []
     for _, off, data in rounds:
         d_bytes = torch.zeros((len(data) + 15) // 16 * 16, dtype=torch.uint8, device="cuda")
         d_bytes[:len(data)] = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy())
         d_off = torch.from_numpy(np.asarray(off, dtype=np.int64)).cuda()
-        res = call_wide(img, d_bytes, d_off, buf, n)
+        res = call_records(img, d_bytes, d_off, buf, n, WIDE_WORDS)
         torch.cuda.synchronize()
         digits.append(results_of(res, n))
-        recs.append(records_of(buf, n))
+        recs.append(records_of(buf, n, WIDE_WORDS))
     check_sticky(blob, digits, recs, "device")
     bookkeeping(img)
 
@@ -223,10 +219,10 @@ def test_no_result_bytes_on_intermediate_rounds(env, tmp_path):
     img = regex_image(env, blob)
     assert img.info()["is_reversed"]
     thirds = [[s[k * len(s) // 3:(k + 1) * len(s) // 3] for s in strings] for k in range(3)][::-1]
-    buf = new_records(len(strings))
-    assert feed_wide(img, thirds[0], buf, results=False) is None
-    assert feed_wide(img, thirds[1], buf, results=False) is None
-    got = feed_wide(img, thirds[2], buf)
+    buf = new_records(len(strings), WIDE_WORDS)
+    assert feed_records(img, thirds[0], buf, WIDE_WORDS, results=False) is None
+    assert feed_records(img, thirds[1], buf, WIDE_WORDS, results=False) is None
+    got = feed_records(img, thirds[2], buf, WIDE_WORDS)
     want = oracle_lib.OracleImage(blob).match(strings)
     assert 0 < int(want.sum()) < len(strings)
     mismatch(got, want, strings, "no result bytes")
@@ -250,13 +246,13 @@ def test_wide_records_equal_the_lane_records(env, tmp_path):
         assert (lane.resume_state_bytes(), wave.resume_state_bytes()) == (48, 272)
         rounds, is_rev = three_rounds(blob, strings, rng)
         n = len(strings)
-        d_lane, buf = new_lane_records(n), new_records(n)
+        d_lane, buf = new_records(n, LANE_WORDS), new_records(n, WIDE_WORDS)
         for r in range(N_ROUNDS):
             pieces = pieces_of(strings, rounds[r])
-            got_lane, got_wave = feed_set(lane, pieces, d_lane), feed_wide(wave, pieces, buf)
+            got_lane, got_wave = feed_records(lane, pieces, d_lane, LANE_WORDS), feed_records(wave, pieces, buf, WIDE_WORDS)
             assert np.array_equal(got_lane, got_wave), "%s round %d" % (key, r)
         mismatch(got_wave, want, strings, key)
-        recs_lane, recs = lane_records_of(d_lane, n), records_of(buf, n)
+        recs_lane, recs = records_of(d_lane, n, LANE_WORDS), records_of(buf, n, WIDE_WORDS)
         assert np.array_equal(recs[:, :12], recs_lane) and not recs[:, 12:].any(), key
 
 
@@ -274,20 +270,20 @@ def test_two_streams_one_image(env):
         mine = strings[v * n:(v + 1) * n]
         thirds = [[s[k * len(s) // 3:(k + 1) * len(s) // 3] for s in mine] for k in range(3)]
         rounds = [upload(p, exact=True) for p in (thirds[::-1] if is_rev else thirds)]
-        work.append((rounds, new_records(n), want[v * n:(v + 1) * n]))
+        work.append((rounds, new_records(n, WIDE_WORDS), want[v * n:(v + 1) * n]))
     assert not np.array_equal(work[0][2], work[1][2])
     torch.cuda.synchronize()
     res = [None, None]
     for r in range(3):
         for v in range(2):
             rounds, buf, _ = work[v]
-            out = call_wide(img, rounds[r][0], rounds[r][1], buf, n, results=r == 2, stream=streams[v])
+            out = call_records(img, rounds[r][0], rounds[r][1], buf, n, WIDE_WORDS, results=r == 2, stream=streams[v])
             if r == 2:
                 res[v] = out
     torch.cuda.synchronize()
     for v in range(2):
         assert np.array_equal(results_of(res[v], n), work[v][2])
-        assert (records_of(work[v][1], n)[:, 0] == LIVE).all()
+        assert (records_of(work[v][1], n, WIDE_WORDS)[:, 0] == LIVE).all()
 
 
 def test_wide_call_is_capturable(env, tmp_path):
@@ -307,8 +303,8 @@ def test_wide_call_is_capturable(env, tmp_path):
     assert 0 < int(want_first.sum()) < len(first) and 0 < int(want_joined.sum()) < len(first) and not np.array_equal(want_first, want_joined)
     n = len(first)
     d_bytes, d_off, _ = upload(first, exact=True)
-    buf = new_records(n)
-    view = buf[4:4 + n * WORDS]
+    buf = new_records(n, WIDE_WORDS)
+    view = records_view(buf, n, WIDE_WORDS)
     res = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -329,7 +325,7 @@ def test_wide_call_is_capturable(env, tmp_path):
         g.replay()
         torch.cuda.synchronize()
         assert np.array_equal(res.cpu().numpy(), want)
-    assert (records_of(buf, n)[:, 0] == LIVE).all()
+    assert (records_of(buf, n, WIDE_WORDS)[:, 0] == LIVE).all()
 
 
 def test_host_entry_point(env, tmp_path):
@@ -339,15 +335,15 @@ def test_host_entry_point(env, tmp_path):
     img = capi.Image(blob)
     env.delenv("MFA_DFA_STATE_LIMIT")
     strings = [b"a" * 300, b"a" * 299, b"", b"a" * 150 + b"b" + b"a" * 149, b"a" * 900]
-    states = np.zeros(len(strings) * WORDS, dtype=np.uint32)
+    states = np.zeros(len(strings) * WIDE_WORDS, dtype=np.uint32)
     d1, o1 = oracle_lib.pack([s[:len(s) // 2] for s in strings])
     d2, o2 = oracle_lib.pack([s[len(s) // 2:] for s in strings])
     assert img.match_host_resume_set_wide(np.concatenate([d1, np.zeros(16, np.uint8)]), o1, states, want_results=False) is None
     got = img.match_host_resume_set_wide(np.concatenate([d2, np.zeros(16, np.uint8)]), o2, states)
     assert list(got) == list(oracle_lib.OracleImage(blob).match(strings)) == [1, 0, 1, 0, 1]
-    recs = states.reshape(len(strings), WORDS)
-    check_records_are_clean(recs, 303)
-    assert list(recs[:, 0]) == [LIVE] * 5 and list(recs[3]) == [LIVE] + [0] * (WORDS - 1)      # the string with a `b`: dead
+    recs = states.reshape(len(strings), WIDE_WORDS)
+    check_records_are_clean(recs, 303, WIDE_WORDS)
+    assert list(recs[:, 0]) == [LIVE] * 5 and list(recs[3]) == [LIVE] + [0] * (WIDE_WORDS - 1)      # the string with a `b`: dead
     bookkeeping(img)
 
 

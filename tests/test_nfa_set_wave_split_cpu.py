@@ -12,11 +12,10 @@ import pytest
 
 import oracle_lib
 from mfa_amd import image
-from setsplit_lib import CHUNKS, LOOKBACKS, ROUNDS, ab_strings, chunk_lengths, fixture_corpus, run_split, split_emul_exe
-from setwave_lib import COUNTER300, EDGE_LENGTHS, pack_every_offset, raw_corpus_once, wide_regex_images, words_of
-from setwaveresume_lib import INVALID, LIVE, START, WORDS, check_records_are_clean, pieces_of, record, resume_emul_exe, run_pieces
-from setwavesplit_lib import COUNT_KEYS, PREFIX_WIDE, run_wave_split, run_wave_split_pieces, wave_split_emul_exe
-from testlib import NFA_NAMES, front_end_blob, out_offsets
+from setwalk_lib import (CHUNKS, COUNTER300, COUNT_KEYS, EDGE_LENGTHS, INVALID, LIVE, LOOKBACKS, PREFIX_WIDE, REPAIR_ROUNDS, START, WIDE_WORDS, ab_strings, check_records_are_clean,
+                         chunk_lengths, fixture_corpus, pack_every_offset, pieces_of, raw_corpus_once, record, run_lane_split, run_wave_split, run_wide_pieces,
+                         run_wide_split_pieces, wide_regex_images, words_of)
+from testlib import NFA_NAMES, emul_exe, front_end_blob, out_offsets
 
 REGEX_IMAGES = ("k_512", "k_512_rev", "k_1024", "k_2048", "deep")
 RAW = ((257, 1025, 2048), 2)
@@ -25,11 +24,11 @@ SPLIT_LENGTHS = chunk_lengths() + EDGE_LENGTHS      # around multiples of every 
 
 @pytest.fixture(scope="module")
 def emul():
-    return wave_split_emul_exe()
+    return emul_exe("nfa_set_wave_split")
 
 
 def check_all(runs, want, strings, what, n_nodes):
-    assert len(runs) == len(CHUNKS) * len(LOOKBACKS) * len(ROUNDS)
+    assert len(runs) == len(CHUNKS) * len(LOOKBACKS) * len(REPAIR_ROUNDS)
     for (chunk, lookback, rounds), got, res in runs:
         bad = np.nonzero(res != want)[0]
         assert bad.size == 0, "%s chunk %d lookback %d rounds %d: %d mismatches, first len %d want %d" % (
@@ -55,7 +54,7 @@ def test_wide_regex_images(emul, name, tmp_path):
     strings = split_strings(lambda ln: bytes(rng.choice(list(alphabet), size=int(ln)).tolist()))
     want = oracle_lib.OracleImage(blob).match(strings)
     assert 0 < int(want.sum()) < len(strings)
-    check_all(run_wave_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, ROUNDS), want, strings, name, image.blob_info(blob)["n_nodes"])
+    check_all(run_wave_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS), want, strings, name, image.blob_info(blob)["n_nodes"])
 
 
 def test_raw_images(emul, tmp_path):
@@ -70,7 +69,7 @@ def test_raw_images(emul, tmp_path):
         assert set(EDGE_LENGTHS) <= {len(s) for s in strings}
         folder = tmp_path / name
         folder.mkdir()
-        return run_wave_split(emul, folder, blob, strings, CHUNKS, LOOKBACKS, ROUNDS)
+        return run_wave_split(emul, folder, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS)
 
     with ThreadPoolExecutor(max_workers=max(1, min(len(corpus), os.cpu_count() or 1))) as pool:
         all_runs = list(pool.map(one, corpus))
@@ -87,9 +86,9 @@ def test_narrow_fixtures_count_what_the_lane_path_counts(emul, name, rev, tmp_pa
     blob, strings = fixture_corpus(name, rev)
     assert {o % 16 for o in out_offsets(strings)} == set(range(16))
     want = oracle_lib.OracleImage(blob).match(strings)
-    wave = run_wave_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, ROUNDS)
+    wave = run_wave_split(emul, tmp_path, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS)
     check_all(wave, want, strings, "%s rev %d" % (name, rev), image.blob_info(blob)["n_nodes"])
-    lane = run_split(split_emul_exe(), tmp_path, blob, strings, CHUNKS, LOOKBACKS, ROUNDS)
+    lane = run_lane_split(emul_exe("nfa_set_split"), tmp_path, blob, strings, CHUNKS, LOOKBACKS, REPAIR_ROUNDS)
     for (combo, got_w, res_w), (combo_l, got_l, res_l) in zip(wave, lane):
         assert combo == combo_l and np.array_equal(res_w, res_l)
         assert [got_w[k] for k in COUNT_KEYS + ("home_guesses", "home_nodes")] == [got_l[k] for k in COUNT_KEYS + ("home_guesses", "home_nodes")], (name, combo)
@@ -189,14 +188,14 @@ def test_resume_form_pieces_equal_the_whole_walk(emul, name, tmp_path):
         for r in range(3):
             rounds[r].append(cuts[r])
     ora = oracle_lib.OracleImage(blob)
-    digits, queued, recs = run_wave_split_pieces(emul, tmp_path, blob, [pieces_of(strings, row) for row in rounds], 64, 64, 3, 200)
+    digits, queued, recs = run_wide_split_pieces(emul, tmp_path, blob, [pieces_of(strings, row) for row in rounds], 64, 64, 3, 200)
     assert queued == [sum(1 for t in lens if t[r] >= 200) for r in range(3)] and min(queued) >= 3
     for r in range(3):
         seen = [s[rounds[r][k][0]:] if is_rev else s[:rounds[r][k][1]] for k, s in enumerate(strings)]
         assert np.array_equal(digits[r], ora.match(seen)), "round %d" % r
-    _, whole_digits, whole_recs = run_pieces(resume_emul_exe(), tmp_path, blob, [strings])
+    _, whole_digits, whole_recs = run_wide_pieces(emul_exe("nfa_set_wave_resume"), tmp_path, blob, [strings])
     assert np.array_equal(recs, whole_recs) and np.array_equal(digits[2], whole_digits[0])
-    check_records_are_clean(recs, image.blob_info(blob)["n_nodes"])
+    check_records_are_clean(recs, image.blob_info(blob)["n_nodes"], WIDE_WORDS)
 
 
 def test_resume_form_queues_live_records_only(emul, tmp_path):
@@ -205,16 +204,16 @@ def test_resume_form_queues_live_records_only(emul, tmp_path):
     blob, alphabet, _ = wide_regex_images(tmp_path)["k_512"]
     rng = np.random.default_rng(4)
     piece = bytes(rng.choice(list(alphabet), size=600).tolist())
-    rows = np.stack([record(LIVE), record(INVALID), record(7), record(LIVE, {63: 1 << 31}), record(START)])
-    digits, queued, recs = run_wave_split_pieces(emul, tmp_path, blob, [[piece] * len(rows)], 64, 64, 3, 200, states=rows)
+    rows = np.stack([record(WIDE_WORDS, LIVE), record(WIDE_WORDS, INVALID), record(WIDE_WORDS, 7), record(WIDE_WORDS, LIVE, {63: 1 << 31}), record(WIDE_WORDS, START)])
+    digits, queued, recs = run_wide_split_pieces(emul, tmp_path, blob, [[piece] * len(rows)], 64, 64, 3, 200, states=rows)
     assert queued == [1]
     assert list(digits[0]) == [0, 2, 2, 2, oracle_lib.OracleImage(blob).match([piece])[0]]
-    assert list(recs[0]) == [LIVE] + [0] * (WORDS - 1)
+    assert list(recs[0]) == [LIVE] + [0] * (WIDE_WORDS - 1)
     for k in (1, 2, 3):
-        assert list(recs[k]) == [INVALID] + [0] * (WORDS - 1)
+        assert list(recs[k]) == [INVALID] + [0] * (WIDE_WORDS - 1)
     assert recs[4, 0] == LIVE and recs[4, 4:].any()
     # a second piece on the live record it left: queued again, from a set that is not {start}
-    digits2, queued2, recs2 = run_wave_split_pieces(emul, tmp_path, blob, [[piece] * len(rows)], 64, 64, 0, 200, states=recs)
+    digits2, queued2, recs2 = run_wide_split_pieces(emul, tmp_path, blob, [[piece] * len(rows)], 64, 64, 0, 200, states=recs)
     assert queued2 == [1] and digits2[0][4] == oracle_lib.OracleImage(blob).match([piece + piece])[0] and list(digits2[0][:4]) == [0, 2, 2, 2]
 
 
@@ -222,7 +221,7 @@ def test_harness_under_sanitizers(tmp_path):
     """the harness once more with -fsanitize=address,undefined, a stand-alone program, on one image: k_512 scanning from the end, in the
     room the read rule gives and not a byte more, with the stacks and the records at exactly their sizes; the split form and the resume
     form"""
-    exe = wave_split_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("nfa_set_wave_split", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     blob, alphabet, _ = wide_regex_images(tmp_path)["k_512_rev"]
     rng = np.random.default_rng(9)
     pick = lambda ln: bytes(rng.choice(list(alphabet), size=int(ln)).tolist())
@@ -231,6 +230,6 @@ def test_harness_under_sanitizers(tmp_path):
     for (chunk, lookback, rounds), got, res in run_wave_split(exe, tmp_path, blob, strings, (16, 64), (0, 8, 256), (0, 3)):
         assert np.array_equal(res, want) and got["checks"] == len(strings)
     pieces = [[pick(300), pick(17), b""], [pick(64), pick(500), pick(200)]]
-    digits, queued, _ = run_wave_split_pieces(exe, tmp_path, blob, pieces, 32, 8, 1, 200)
+    digits, queued, _ = run_wide_split_pieces(exe, tmp_path, blob, pieces, 32, 8, 1, 200)
     assert queued == [1, 2]
     assert np.array_equal(digits[1], oracle_lib.OracleImage(blob).match([b + a for a, b in zip(*pieces)]))

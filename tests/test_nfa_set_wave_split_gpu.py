@@ -11,11 +11,9 @@ import pytest
 
 import oracle_lib
 from mfa_amd import capi, image
-from setwave_lib import COUNTER300, LANE_MAX_NODES, raw_corpus_once, wide_regex_images
-from setwaveresume_lib import (INVALID, LIVE, WORDS, feed_wide, new_records, pieces_of, record, records_of, results_of, resume_emul_exe, run_pieces, tables_in_lds)
-from setwavesplit_lib import PREFIX_WIDE, run_wave_split, wave_split_emul_exe
-from setsplit_lib import ab_strings
-from testlib import DIPLOMA, blob_of, expected_split, filled, front_end_blob, match_on_gpu, mixed_match, rnd, upload
+from setwalk_lib import (COUNTER300, INVALID, LANE_MAX_NODES, LIVE, PREFIX_WIDE, WIDE_WORDS, ab_strings, feed_records, new_records, pieces_of, raw_corpus_once, record, records_of,
+                         results_of, run_wave_split, run_wide_pieces, tables_in_lds, wide_regex_images)
+from testlib import DIPLOMA, blob_of, emul_exe, expected_split, filled, front_end_blob, match_on_gpu, mixed_match, rnd, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +39,7 @@ def wave_image(env, blob):
     env.setenv("MFA_DFA_STATE_LIMIT", "2")
     img = capi.Image(blob)
     env.delenv("MFA_DFA_STATE_LIMIT")
-    assert img.info()["dfa_states"] == 0 and img.info()["n_nodes"] > LANE_MAX_NODES and img.resume_state_bytes() == 4 * WORDS
+    assert img.info()["dfa_states"] == 0 and img.info()["n_nodes"] > LANE_MAX_NODES and img.resume_state_bytes() == 4 * WIDE_WORDS
     return img
 
 
@@ -53,7 +51,7 @@ def forced(env, blob, wave):
     img = capi.Image(blob)
     env.delenv("MFA_NFA_SETWALK")
     env.delenv("MFA_SET_WAVE", raising=False)
-    assert img.info()["dfa_states"] == 0 and img.resume_state_bytes() == (4 * WORDS if wave else 48)
+    assert img.info()["dfa_states"] == 0 and img.resume_state_bytes() == (4 * WIDE_WORDS if wave else 48)
     return img
 
 
@@ -129,7 +127,7 @@ def test_raw_images_own_long_strings(env, n_nodes):
     env.setenv("MFA_NFA_SETWALK", "1")
     img = capi.Image(blob)
     env.delenv("MFA_NFA_SETWALK")
-    assert img.info()["n_nodes"] == n_nodes and img.resume_state_bytes() == 4 * WORDS
+    assert img.info()["n_nodes"] == n_nodes and img.resume_state_bytes() == 4 * WIDE_WORDS
     got, off = guarded_match(img, strings)
     mismatch(got, want, strings, name)
     report = check_split_report(img, off, name)
@@ -143,7 +141,7 @@ def test_all_four_instantiations_are_walked(tmp_path):
     cases = [(name, images[name][0]) for name in REGEX_IMAGES] + [(c[0], c[1]) for c in raw_by_nodes().values()]
     seen = {}
     for name, blob in cases:
-        tables = run_pieces(resume_emul_exe(), tmp_path, blob, [[b"ab"]])[0]
+        tables = run_wide_pieces(emul_exe("nfa_set_wave_resume"), tmp_path, blob, [[b"ab"]])[0]
         seen.setdefault((image.blob_info(blob)["reversed"], tables_in_lds(tables)), []).append(name)
     assert set(seen) == {(0, True), (0, False), (1, True), (1, False)}, seen
 
@@ -153,7 +151,7 @@ def test_all_four_instantiations_are_walked(tmp_path):
 def test_resume_form(env, name, tmp_path):
     """pieces in three rounds, long pieces cut: each round the records equal the whole-walk harness's word for word (guard quarters round
     them) and the results the oracle's; the count of queued pieces is the count of long pieces.  Dead and INVALID records are not queued"""
-    emul = resume_emul_exe()
+    emul = emul_exe("nfa_set_wave_resume")
     blob, alphabet, _ = wide_regex_images(tmp_path)[name]
     is_rev = image.blob_info(blob)["reversed"]
     rng = np.random.default_rng(17)
@@ -167,23 +165,23 @@ def test_resume_form(env, name, tmp_path):
         cuts = [(n - a, n), (n - a - b, n - a), (0, n - a - b)] if is_rev else [(0, a), (a, a + b), (a + b, n)]
         for r in range(3):
             rounds[r].append(cuts[r])
-    buf = new_records(len(strings))
+    buf = new_records(len(strings), WIDE_WORDS)
     for r in range(3):
         pieces = pieces_of(strings, rounds[r])
-        got = feed_wide(img, pieces, buf)
+        got = feed_records(img, pieces, buf, WIDE_WORDS)
         seen = [s[rounds[r][k][0]:] if is_rev else s[:rounds[r][k][1]] for k, s in enumerate(strings)]
         mismatch(got, ora.match(seen), seen, "round %d" % r)
-        _, _, recs_host = run_pieces(emul, tmp_path, blob, [seen])
-        assert np.array_equal(records_of(buf, len(strings)), recs_host), "round %d" % r
+        _, _, recs_host = run_wide_pieces(emul, tmp_path, blob, [seen])
+        assert np.array_equal(records_of(buf, len(strings), WIDE_WORDS), recs_host), "round %d" % r
         assert img.last_set_split()[0] == sum(1 for p in pieces if len(p) >= SPLIT_MIN) >= 3
         assert img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
     # dead, INVALID and a live neighbour, each with a long piece: only the neighbour is queued
-    rows = np.stack([record(LIVE), record(INVALID), record(0)])
-    buf = new_records(3, rows)
-    got = feed_wide(img, [strings[1]] * 3, buf)
-    recs = records_of(buf, 3)
+    rows = np.stack([record(WIDE_WORDS, LIVE), record(WIDE_WORDS, INVALID), record(WIDE_WORDS, 0)])
+    buf = new_records(3, WIDE_WORDS, rows)
+    got = feed_records(img, [strings[1]] * 3, buf, WIDE_WORDS)
+    recs = records_of(buf, 3, WIDE_WORDS)
     assert list(got[:2]) == [0, 2] and got[2] == ora.match([strings[1]])[0]
-    assert list(recs[0]) == [LIVE] + [0] * (WORDS - 1) and list(recs[1]) == [INVALID] + [0] * (WORDS - 1) and recs[2, 0] == LIVE
+    assert list(recs[0]) == [LIVE] + [0] * (WIDE_WORDS - 1) and list(recs[1]) == [INVALID] + [0] * (WIDE_WORDS - 1) and recs[2, 0] == LIVE
     assert img.last_set_split()[0] == 1
 
 
@@ -197,14 +195,14 @@ def test_resume_form_without_result_bytes(env, tmp_path):
     thirds = [(2048, 1500), (1024, 1025), (5000, 1024), (100, 3000)]
     rounds = [[s[len(s) - a:] for s, (a, b) in zip(strings, thirds)], [s[len(s) - a - b:len(s) - a] for s, (a, b) in zip(strings, thirds)],
               [s[:len(s) - a - b] for s, (a, b) in zip(strings, thirds)]]      # (the image scans from the end)
-    buf = new_records(len(strings))
+    buf = new_records(len(strings), WIDE_WORDS)
     for r in range(2):
-        assert feed_wide(img, rounds[r], buf, results=False) is None
+        assert feed_records(img, rounds[r], buf, WIDE_WORDS, results=False) is None
         assert img.last_set_split()[0] == sum(1 for p in rounds[r] if len(p) >= SPLIT_MIN) >= 3
-    got = feed_wide(img, rounds[2], buf)
+    got = feed_records(img, rounds[2], buf, WIDE_WORDS)
     mismatch(got, oracle_lib.OracleImage(blob).match(strings), strings, "no result bytes")
-    _, _, recs_host = run_pieces(resume_emul_exe(), tmp_path, blob, [strings])
-    assert np.array_equal(records_of(buf, len(strings)), recs_host)
+    _, _, recs_host = run_wide_pieces(emul_exe("nfa_set_wave_resume"), tmp_path, blob, [strings])
+    assert np.array_equal(records_of(buf, len(strings), WIDE_WORDS), recs_host)
 
 
 # ---- counts -----------------------------------------------------------------------------------------------------------------------------
@@ -217,7 +215,7 @@ def counts_against_the_harness(env, tmp_path, img, blob, strings, rounds, lookba
     got, off = guarded_match(img, strings)
     mismatch(got, oracle_lib.OracleImage(blob).match(strings), strings, "rounds %d" % rounds)
     report = check_split_report(img, off, "rounds %d" % rounds)
-    (_, host, _), = run_wave_split(wave_split_emul_exe(), tmp_path, blob, strings, (CHUNK,), (lookback,), (rounds,))
+    (_, host, _), = run_wave_split(emul_exe("nfa_set_wave_split"), tmp_path, blob, strings, (CHUNK,), (lookback,), (rounds,))
     assert report[3:] == (host["rewalked"], host["serial_strings"], host["serial_bytes"]), (report, host)
     return report, host
 
@@ -271,7 +269,7 @@ def test_six_zeros_and_the_same_answers(env, knob, tmp_path):
     off, _ = guarded_match(img, strings)
     mismatch(off, want, strings, "%s=0" % knob)
     assert img.last_set_split() == ZEROS and img.last_dfa_split() == (0, 0, 0) and img.last_dfa_spec() == (0, 0, 0)
-    mismatch(feed_wide(img, strings, new_records(len(strings))), want, strings, "%s=0, resume form" % knob)
+    mismatch(feed_records(img, strings, new_records(len(strings), WIDE_WORDS), WIDE_WORDS), want, strings, "%s=0, resume form" % knob)
     assert img.last_set_split() == ZEROS
 
 
@@ -380,9 +378,9 @@ def test_host_pointers(env, tmp_path):
     mismatch(img.match_host(data, off), want, strings, "host")
     n_long = sum(1 for s in strings if len(s) >= SPLIT_MIN)
     assert img.last_set_split()[0] == n_long
-    states = np.zeros(len(strings) * WORDS, dtype=np.uint32)
+    states = np.zeros(len(strings) * WIDE_WORDS, dtype=np.uint32)
     mismatch(img.match_host_resume_set_wide(data, off, states), want, strings, "host, resume form")
-    assert img.last_set_split()[0] == n_long and (states.reshape(-1, WORDS)[:, 0] == LIVE).all()
+    assert img.last_set_split()[0] == n_long and (states.reshape(-1, WIDE_WORDS)[:, 0] == LIVE).all()
 
 
 def test_mixed_object_inherits_the_path(env, tmp_path):
@@ -423,7 +421,7 @@ def counter_image(env, blob):
     env.setenv("MFA_DFA_STATE_LIMIT", "100")
     img = capi.Image(blob)
     env.delenv("MFA_DFA_STATE_LIMIT")
-    assert img.info()["dfa_states"] == 0 and img.resume_state_bytes() == 4 * WORDS
+    assert img.info()["dfa_states"] == 0 and img.resume_state_bytes() == 4 * WIDE_WORDS
     return img
 
 
@@ -451,7 +449,7 @@ def test_command_line_pieces_that_are_cut(env, tmp_path):
     # the wide host call, no result bytes before the last), under the knobs it ran with -- every piece that enters alive is queued and cut
     img = counter_image(env, blob)
     strings = [w.encode() for w in words[:3]]
-    states = np.zeros(len(strings) * WORDS, dtype=np.uint32)
+    states = np.zeros(len(strings) * WIDE_WORDS, dtype=np.uint32)
     queued = []
     for r in range(3):
         data, off = oracle_lib.pack([s[2048 * r:2048 * (r + 1)] for s in strings])

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 from mfa_amd import capi
-from select_lib import (ALL_FLAGS, CSRC, INVERT, NEWLINE, all_cases, case, check_against_python, emul_results, expected, geometry,
-                        select_emul_exe)
+from select_lib import (ALL_FLAGS, INVERT, NEWLINE, all_cases, case, check_against_python, emul_results, expected, geometry)
+from testlib import CSRC, emul_exe
 
 B, T, SCAN_ROUND = geometry()
 
@@ -52,13 +52,13 @@ def test_cases_cover_what_they_are_for(cases):
 
 
 def test_harness_against_python(cases, tmp_path):
-    check_against_python(emul_results(select_emul_exe(), tmp_path, cases), cases, "harness")
+    check_against_python(emul_results(emul_exe("select"), tmp_path, cases), cases, "harness")
 
 
 def test_under_sanitizers(cases, tmp_path):
     """the same cases once more with the harness built with -fsanitize=address,undefined (a plain executable, nothing preloaded): the
     strings lie in exactly the aligned 16-byte blocks they touch and every output in exactly its capacity"""
-    exe = select_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("select", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     check_against_python(emul_results(exe, tmp_path, cases), cases, "sanitized")
 
 

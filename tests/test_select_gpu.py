@@ -12,8 +12,8 @@ import torch
 
 import oracle_lib
 from mfa_amd import capi, image
-from select_lib import (INVERT, NEWLINE, all_cases, case, emul_results, expected_case, fill, info_dict, select_emul_exe)
-from testlib import DIPLOMA
+from select_lib import (INVERT, NEWLINE, all_cases, case, emul_results, expected_case, fill, info_dict)
+from testlib import DIPLOMA, emul_exe
 
 pytestmark = pytest.mark.gpu
 GUARD, GUARD8, FRONT = 0x5a, 0x5a5a5a5a5a5a5a5a, 64
@@ -100,7 +100,7 @@ def test_every_case_against_python_and_the_harness(tmp_path):
     workgroup, every clipping and the 200 random batches: count and write with no wait in between, compared with the rule in Python and,
     byte for byte, with what the host harness leaves"""
     cases = all_cases()
-    emul = emul_results(select_emul_exe(), tmp_path, cases)
+    emul = emul_results(emul_exe("select"), tmp_path, cases)
     for c, e in zip(cases, emul):
         same(gpu_select(c), expected_case(c), e, c)
 

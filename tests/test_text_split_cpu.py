@@ -12,16 +12,15 @@ import numpy as np
 import pytest
 
 from mfa_amd import capi
-from testlib import EMUL_DIR
-from textsplit_lib import (LINES, STOP, TOKENS, both_modes, edge_texts, emul_results, expected, py_split, random_texts, split_emul_exe,
-                           tile_bytes)
+from testlib import EMUL_DIR, emul_exe
+from textsplit_lib import (LINES, STOP, TOKENS, both_modes, edge_texts, emul_results, expected, py_split, random_texts, tile_bytes)
 
 T = tile_bytes()
 
 
 @pytest.fixture(scope="module")
 def emul():
-    return split_emul_exe()
+    return emul_exe("text_split")
 
 
 @pytest.fixture(scope="module")
@@ -127,7 +126,7 @@ def test_against_libstdcxx(emul, iostream_exe, tmp_path):
 def test_under_sanitizers(tmp_path):
     """the harness once more as a stand-alone program built with -fsanitize=address,undefined (a plain executable, nothing preloaded): the
     edge texts, 40 random ones and the clipped cases, with the text, d_bytes and d_offsets in exactly the room they are promised"""
-    exe = split_emul_exe("-fsanitize=address,undefined -fno-sanitize-recover=all")
+    exe = emul_exe("text_split", "-fsanitize=address,undefined -fno-sanitize-recover=all")
     texts = list(edge_texts(T).values()) + random_texts(T)[:40]
     cases = both_modes(texts)
     for t in texts[:50]:

@@ -11,9 +11,8 @@ import torch
 
 import oracle_lib
 from mfa_amd import capi, image
-from testlib import DIPLOMA
-from textsplit_lib import (LINES, STOP, TOKENS, both_modes, edge_texts, emul_results, expected, info_dict, py_split, random_texts,
-                           split_emul_exe)
+from testlib import DIPLOMA, emul_exe
+from textsplit_lib import (LINES, STOP, TOKENS, both_modes, edge_texts, emul_results, expected, info_dict, py_split, random_texts)
 
 pytestmark = pytest.mark.gpu
 GUARD = 0x5a
@@ -91,7 +90,7 @@ def test_stop_token(T):
 def test_random_texts_against_the_harness(T, tmp_path):
     """the 300 random texts of the CPU test, both modes: info record, offsets and bytes as the host harness leaves them, byte for byte"""
     cases = both_modes(random_texts(T))
-    want = emul_results(split_emul_exe(), tmp_path, cases)
+    want = emul_results(emul_exe("text_split"), tmp_path, cases)
     for k, ((text, mode, stop, _, _), (_, w_off, w_data, w_raw)) in enumerate(zip(cases, want)):
         raw_info, off, data = gpu_split(text, mode, stop, shift=k % 16)
         assert raw_info == w_raw, "case %d: %r != %r" % (k, info_dict(raw_info), info_dict(w_raw))

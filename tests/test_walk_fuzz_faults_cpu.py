@@ -17,10 +17,10 @@ import pytest
 
 import oracle_lib
 import regex_fuzz
-from testlib import EMUL_DIR, walk_emul_run
+from testlib import CSRC, EMUL_DIR, walk_emul_run
 
-CSRC = os.path.join("re2-modification_amd", "csrc")
-CORE, TABLES = os.path.join(CSRC, "walk_core.h"), os.path.join(CSRC, "walk_tables.cpp")
+REL_CSRC = os.path.relpath(CSRC, oracle_lib.ROOT)
+CORE, TABLES = os.path.join(REL_CSRC, "walk_core.h"), os.path.join(REL_CSRC, "walk_tables.cpp")
 N_REGEX, NCELL, SETTING = 44, 9, (8, 0)                     # the corpus of tests/test_walk_fuzz_cpu.py; (list capacity, regions)
 
 # name -> (file, text, replacement)
@@ -46,11 +46,11 @@ UNPLANTED = "no fault"
 
 def plant(root, fault):
     """the copy of the walk source under `root`, with the fault's replacement made"""
-    os.makedirs(os.path.join(root, CSRC))
+    os.makedirs(os.path.join(root, REL_CSRC))
     shutil.copytree(os.path.join(oracle_lib.ROOT, "include"), os.path.join(root, "include"))
     for pattern in ("*.h", "walk_tables.cpp", "image_host.cpp"):
-        for src in glob.glob(os.path.join(oracle_lib.ROOT, CSRC, pattern)):
-            shutil.copy(src, os.path.join(root, CSRC))
+        for src in glob.glob(os.path.join(CSRC, pattern)):
+            shutil.copy(src, os.path.join(root, REL_CSRC))
     if fault is not None:
         name, old, new = fault
         with open(os.path.join(root, name)) as f:

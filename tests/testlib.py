@@ -18,6 +18,7 @@ from mfa_amd import capi, image
 
 DIPLOMA = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "host", "diploma")
 EMUL_DIR = os.path.join(oracle_lib.ROOT, "tests", "emul")
+CSRC = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "csrc")
 
 with open(os.path.join(oracle_lib.GOLDEN, "manifest.json")) as f:
     MANIFEST = json.load(f)

@@ -1,40 +1,17 @@
-"""What tests/test_text_split_cpu.py and tests/test_text_split_gpu.py share: the rule in Python, the host harness
-tests/emul/text_split_emul.cpp built once per session, its case files and its output, the edge texts and the seeded random ones --
+"""What tests/test_text_split_cpu.py and tests/test_text_split_gpu.py share: the rule in Python, the case files of the host harness
+tests/emul/text_split_emul.cpp (built by testlib.emul_exe) and its output, the edge texts and the seeded random ones --
 TEST INFRASTRUCTURE ONLY: no tests, no fixtures, no marks in here."""
-import atexit
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
-import oracle_lib
-from testlib import EMUL_DIR
+from testlib import CSRC
 
-CSRC = os.path.join(oracle_lib.ROOT, "re2-modification_amd", "csrc")
 LINES, TOKENS = 0, 1
 STOP = b"exit"
 ALPHABET = [b"a", b"b", b"e", b"x", b"i", b"t", b" ", b"\n", b"\t", b"\r", b"\x0b", b"\x00"]
-
-_built = {}
-
-
-def split_emul_exe(flags=""):
-    """tests/emul/text_split_emul.cpp through the HIP shim, with `flags` behind the caller's EMUL_FLAGS, once per session, in a temporary
-    directory of its own; the compiler is heard only when it fails"""
-    if flags not in _built:
-        folder = tempfile.mkdtemp(prefix="text_split_emul_")
-        atexit.register(shutil.rmtree, folder, ignore_errors=True)
-        exe = os.path.join(folder, "text_split_emul")
-        cmd = (["g++", "-O2", "-g", "-std=c++17"] + (os.environ.get("EMUL_FLAGS", "") + " " + flags).split()
-               + ["-Wall", "-Ishim", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-unused-variable", "-I" + CSRC,
-                  "-I" + os.path.join(oracle_lib.ROOT, "include"), "-o", exe, "text_split_emul.cpp"])
-        p = subprocess.run(cmd, cwd=EMUL_DIR, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, "building text_split_emul failed:\n%s" % p.stdout
-        _built[flags] = exe
-    return _built[flags]
 
 
 def tile_bytes():

@@ -176,12 +176,23 @@ int match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
     return rc;
 }
 
-// Whatever happens to a launch once it holds a context, the context's `done` event is recorded behind what was enqueued: a launch on
-// another stream must not be handed this context (its counter, scratch area and table) while a kernel of this call may still be using it
-struct DoneGuard {
-    LaunchCtx* cx; void* stream;
-    ~DoneGuard() { (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
+// A launch: the image's lock, its state on the device and a context.  Whatever happens to a launch once it holds a context, the context's
+// `done` event is recorded behind what was enqueued (before the lock goes): a launch on another stream must not be handed this context (its
+// counter, scratch area and table) while a kernel of this call may still be using it
+struct Launch {
+    std::unique_lock<std::mutex> lk;
+    DeviceState* ds = nullptr; LaunchCtx* cx = nullptr; void* stream = nullptr;
+    ~Launch() { if (cx) (void)hipEventRecord((hipEvent_t)cx->ev_done, (hipStream_t)stream); }
 };
+// locks the image and prepares the device (unless L holds them already), takes the context for a launch on `stream`, notes which kernel walks
+static int launch_open(mfa_image* img, int device, void* stream, uint32_t kernel, Launch& L) {
+    int rc = MFA_OK;
+    if (!L.ds) { L.lk = std::unique_lock<std::mutex>(img->mu); rc = device_prepare(img, device, &L.ds); }
+    if (rc == MFA_OK) rc = ctx_acquire(*L.ds, stream, &L.cx);
+    if (rc != MFA_OK) return rc;
+    L.stream = stream; img->last_kernel = kernel;
+    return MFA_OK;
+}
 
 // the workspace of the image's last launch on `device`, or nullptr; the caller holds img->mu
 static LaunchCtx* last_ctx(mfa_image* img, int device) {
@@ -201,6 +212,18 @@ static int last_split_header(mfa_image* img, int device, bool LaunchCtx::*ran, u
         HIP_TRY(hipMemcpy(h, cx->d_split, sizeof h, hipMemcpyDeviceToHost));
     }
     return MFA_OK;
+}
+
+// what the plan kernel, and what the repair and resolve kernels, left in a header
+static void split_words(const uint32_t (&h)[SPLIT_H_WORDS], uint64_t* strings, uint64_t* chunks, uint32_t* chunk_bytes) {
+    if (strings) *strings = h[SPLIT_H_STRINGS];
+    if (chunks) *chunks = h[SPLIT_H_CHUNKS];
+    if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
+}
+static void spec_words(const uint32_t (&h)[SPLIT_H_WORDS], uint64_t* rewalked_chunks, uint64_t* serial_strings, uint64_t* serial_bytes) {
+    if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
+    if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
+    if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
 }
 
 }  // namespace mfa
@@ -268,10 +291,11 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
                       const uint64_t* d_table, bool own_regions, int device, void* stream) {
     if (!img || !d_offsets || (!d_results && n)) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
-    std::lock_guard<std::mutex> lk(img->mu);
-    DeviceState* ds = nullptr;
-    int rc = device_prepare(img, device, &ds);
+    Launch L;
+    L.lk = std::unique_lock<std::mutex>(img->mu);
+    int rc = device_prepare(img, device, &L.ds);
     if (rc != MFA_OK) return rc;
+    DeviceState* ds = L.ds;
     const bool is_mfa = img->host.h.kind == MFA_KIND_MFA;
     // Which walk: the table-driven kernel (walk.hip) works for every automaton at once; a kernel generated for this automaton
     // (jit_gen.cpp) steps faster on small automata but has to be compiled first.  Automatic: the generated kernel if its code object
@@ -294,11 +318,9 @@ static int match_impl(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* 
     if (is_mfa && !jit) { const char* rq = getenv("MFA_REQUIRE_JIT"); if (rq && rq[0] == '1') return MFA_ERR_JIT; }
     if (const char* vb = getenv("MFA_VERBOSE"))
         if (vb[0] == '1') fprintf(stderr, "mfa_hip: %s\n", !is_mfa ? img->host.set_wave ? "set walk of the automaton's nodes, one string per wave (nfa_set_wave_kernel)" : img->host.set_walk ? "set walk of the automaton's nodes (nfa_set_kernel)" : "table walk of the tabulated automaton (dfa_*_kernel)" : jit ? "kernel generated for this automaton (mfa_jit_kernel)" : "table-driven walk (walk_kernel)");
-    LaunchCtx* cx = nullptr;
-    rc = ctx_acquire(*ds, stream, &cx);
+    rc = launch_open(img, device, stream, table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : img->host.set_walk ? MFA_KERNEL_NODESET : MFA_KERNEL_TABLE, L);
     if (rc != MFA_OK) return rc;
-    DoneGuard done_guard{cx, stream};
-    img->last_kernel = table_walk ? MFA_KERNEL_WALK : jit ? MFA_KERNEL_SPECIALISED : img->host.set_walk ? MFA_KERNEL_NODESET : MFA_KERNEL_TABLE;
+    LaunchCtx* cx = L.cx;
     if (is_mfa && own_regions && regions_enabled()) {
         rc = ctx_reserve((void**)&cx->d_regions, &cx->region_bytes, (size_t)n * MFA_REGION_WORDS * sizeof(uint64_t));
         if (rc != MFA_OK) return rc;
@@ -363,16 +385,10 @@ int mfa_match_batch_resume(mfa_image_t* img, const uint8_t* d_bytes, const uint6
     if (img->host.set_walk) return MFA_ERR_UNSUPPORTED;                    // a set-walk image's state is a set of nodes, not one 32-bit number
     if (!d_states) return MFA_ERR_INVALID_ARG;
     if (n == 0) return MFA_OK;
-    std::lock_guard<std::mutex> lk(img->mu);
-    DeviceState* ds = nullptr;
-    int rc = device_prepare(img, device, &ds);
+    Launch L;
+    const int rc = launch_open(img, device, stream, MFA_KERNEL_TABLE, L);
     if (rc != MFA_OK) return rc;
-    LaunchCtx* cx = nullptr;
-    rc = ctx_acquire(*ds, stream, &cx);
-    if (rc != MFA_OK) return rc;
-    DoneGuard done_guard{cx, stream};
-    img->last_kernel = MFA_KERNEL_TABLE;
-    return launch_dfa_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, d_states, d_results, stream);
+    return launch_dfa_resume(img->host, *L.ds, *L.cx, d_bytes, d_offsets, n, d_states, d_results, stream);
 }
 
 // host pointers: stage the pieces and the states, match, copy states (and results, unless NULL) back, synchronise.  No length check
@@ -396,16 +412,10 @@ int mfa_match_batch_resume_set(mfa_image_t* img, const uint8_t* d_bytes, const u
     if (img->host.set_wave) return MFA_ERR_UNSUPPORTED;                    // a wave image's set may take 64 words, a record has eight: the records are left as they came
     if ((uintptr_t)d_states & 15u) return MFA_ERR_INVALID_ARG;             // the kernel reads and writes a record as 16-byte quarters
     if (n == 0) return MFA_OK;
-    std::lock_guard<std::mutex> lk(img->mu);
-    DeviceState* ds = nullptr;
-    int rc = device_prepare(img, device, &ds);
+    Launch L;
+    const int rc = launch_open(img, device, stream, MFA_KERNEL_NODESET, L);
     if (rc != MFA_OK) return rc;
-    LaunchCtx* cx = nullptr;
-    rc = ctx_acquire(*ds, stream, &cx);
-    if (rc != MFA_OK) return rc;
-    DoneGuard done_guard{cx, stream};
-    img->last_kernel = MFA_KERNEL_NODESET;
-    return launch_nfa_set_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
+    return launch_nfa_set_resume(img->host, *L.ds, *L.cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
 }
 
 // host pointers: as mfa_match_batch_resume_host, with records of sizeof(mfa_set_state) (the staging buffer is 16-byte aligned whatever
@@ -435,18 +445,11 @@ int mfa_match_batch_resume_set_wide(mfa_image_t* img, const uint8_t* d_bytes, co
     if (rc != MFA_OK) return rc;
     if ((uintptr_t)d_states & 15u) return MFA_ERR_INVALID_ARG;             // the kernel reads and writes a record's tag as one 16-byte quarter
     if (n == 0) return MFA_OK;
-    std::lock_guard<std::mutex> lk(img->mu);
-    DeviceState* ds = nullptr;
-    rc = device_prepare(img, device, &ds);
-    if (rc != MFA_OK) return rc;
+    Launch L;
+    if ((rc = launch_open(img, device, stream, MFA_KERNEL_NODESET, L)) != MFA_OK) return rc;
     if (const char* vb = getenv("MFA_VERBOSE"))      // (as mfa_match_batch: which kernel walks, on stderr)
         if (vb[0] == '1') fprintf(stderr, "mfa_hip: set walk of the automaton's nodes on strings in pieces, one string per wave (nfa_set_wave_resume_kernel)\n");
-    LaunchCtx* cx = nullptr;
-    rc = ctx_acquire(*ds, stream, &cx);
-    if (rc != MFA_OK) return rc;
-    DoneGuard done_guard{cx, stream};
-    img->last_kernel = MFA_KERNEL_NODESET;
-    return launch_nfa_set_wave_resume(img->host, *ds, *cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
+    return launch_nfa_set_wave_resume(img->host, *L.ds, *L.cx, d_bytes, d_offsets, n, reinterpret_cast<uint32_t*>(d_states), d_results, stream);
 }
 
 // host pointers: as mfa_match_batch_resume_set_host, with records of sizeof(mfa_set_state_wide)
@@ -481,9 +484,7 @@ int mfa_last_dfa_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t
     uint32_t h[SPLIT_H_WORDS] = {0};
     const int rc = last_split_header(img, device, &LaunchCtx::split_ran, h);
     if (rc != MFA_OK) return rc;
-    if (strings) *strings = h[SPLIT_H_STRINGS];
-    if (chunks) *chunks = h[SPLIT_H_CHUNKS];
-    if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
+    split_words(h, strings, chunks, chunk_bytes);
     return MFA_OK;
 }
 
@@ -491,9 +492,7 @@ int mfa_last_dfa_spec(mfa_image_t* img, int device, uint64_t* rewalked_chunks, u
     uint32_t h[SPLIT_H_WORDS] = {0};
     const int rc = last_split_header(img, device, &LaunchCtx::spec_ran, h);
     if (rc != MFA_OK) return rc;
-    if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
-    if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
-    if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
+    spec_words(h, rewalked_chunks, serial_strings, serial_bytes);
     return MFA_OK;
 }
 
@@ -502,12 +501,8 @@ int mfa_last_set_split(mfa_image_t* img, int device, uint64_t* strings, uint64_t
     uint32_t h[SPLIT_H_WORDS] = {0};
     const int rc = last_split_header(img, device, &LaunchCtx::set_split_ran, h);
     if (rc != MFA_OK) return rc;
-    if (strings) *strings = h[SPLIT_H_STRINGS];
-    if (chunks) *chunks = h[SPLIT_H_CHUNKS];
-    if (chunk_bytes) *chunk_bytes = h[SPLIT_H_STRINGS] ? h[SPLIT_H_CHUNK] : 0u;
-    if (rewalked_chunks) *rewalked_chunks = h[SPEC_H_REWALKED];
-    if (serial_strings) *serial_strings = h[SPEC_H_SERIAL_STRINGS];
-    if (serial_bytes) *serial_bytes = (uint64_t)h[SPEC_H_SERIAL_BYTES] | (uint64_t)h[SPEC_H_SERIAL_BYTES + 1u] << 32;
+    split_words(h, strings, chunks, chunk_bytes);
+    spec_words(h, rewalked_chunks, serial_strings, serial_bytes);
     return MFA_OK;
 }
 

@@ -11,8 +11,6 @@
 // is read and written by the lane of chunk c alone.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "mfa_internal.h"
 #include "dfa_spec_core.h"
 
@@ -135,30 +133,12 @@ dfa_spec_resolve_kernel(const T* __restrict__ trans, const uint8_t* __restrict__
 // ---- host side ---------------------------------------------------------------------------------------
 bool spec_applies(const HostImage& img) {
     // the tables launch_dfa_walk and launch_dfa_resume give the L2 kernels: beyond 16-bit pre-multiplied states, 255 state sets and more
-    // (split_applies has those up to 127; 128 to 254 are outside both, as they are outside mfa_match_batch)
+    // (dfa_split.hip has those up to 127; 128 to 254 are outside both, as they are outside mfa_match_batch)
     return img.h.kind == MFA_KIND_NFA && (size_t)img.dfa_states * kDfaRow > 0xffffu;
 }
 
-// arena: start_used[map_cap], end[2][map_cap]
-static constexpr size_t kSpecWordsPerChunk = 3;
-
-int spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
-    *out = SplitLaunch{};
-    cx.split_ran = false;
-    cx.spec_ran = false;
-    const char* on = getenv("MFA_DFA_SPEC");
-    if ((on && on[0] == '0') || !spec_applies(img)) return MFA_OK;
-    uint64_t rounds = env_u64("MFA_DFA_SPEC_ROUNDS", kSpecRounds), lookback = env_u64("MFA_DFA_SPEC_LOOKBACK", kSpecLookback);
-    out->spec_rounds = (uint32_t)(rounds > kSpecRoundsMax ? kSpecRoundsMax : rounds);
-    out->spec_lookback = (uint32_t)(lookback > MFA_MAX_STRING_BYTES ? MFA_MAX_STRING_BYTES : lookback);
-    // A workspace starts QUIET here: until it has met a long string once (the main kernel then writes 3 to the pinned word) it launches the
-    // main kernel alone, so traffic of short strings never pays for the seven launches behind it, and the first batch with long strings on
-    // a workspace is walked whole, as it was before this path existed; from the next call on the workspace keeps the tail for good.
-    // MFA_DFA_SPLIT=2 launches the tail from the first call on.
-    const int rc = split_begin_arena(cx, n, stream, out, kSpecWordsPerChunk * sizeof(uint32_t), true, kSplitChunkMin);
-    cx.spec_ran = cx.split_ran;
-    return rc;
-}
+static_assert(kSplitSchemeL2.per_chunk == 3 * sizeof(uint32_t) && kSplitSchemeL2.rounds == kSpecRounds && kSplitSchemeL2.lookback == kSpecLookback &&
+              kSplitRoundsMax == kSpecRoundsMax, "memless_plan.h: the L2 scheme");
 
 template <bool REV, class T>
 static int spec_main_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
@@ -166,37 +146,35 @@ static int spec_main_go(const HostImage& img, DeviceState& ds, const SplitLaunch
     auto kern = d_states != nullptr ? dfa_spec_big_kernel<REV, T, true> : dfa_spec_big_kernel<REV, T, false>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, (const T*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class, img.dfa_states, img.n_classes,
                        d_bytes, d_offsets, n, d_states, d_results, sl.args);
-    HIP_TRY(hipGetLastError());
-    return MFA_OK;
+    return MFA_OK;                                                    // (memless_bracket asks for the launch's error)
 }
 
+// (A workspace starts QUIET here, kSplitSchemeL2: traffic of short strings never pays for the seven launches below, and the first batch with
+// long strings on a workspace is walked whole, as it was before this path existed.  MFA_DFA_SPLIT=2 launches them from the first call on.)
 template <bool REV, class T>
 static int spec_tail_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                         uint8_t* d_results, hipStream_t s, uint32_t* d_states) {
-    const int rc = split_plan(sl, d_offsets, s);
-    if (rc != MFA_OK) return rc;
     const T* trans = (const T*)ds.d_dfa_trans;
-    uint32_t* start_used = reinterpret_cast<uint32_t*>(sl.maps);
-    uint32_t* end[2] = {start_used + sl.map_cap, start_used + 2u * (size_t)sl.map_cap};
+    const SplitEntry* queue = sl.args.queue;
     // one lane per chunk, the chunk count is the plan's: a grid for every chunk the arena holds, blocks beyond the count leave at once
-    const unsigned n_cus = (unsigned)(ds.n_cus > 0 ? ds.n_cus : 256);
-    unsigned blocks = (sl.map_cap + 255u) / 256u;
-    if (blocks > n_cus * 8u) blocks = n_cus * 8u;
-    hipLaunchKernelGGL((dfa_spec_walk_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
-                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, end[0], (const uint32_t*)d_states, img.dfa_home, sl.spec_lookback);
-    HIP_TRY(hipGetLastError());
-    for (uint32_t r = 1; r <= sl.spec_rounds; r++) {
-        hipLaunchKernelGGL((dfa_spec_repair_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
-                           sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, (const uint32_t*)end[(r - 1u) & 1u], end[r & 1u]);
-        HIP_TRY(hipGetLastError());
-    }
-    const uint32_t* end_fin = end[sl.spec_rounds & 1u];
-    const unsigned q_blocks = (sl.args.qcap + 255u) / 256u;
-    auto resolve = d_states != nullptr ? dfa_spec_resolve_kernel<REV, T, true> : dfa_spec_resolve_kernel<REV, T, false>;
-    hipLaunchKernelGGL(resolve, dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes, d_bytes, d_offsets, sl.args.hdr,
-                       (const SplitEntry*)sl.args.queue, (const uint32_t*)start_used, end_fin, d_states, d_results);
-    HIP_TRY(hipGetLastError());
-    return MFA_OK;
+    const unsigned blocks = persistent_grid(sl.map_cap, 256, (uint64_t)ds.n_cus, 8), q_blocks = (sl.args.qcap + 255u) / 256u;
+    return guess_tail<uint32_t>(sl, 1, d_offsets, s,
+        [&](uint32_t* start_used, uint32_t* end0) {
+            hipLaunchKernelGGL((dfa_spec_walk_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
+                               (const uint32_t*)sl.args.hdr, queue, start_used, end0, (const uint32_t*)d_states, img.dfa_home, sl.spec_lookback);
+            return MFA_OK;
+        },
+        [&](uint32_t* start_used, const uint32_t* end_prev, uint32_t* end_next) {
+            hipLaunchKernelGGL((dfa_spec_repair_kernel<REV, T>), dim3(blocks), dim3(256), 0, s, trans, ds.d_byte_class, img.n_classes, d_bytes, d_offsets,
+                               sl.args.hdr, queue, start_used, end_prev, end_next);
+            return MFA_OK;
+        },
+        [&](const uint32_t* start_used, const uint32_t* end_fin) {
+            auto resolve = d_states != nullptr ? dfa_spec_resolve_kernel<REV, T, true> : dfa_spec_resolve_kernel<REV, T, false>;
+            hipLaunchKernelGGL(resolve, dim3(q_blocks), dim3(256), 0, s, trans, ds.d_dfa_accept, ds.d_byte_class, img.n_classes, d_bytes, d_offsets, sl.args.hdr,
+                               queue, start_used, end_fin, d_states, d_results);
+            return MFA_OK;
+        });
 }
 
 #define MFA_SPEC_DISPATCH(FN, ...)                                                                                  \

@@ -5,6 +5,7 @@
 #define MFA_DFA_SPLIT_H
 
 #include "dfa_resume_core.h"      // and dfa_split_core.h
+#include "memless_plan.h"         // kSplitChunkMin and the other figures of the host side
 
 namespace mfa {
 
@@ -17,13 +18,12 @@ enum : uint32_t {
     SPLIT_H_WORDS = 8,
 };
 
-static constexpr uint32_t kSplitChunkMin = 4096;            // MFA_DFA_CHUNK of the tabulated engines; DESIGN.md section 4.5 has the sweep
-
 struct SplitEntry {
     uint64_t sid;            // string number
     uint32_t first, nc;      // its first map in the arena, its chunk count; maps are stored in scan order
     uint32_t dead_at, pad;   // lowest scan index of a chunk whose map is all 0 (0xffffffff: none known): later chunks need no walk
 };
+static_assert(sizeof(SplitEntry) == kSplitEntryBytes && kDfaRow == kMemlessRow, "memless_plan.h lays out the workspace and sizes the tables");
 
 // argument of the main kernels.  split_min == 0: the split path is off, the kernel behaves as it always has.
 struct SplitArgs {

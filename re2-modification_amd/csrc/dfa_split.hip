@@ -7,18 +7,12 @@
 // Geometry, chunk size, the chunk walk and the composition of maps are in dfa_split_core.h (checked on the CPU: tests/emul).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "mfa_internal.h"
 
 namespace mfa {
 
-static constexpr uint32_t kSplitQueueCap = 16384;           // long strings per call; the ones beyond are walked by the main kernel
-static constexpr uint32_t kSplitArenaChunks = 131072;       // the chunk size grows so that the chunks stay near this count
-static constexpr uint64_t kSplitMinDefault = 64u * 1024u;   // MFA_DFA_SPLIT_MIN; never below 64 KiB by default
 static constexpr uint32_t kFoldTileBytes = 32768;           // maps of one string staged in LDS per round of the fold
 static constexpr uint32_t kPlanThreads = 1024;
-static constexpr uint32_t kSplitQuietCalls = 4;             // launches in a row without a long string before the tail is left out
 
 // ---- plan --------------------------------------------------------------------------------------------
 // inclusive scan over the block's values; s[kPlanThreads - 1] is the total
@@ -169,75 +163,31 @@ dfa_fold_kernel(const uint8_t* __restrict__ accept_tab, const uint32_t* __restri
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-uint64_t env_u64(const char* name, uint64_t dflt) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    return end == e ? dflt : (uint64_t)v;
-}
-
-bool split_applies(const HostImage& img) {
-    return img.h.kind == MFA_KIND_NFA && img.dfa_states >= 2 && img.dfa_states <= 127;     // the table lives in LDS
-}
-
-int split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
+// (memless_plan.h: plan_split has the knobs, the quiet-workspace rule and the layout; here are its four HIP calls)
+int split_begin(const SplitScheme& sc, const MemlessKnobs& kn, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
     *out = SplitLaunch{};
-    cx.split_ran = false;
-    cx.spec_ran = false;
-    if (!split_applies(img)) return MFA_OK;
-    out->lanes_log2 = split_lanes_log2(img.dfa_states);
-    return split_begin_arena(cx, n, stream, out, (size_t)1 << out->lanes_log2, false, kSplitChunkMin);
-}
-
-// What split_begin and spec_begin (dfa_spec.hip) share: the knobs, the quiet-workspace rule, queue and arena -- `per_chunk` bytes of arena for
-// each of the map_cap chunks the plan can hand out -- and the zeroed header.  *out is the caller's, cleared but for what it has set itself.
-// start_quiet: a workspace counts as quiet from its first call on, not after kSplitQuietCalls calls without a long string (dfa_spec.hip).
-// chunk_min_default: the chunk minimum where MFA_DFA_CHUNK is not set (kSplitChunkMin; nfa_set_split.hip has its own).
-// arena_cap: the most chunks of arena this caller reserves records for (0: kSplitArenaChunks; nfa_set_wave_split.hip's records are 816 bytes).
-int split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default,
-                      uint32_t arena_cap) {
-    const char* on = getenv("MFA_DFA_SPLIT");
-    // (n < 2^31: the queue counter is a 32-bit word that every long string increments, also when the queue is full; it must not wrap)
-    if ((on && on[0] == '0') || n >= 0x80000000ull) return MFA_OK;
-    uint64_t split_min = env_u64("MFA_DFA_SPLIT_MIN", kSplitMinDefault);
-    if (split_min == 0) split_min = 1;
-    out->args.split_min = split_min;
-    // Leaving the tail out.  Memset, plan, chunk and fold cost a stream of 1 KiB strings a few microseconds per call (DESIGN.md section 4.5
-    // has the figure), so a workspace whose last kSplitQuietCalls launches all reported "no long string" (the plan kernel writes 1) launches
-    // the main kernel alone.  That kernel walks whatever it meets, and if it meets a long string it writes 3.  A workspace that has read a 3
-    // once keeps the tail for good: what the hint can cost is ONE long string walked whole per workspace, never one per batch.
-    // MFA_DFA_SPLIT=2: always with the tail (measurements).
-    if (cx.split_seen == nullptr) {
+    cx.split_ran = cx.spec_ran = cx.set_split_ran = false;
+    if (cx.split_seen == nullptr && split_on(sc, kn, n)) {
         if (hipHostMalloc((void**)&cx.split_seen, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) *cx.split_seen = 0u;
         else { (void)hipGetLastError(); cx.split_seen = nullptr; }
     }
+    const bool has_word = cx.split_seen != nullptr;
+    const SplitPlan p = plan_split(sc, kn, n, SplitWorkspace{has_word, has_word ? *(volatile uint32_t*)cx.split_seen : 0u, cx.split_keep, cx.split_quiet});
+    cx.split_keep = p.keep; cx.split_quiet = p.quiet;
+    out->args.split_min = p.split_min;
+    if (p.split_min == 0) return MFA_OK;
     out->args.seen = cx.split_seen;
-    if (cx.split_seen != nullptr) {
-        const uint32_t seen = *(volatile uint32_t*)cx.split_seen;
-        if (seen == 3u) cx.split_keep = true;
-        cx.split_quiet = seen == 1u ? cx.split_quiet + 1u : 0u;
-        if (!cx.split_keep && (start_quiet || cx.split_quiet >= kSplitQuietCalls) && !(on && on[0] == '2')) return MFA_OK;      // args.hdr stays NULL: no tail
-    }
-    uint64_t chunk_min = (env_u64("MFA_DFA_CHUNK", chunk_min_default) + 15u) & ~(uint64_t)15;
-    if (chunk_min < 16u) chunk_min = 16u;
-    if (chunk_min > (1u << 30)) chunk_min = 1u << 30;
-    if (arena_cap == 0u || arena_cap > kSplitArenaChunks) arena_cap = kSplitArenaChunks;
-    uint64_t arena = env_u64("MFA_DFA_ARENA", arena_cap);               // (tests shrink it to see the chunk size grow)
-    if (arena < 1u) arena = 1u;
-    if (arena > arena_cap) arena = arena_cap;
-    out->chunk_min = (uint32_t)chunk_min;
-    out->arena_chunks = (uint32_t)arena;
-    out->map_cap = (uint32_t)split_map_capacity(arena, kSplitQueueCap);
-    const size_t queue_at = 256, maps_at = queue_at + (size_t)kSplitQueueCap * sizeof(SplitEntry);
-    int rc = ctx_reserve((void**)&cx.d_split, &cx.split_bytes, maps_at + (size_t)out->map_cap * per_chunk);
+    out->spec_rounds = p.rounds; out->spec_lookback = p.lookback;
+    if (!p.tail) return MFA_OK;                                       // args.hdr stays NULL
+    out->chunk_min = p.chunk_min; out->arena_chunks = p.arena_chunks; out->map_cap = p.map_cap;
+    const int rc = ctx_reserve((void**)&cx.d_split, &cx.split_bytes, p.bytes);
     if (rc != MFA_OK) return rc;
     out->args.hdr = reinterpret_cast<uint32_t*>(cx.d_split);
-    out->args.queue = reinterpret_cast<SplitEntry*>(cx.d_split + queue_at);
+    out->args.queue = reinterpret_cast<SplitEntry*>(cx.d_split + p.queue_at);
     out->args.qcap = kSplitQueueCap;
-    out->maps = cx.d_split + maps_at;
+    out->maps = cx.d_split + p.arena_at;
     HIP_TRY(hipMemsetAsync(cx.d_split, 0, SPLIT_H_WORDS * sizeof(uint32_t), (hipStream_t)stream));
-    cx.split_ran = true;
+    cx.split_ran = sc.tail != TAIL_SET; cx.spec_ran = sc.tail == TAIL_SPEC; cx.set_split_ran = sc.tail == TAIL_SET;
     return MFA_OK;
 }
 
@@ -258,13 +208,14 @@ static int split_tail_dir(const HostImage& img, DeviceState& ds, const SplitLaun
     // a workgroup may have on gfx950 (tests/test_dfa_split_gpu.py runs that shape)
     const size_t lds = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t);
     const uint64_t per_cu = lds_blocks_per_cu(lds + 512u);
-    const unsigned n_cus = (unsigned)(ds.n_cus > 0 ? ds.n_cus : 256);
+    const unsigned n_cus = (unsigned)ds.n_cus;
+    const uint32_t lanes_log2 = split_lanes_log2(img.dfa_states);
     HIP_TRY(hipFuncSetAttribute((const void*)dfa_chunk_kernel<REV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(dfa_chunk_kernel<REV>, dim3(n_cus * (unsigned)per_cu), dim3(256), lds, s, (const uint16_t*)ds.d_dfa_trans, ds.d_byte_class,
-                       img.dfa_states, img.n_classes, d_bytes, d_offsets, (const uint32_t*)sl.args.hdr, sl.args.queue, sl.maps, sl.lanes_log2);
+                       img.dfa_states, img.n_classes, d_bytes, d_offsets, (const uint32_t*)sl.args.hdr, sl.args.queue, sl.maps, lanes_log2);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(d_states != nullptr ? dfa_fold_kernel<true> : dfa_fold_kernel<false>, dim3(n_cus * 2u), dim3(256), 0, s, ds.d_dfa_accept,
-                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, sl.lanes_log2, d_states, d_results);
+                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint8_t*)sl.maps, lanes_log2, d_states, d_results);
     HIP_TRY(hipGetLastError());
     return MFA_OK;
 }

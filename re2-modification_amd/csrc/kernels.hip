@@ -3,7 +3,6 @@
 // (Memory automata: regions.hip + walk.hip, or the kernels jit_gen.cpp generates.)
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 
 #include "mfa_internal.h"
@@ -217,71 +216,56 @@ static bool make_packed(const HostImage& img, DfaPacked& pk) {
     return true;
 }
 
-// One launch of a kernel with the fused table in LDS (`lds` bytes of it and, tiled, the input tile), between split_begin and split_tail.
+static_assert(kMemlessTileBytes == 4 * 64 * kTileRow, "memless_plan.h sizes the tile");
+
+// One launch of a kernel with the fused table in LDS (p.lds bytes of it and, tiled, the input tile), with dfa_split.hip's tail behind it.
 // head: what the kernel takes in front of the arguments all of them share.
 template <class Kern, class... Head>
-static int launch_lds(Kern kern, size_t lds, const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
-                      uint64_t n, uint32_t* d_states, uint8_t* d_results, hipStream_t s, const Head&... head) {
-    SplitLaunch sl;
-    int rc = split_begin(img, cx, n, s, &sl);
-    if (rc != MFA_OK) return rc;
-    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(lds);
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, head..., (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
-                       img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results, sl.args);
-    HIP_TRY(hipGetLastError());
-    rc = split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
-    if (rc != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-    return MFA_OK;
+static int launch_lds(Kern kern, const EnginePlan& p, const MemlessKnobs& kn, const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes,
+                      const uint64_t* d_offsets, uint64_t n, uint32_t* d_states, uint8_t* d_results, hipStream_t s, const Head&... head) {
+    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    const bool maps = img.dfa_states >= 2 && img.dfa_states <= 127;      // a lane per live state set and chunk (dfa_split.hip); beyond: no split path
+    return memless_bracket(maps ? split_scheme_lds(split_lanes_log2(img.dfa_states)) : kSplitSchemeNone, kn, cx, n, s,
+        [&](const SplitLaunch& sl) {
+            hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, s, head..., (const uint16_t*)ds.d_dfa_trans, ds.d_dfa_accept, ds.d_byte_class,
+                               img.dfa_states, img.n_classes, d_bytes, d_offsets, n, d_states, d_results, sl.args);
+            return MFA_OK;
+        },
+        [&](const SplitLaunch& sl) { return split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states); });
 }
 
-// Which kernel: table in L2 (dfa_spec.hip) or fused in LDS, there tiled (table + tile <= 64 KiB), SGPR-packed, or untiled.
+// Which kernel: plan_memless_engine (memless_plan.h) says; the packed form also asks the byte classes (make_packed).
+// measured on MI355X, (a|b)*abb, 1M x 1 KiB: table in LDS 4.58 TB/s (3.25 when the packed form was measured: 2.65), untiled 1.0 TB/s -- the
+// LDS table is the default, MFA_DFA_KERNEL=packed selects the SGPR form (which has no resume instantiation), "simple" the untiled walk
 template <bool REV, bool RESUME>
 static int launch_dfa(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
-    if ((size_t)img.dfa_states * kDfaRow > 0xffffu) {                               // beyond 16-bit pre-multiplied states: table in L2
-        uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * 8;
-        if (blocks > cap) blocks = cap;
-        if (blocks == 0) blocks = 1;
-        // long strings of such a table are cut by dfa_spec.hip; MFA_DFA_SPLIT=0, MFA_DFA_SPEC=0 and n >= 2^31 leave split_min 0: the same
-        // kernel with the queue off, and no tail
-        SplitLaunch sl;
-        int rc = spec_begin(img, cx, n, s, &sl);
-        if (rc != MFA_OK) return rc;
-        HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-        rc = spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, d_states, (unsigned)blocks);
-        if (rc == MFA_OK) rc = spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
-        if (rc != MFA_OK) return rc;
-        HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-        return MFA_OK;
+    const MemlessImage im{img.dfa_states, img.n_classes, false, false, 0, 0};
+    MemlessKnobs kn = memless_knobs();
+    EnginePlan p = plan_memless_engine(im, RESUME, kn, n, (uint64_t)ds.n_cus);
+    DfaPacked pk{};
+    if (p.engine == ENGINE_PACKED && !(make_packed(img, pk) && pk.n_lit <= 4)) {
+        kn.kernel = 0;
+        p = plan_memless_engine(im, RESUME, kn, n, (uint64_t)ds.n_cus);
     }
-    const size_t table = (size_t)img.dfa_states * kDfaRow * sizeof(uint16_t), tile = 4 * 64 * kTileRow;
-    const char* mode = getenv("MFA_DFA_KERNEL");                                     // "simple" selects the untiled walk
-    if (!(mode && mode[0] == 's') && table + tile <= 64 * 1024) {
-        // measured on MI355X, (a|b)*abb, 1M x 1 KiB: table in LDS 4.58 TB/s (3.25 when the packed form was measured: 2.65),
-        // untiled 1.0 TB/s -- the LDS table is the default, "packed" selects the SGPR form (which has no resume instantiation)
-        DfaPacked pk{};
-        if (!RESUME && mode && mode[0] == 'p' && make_packed(img, pk) && pk.n_lit <= 4) {
-#define MFA_DFA_PACKED(NL) launch_lds(dfa_tiled_kernel<REV, true, NL, false>, tile, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk)
+#define MFA_DFA_PACKED(NL) launch_lds(dfa_tiled_kernel<REV, true, NL, false>, p, kn, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk)
+    switch (p.engine) {
+        case ENGINE_L2:
+            // long strings of such a table are cut by dfa_spec.hip; MFA_DFA_SPLIT=0, MFA_DFA_SPEC=0 and n >= 2^31 leave split_min 0: the same
+            // kernel with the queue off, and no tail
+            return memless_bracket(kSplitSchemeL2, kn, cx, n, s,
+                [&](const SplitLaunch& sl) { return spec_main(img, ds, sl, d_bytes, d_offsets, n, d_results, s, d_states, p.grid); },
+                [&](const SplitLaunch& sl) { return spec_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states); });
+        case ENGINE_PACKED:
             switch (pk.n_lit) {
-                case 0: return MFA_DFA_PACKED(0);
-                case 1: return MFA_DFA_PACKED(1);
-                case 2: return MFA_DFA_PACKED(2);
-                case 3: return MFA_DFA_PACKED(3);
+                case 0: return MFA_DFA_PACKED(0); case 1: return MFA_DFA_PACKED(1); case 2: return MFA_DFA_PACKED(2); case 3: return MFA_DFA_PACKED(3);
                 default: return MFA_DFA_PACKED(4);
             }
-#undef MFA_DFA_PACKED
-        }
-        return launch_lds(dfa_tiled_kernel<REV, false, 0, RESUME>, table + tile, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk);
+        case ENGINE_TILED: return launch_lds(dfa_tiled_kernel<REV, false, 0, RESUME>, p, kn, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s, pk);
+        case ENGINE_UNTILED: return launch_lds(dfa_walk_kernel<REV, RESUME>, p, kn, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s);
+        default: return MFA_ERR_UNSUPPORTED;      // 128 to 254 state sets: mfa_match_batch has always refused them
     }
-    // 128 to 254 state sets (a table of 64 to 128 KiB): mfa_match_batch has always refused them; mfa_match_batch_resume walks them, one
-    // workgroup per CU (its 160 KiB hold the table)
-    if (!RESUME && table > 64 * 1024) return MFA_ERR_UNSUPPORTED;
-    return launch_lds(dfa_walk_kernel<REV, RESUME>, table, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s);
+#undef MFA_DFA_PACKED
 }
 
 // d_states == NULL: mfa_match_batch; else mfa_match_batch_resume

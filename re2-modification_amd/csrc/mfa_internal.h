@@ -13,7 +13,7 @@
 
 #include "../../include/mfa_hip.h"
 #include "walk_tables.h"
-#include "dfa_split.h"
+#include "dfa_split.h"      // and memless_plan.h: MemlessKnobs, SplitScheme, plan_split, plan_memless_engine, persistent_grid
 #include "walk_plan.h"      // LeanHint, WalkPlanInput, env_int, regions_enabled
 
 #define HIP_TRY(expr)                                                   \
@@ -84,7 +84,7 @@ struct LaunchCtx {
     // split path for long strings of memory-less automata (dfa_split.hip): plan header, queue and map arena of this launch
     uint8_t*            d_split = nullptr;
     size_t              split_bytes = 0;
-    uint32_t*           split_seen = nullptr;  // pinned, device-visible; dfa_split.hip: split_begin has the values
+    uint32_t*           split_seen = nullptr;  // pinned, device-visible; memless_plan.h: SplitWorkspace has the values
     uint32_t            split_quiet = 0;       // calls in a row that found "no long string" there
     bool                split_keep = false;    // a launch without the split kernels met a long string once: this workspace keeps them
     bool                split_ran = false;     // this launch has the split kernels behind its main kernel
@@ -150,45 +150,31 @@ int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, co
 // 68 words, 16-byte aligned); d_results may be NULL
 int launch_nfa_set_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                                uint32_t* d_states, uint8_t* d_results, void* stream);
-// workgroups of 256 lanes with `lds` bytes of LDS each that a CU keeps resident: what its 160 KiB allow, at most 8 (32 waves), at least 1
-inline uint64_t lds_blocks_per_cu(size_t lds) {
-    const uint64_t per_cu = (160u * 1024u) / (lds ? lds : 1);
-    return per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;
-}
-// dfa_split.hip: split_begin in front of the main kernel (its `args` go to that kernel), split_tail behind it
+// dfa_split.hip: split_begin in front of the main kernel (its `args` go to that kernel), the engine's tail behind it
 struct SplitLaunch {
     SplitArgs args{};
     uint8_t*  maps = nullptr;
-    uint32_t  lanes_log2 = 0, chunk_min = 0, arena_chunks = 0, map_cap = 0;
-    uint32_t  spec_rounds = 0, spec_lookback = 0;      // dfa_spec.hip: repair launches and lookback bytes of this call (`maps` holds its records)
+    uint32_t  chunk_min = 0, arena_chunks = 0, map_cap = 0;
+    uint32_t  spec_rounds = 0, spec_lookback = 0;      // guess-repair-resolve tails: repair launches and lookback bytes of this call (`maps` holds its records)
 };
-uint64_t env_u64(const char* name, uint64_t dflt);
-bool split_applies(const HostImage& img);
-int  split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
-int  split_begin_arena(LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out, size_t per_chunk, bool start_quiet, uint32_t chunk_min_default,
-                       uint32_t arena_cap = 0u);      // arena_cap: the most chunks of arena (0: kSplitArenaChunks)
+// THE begin of every engine: makes and reads the pinned word, asks plan_split (memless_plan.h), reserves the workspace, zeroes the header
+// and raises the scheme's flags of cx.  out->args.split_min == 0: the path is off; out->args.hdr == NULL: no tail follows this launch.
+int  split_begin(const SplitScheme& sc, const MemlessKnobs& kn, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
 int  split_plan(const SplitLaunch& sl, const uint64_t* d_offsets, void* stream);
-// d_states != NULL (mfa_match_batch_resume): the fold starts from every queued string's word of d_states and writes it back; d_results may then be NULL
+// the tails: nothing when sl.args.hdr == NULL.  d_states != NULL (the resume calls): a queued string starts from its word or record of
+// d_states, which gets what it reaches; d_results may then be NULL
 int  split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                 uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
-// dfa_spec.hip: the same three steps for tables in L2 (255 state sets and more).  spec_main launches the one main kernel of such tables --
-// d_states != NULL: its instantiation for mfa_match_batch_resume -- which queues long strings unless spec_begin has left
-// out->args.split_min == 0 (the path is off); spec_tail launches the kernels behind it (none when out->args.hdr == NULL).
+// dfa_spec.hip: tables in L2 (255 state sets and more).  spec_main launches the one main kernel of such tables -- d_states != NULL: its
+// instantiation for mfa_match_batch_resume
 bool spec_applies(const HostImage& img);
-int  spec_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
 int  spec_main(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                uint8_t* d_results, void* stream, uint32_t* d_states, unsigned blocks);
 int  spec_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                uint8_t* d_results, void* stream, uint32_t* d_states = nullptr);
-// nfa_set_split.hip: the same three steps for a set-walk image.  set_split_begin leaves out->args.split_min == 0 when the path is off
-// (MFA_SET_SPLIT=0, MFA_DFA_SPLIT=0, n >= 2^31); nfa_set.hip hands out->args to its main kernel and calls set_split_tail behind it.
-// d_states != NULL (mfa_match_batch_resume_set): chunk 0 of a queued piece starts from its record, which gets the set reached.
-int  set_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
+// nfa_set_split.hip, nfa_set_wave_split.hip: a set-walk image, a lane or a wave per chunk
 int  set_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                     uint8_t* d_results, void* stream, uint32_t* d_states);
-// nfa_set_wave_split.hip: the same three steps for a wave image, a wave per chunk and records of 68 words (mfa_set_state_wide);
-// nfa_set_wave.hip hands out->args to its main kernel.  d_states != NULL: mfa_match_batch_resume_set_wide.
-int  set_wave_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out);
 int  set_wave_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                          uint8_t* d_results, void* stream, uint32_t* d_states);
 // regions.hip
@@ -220,6 +206,44 @@ typedef std::function<int(const uint8_t* d_bytes, const uint64_t* d_offsets, uin
 int  match_host_staged(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, int device, const HostMatch& match,
                        void* states = nullptr, size_t state_bytes = 0, bool check_lengths = true);
 int  check_device(int device);      // MFA_ERR_NO_DEVICE unless `device` exists; makes it the current one
+
+// ---- one enqueue path of the memory-less engines -------------------------------------------------------------------------------------------
+#ifdef __HIPCC__
+// begin, ev_start, main kernel, tail, ev_stop: what every launch function of these engines does.  main(sl) launches the main kernel with
+// sl.args, tail(sl) the kernels behind it; ev_stop is not recorded behind a tail that failed.
+template <class Main, class Tail>
+int memless_bracket(const SplitScheme& sc, const MemlessKnobs& kn, LaunchCtx& cx, uint64_t n, hipStream_t s, Main main, Tail tail) {
+    SplitLaunch sl;
+    int rc = split_begin(sc, kn, cx, n, s, &sl);
+    if (rc != MFA_OK) return rc;
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
+    if ((rc = main(sl)) != MFA_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    if ((rc = tail(sl)) != MFA_OK) return rc;
+    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
+    return MFA_OK;
+}
+
+// The guess-repair-resolve tail (dfa_spec.hip, nfa_set_split.hip, nfa_set_wave_split.hip) over an arena of records of `words` Rec each,
+// start_used[map_cap], end[2][map_cap]: plan, round 0 into end[0], sl.spec_rounds repairs that read end[(r - 1) & 1] and write end[r & 1],
+// resolve from the last one written.  The callables launch (and return MFA_OK or what kept them from it).
+template <class Rec, class Round0, class Repair, class Resolve>
+int guess_tail(const SplitLaunch& sl, size_t words, const uint64_t* d_offsets, hipStream_t s, Round0 round0, Repair repair, Resolve resolve) {
+    int rc = split_plan(sl, d_offsets, s);
+    if (rc != MFA_OK) return rc;
+    Rec* start_used = reinterpret_cast<Rec*>(sl.maps);
+    Rec* end[2] = {start_used + (size_t)sl.map_cap * words, start_used + 2u * (size_t)sl.map_cap * words};
+    if ((rc = round0(start_used, end[0])) != MFA_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    for (uint32_t r = 1; r <= sl.spec_rounds; r++) {
+        if ((rc = repair(start_used, (const Rec*)end[(r - 1u) & 1u], end[r & 1u])) != MFA_OK) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = resolve((const Rec*)start_used, (const Rec*)end[sl.spec_rounds & 1u])) != MFA_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    return MFA_OK;
+}
+#endif
 
 }  // namespace mfa
 

@@ -10,18 +10,21 @@
 
 namespace mfa {
 
-static constexpr size_t kSetLdsMax = 64u * 1024u;
 static_assert((size_t)kSetMaxDepth * 256u * 4u <= kSetLdsMax, "the stacks alone fit (nfa_set_build holds an image to kSetMaxDepth)");
 
-struct SetLds { uint32_t words, stack_words, in_lds; size_t bytes; };
+// (memless_plan.h has the rule: set_lds, and kSetLdsMax)
+inline SetLds set_lds_of(const HostImage& img) { return set_lds((uint32_t)img.set_tables.size(), img.set_tables[SET_H_DEPTH], img.set_wave); }
+inline MemlessImage set_image(const HostImage& img) { return MemlessImage{0, 0, true, img.set_wave, (uint32_t)img.set_tables.size(), img.set_tables[SET_H_DEPTH]}; }
 
-inline SetLds set_lds_of(const HostImage& img) {
-    SetLds l;
-    l.words = (uint32_t)img.set_tables.size(); l.stack_words = img.set_tables[SET_H_DEPTH] * 256u;
-    l.in_lds = ((size_t)l.stack_words + l.words) * 4u <= kSetLdsMax ? 1u : 0u;
-    l.bytes = ((size_t)l.stack_words + (l.in_lds ? l.words : 0u)) * 4u;
-    return l;
-}
+// the mask width W of a lane image (1, 2, 4, 8 words) and its direction, as template arguments of FN
+#define MFA_SET_DISPATCH(FN, ...)                                                                                      \
+    switch (img.set_tables[SET_H_WORDS]) {                                                                             \
+        case 1: return img.h.is_reversed ? FN<true, 1>(__VA_ARGS__) : FN<false, 1>(__VA_ARGS__);                       \
+        case 2: return img.h.is_reversed ? FN<true, 2>(__VA_ARGS__) : FN<false, 2>(__VA_ARGS__);                       \
+        case 4: return img.h.is_reversed ? FN<true, 4>(__VA_ARGS__) : FN<false, 4>(__VA_ARGS__);                       \
+        case 8: return img.h.is_reversed ? FN<true, 8>(__VA_ARGS__) : FN<false, 8>(__VA_ARGS__);                       \
+    }                                                                                                                  \
+    return MFA_ERR_UNSUPPORTED
 
 // per kernel and device, once; images hold different locks, so the flags are atomic (two first launches at once both set it)
 template <auto KERN>

@@ -63,59 +63,40 @@ nfa_set_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_words,
     }
 }
 
-// d_states == nullptr: nfa_set_kernel; else nfa_set_resume_kernel on these records.  Behind either, the kernels of nfa_set_split.hip for
-// the strings it queued (set_split_begin, set_split_tail); ev_start and ev_stop enclose all of it.
-template <bool REV, int W, bool RESUME>
+// d_states != nullptr: nfa_set_resume_kernel on these records; else nfa_set_kernel.  Behind either, the kernels of nfa_set_split.hip for the
+// strings it queued; ev_start and ev_stop enclose all of it.
+template <bool REV, int W>
 static int launch_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint32_t* d_states, uint8_t* d_results, hipStream_t s) {
     const SetLds l = set_lds_of(img);
-    uint64_t blocks = (n + 255) / 256, cap = (uint64_t)ds.n_cus * lds_blocks_per_cu(l.bytes);
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    int rc = RESUME ? set_allow_lds<nfa_set_resume_kernel<REV, W>>(ds.device) : set_allow_lds<nfa_set_kernel<REV, W>>(ds.device);
+    const bool resume = d_states != nullptr;
+    const MemlessKnobs kn = memless_knobs();
+    const EnginePlan p = plan_memless_engine(set_image(img), resume, kn, n, (uint64_t)ds.n_cus);
+    const uint32_t* tables = (const uint32_t*)ds.d_set_tables;
+    const int rc = resume ? set_allow_lds<nfa_set_resume_kernel<REV, W>>(ds.device) : set_allow_lds<nfa_set_kernel<REV, W>>(ds.device);
     if (rc != MFA_OK) return rc;
-    SplitLaunch sl;
-    rc = set_split_begin(img, cx, n, s, &sl);
-    if (rc != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    if (RESUME)
-        hipLaunchKernelGGL((nfa_set_resume_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.stack_words,
-                           l.in_lds, d_bytes, d_offsets, n, reinterpret_cast<uint4*>(d_states), d_results, sl.args);
-    else
-        hipLaunchKernelGGL((nfa_set_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.stack_words,
-                           l.in_lds, d_bytes, d_offsets, n, d_results, sl.args);
-    HIP_TRY(hipGetLastError());
-    rc = set_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
-    if (rc != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-    return MFA_OK;
-}
-
-template <bool RESUME>
-static int launch_set_by_width(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
-                               uint32_t* d_states, uint8_t* d_results, void* stream) {
-    if (!img.set_walk || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-#define MFA_SET_LAUNCH(W) (img.h.is_reversed ? launch_set<true, W, RESUME>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s) \
-                                             : launch_set<false, W, RESUME>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, s))
-    switch (img.set_tables[SET_H_WORDS]) {
-        case 1: return MFA_SET_LAUNCH(1);
-        case 2: return MFA_SET_LAUNCH(2);
-        case 4: return MFA_SET_LAUNCH(4);
-        case 8: return MFA_SET_LAUNCH(8);
-    }
-#undef MFA_SET_LAUNCH
-    return MFA_ERR_UNSUPPORTED;
+    return memless_bracket(kSplitSchemeSet, kn, cx, n, s,
+        [&](const SplitLaunch& sl) {
+            if (resume)
+                hipLaunchKernelGGL((nfa_set_resume_kernel<REV, W>), dim3(p.grid), dim3(256), p.lds, s, tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets, n,
+                                   reinterpret_cast<uint4*>(d_states), d_results, sl.args);
+            else
+                hipLaunchKernelGGL((nfa_set_kernel<REV, W>), dim3(p.grid), dim3(256), p.lds, s, tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets, n, d_results, sl.args);
+            return MFA_OK;
+        },
+        [&](const SplitLaunch& sl) { return set_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states); });
 }
 
 int launch_nfa_set(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                    uint8_t* d_results, void* stream) {
-    return launch_set_by_width<false>(img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, stream);
+    if (!img.set_walk || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
+    MFA_SET_DISPATCH(launch_set, img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, (hipStream_t)stream);
 }
 
 int launch_nfa_set_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                           uint32_t* d_states, uint8_t* d_results, void* stream) {
-    return launch_set_by_width<true>(img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, stream);
+    if (!img.set_walk || !ds.d_set_tables || img.set_tables.size() < SET_H_SIZE) return MFA_ERR_UNSUPPORTED;
+    MFA_SET_DISPATCH(launch_set, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, (hipStream_t)stream);
 }
 
 }  // namespace mfa

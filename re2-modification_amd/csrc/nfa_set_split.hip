@@ -15,8 +15,6 @@
 // call on -- one long string walked whole costs seconds here, not milliseconds.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "nfa_set.h"
 #include "nfa_set_split_core.h"
 
@@ -98,83 +96,48 @@ nfa_set_resolve_kernel(const uint32_t* __restrict__ tables, uint32_t table_words
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// arena: start_used[map_cap], end[2][map_cap], records of three quarters
-static constexpr size_t kSetSplitBytesPerChunk = 3u * kSetRecQuarters * sizeof(uint4);
-
-int set_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
-    *out = SplitLaunch{};
-    cx.split_ran = false;
-    cx.spec_ran = false;
-    cx.set_split_ran = false;
-    const char* on = getenv("MFA_SET_SPLIT");
-    if ((on && on[0] == '0') || !img.set_walk) return MFA_OK;
-    const uint64_t rounds = env_u64("MFA_SET_SPLIT_ROUNDS", kSetSplitRounds), lookback = env_u64("MFA_SET_SPLIT_LOOKBACK", kSetSplitLookback);
-    out->spec_rounds = (uint32_t)(rounds > kSpecRoundsMax ? kSpecRoundsMax : rounds);
-    out->spec_lookback = (uint32_t)(lookback > MFA_MAX_STRING_BYTES ? MFA_MAX_STRING_BYTES : lookback);
-    // never quiet: cx.split_keep makes split_begin_arena launch the tail whatever the pinned word says
-    cx.split_keep = true;
-    const int rc = split_begin_arena(cx, n, stream, out, kSetSplitBytesPerChunk, false, kSetSplitChunkMin);
-    cx.set_split_ran = cx.split_ran;       // the header's words are mfa_last_set_split's; mfa_last_dfa_split and mfa_last_dfa_spec answer zeros
-    cx.split_ran = false;
-    return rc;
-}
+static_assert(kSplitSchemeSet.per_chunk == 3u * kSetRecQuarters * sizeof(uint4) && kSplitSchemeSet.chunk_min == kSetSplitChunkMin &&
+              kSplitSchemeSet.rounds == kSetSplitRounds && kSplitSchemeSet.lookback == kSetSplitLookback, "memless_plan.h: the lane scheme");
 
 template <bool REV, int W>
 static int set_split_tail_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                              uint8_t* d_results, hipStream_t s, uint32_t* d_states) {
-    int rc = split_plan(sl, d_offsets, s);
-    if (rc != MFA_OK) return rc;
     const SetLds l = set_lds_of(img);
     const uint32_t* tables = (const uint32_t*)ds.d_set_tables;
-    uint4* start_used = reinterpret_cast<uint4*>(sl.maps);
-    uint4* end[2] = {start_used + (size_t)sl.map_cap * kSetRecQuarters, start_used + 2u * (size_t)sl.map_cap * kSetRecQuarters};
-    const uint4* states = reinterpret_cast<const uint4*>(d_states);
+    const SplitEntry* queue = sl.args.queue;
     SetHome home;
     for (int k = 0; k < kSetStateNodeWords; k++) home.w[k] = img.set_home[k];
     // one lane per chunk, the chunk count is the plan's: a grid for every chunk the arena holds, capped by what the CUs keep resident;
     // blocks beyond the count leave at once
-    const uint64_t cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
-    uint64_t blocks = (sl.map_cap + 255u) / 256u, q_blocks = (sl.args.qcap + 255u) / 256u;
-    if (blocks > cap) blocks = cap;
-    if (q_blocks > cap) q_blocks = cap;
-    if ((rc = set_allow_lds<nfa_set_chunk_kernel<REV, W>>(ds.device)) != MFA_OK) return rc;
-    if ((rc = set_allow_lds<nfa_set_repair_kernel<REV, W>>(ds.device)) != MFA_OK) return rc;
-    hipLaunchKernelGGL((nfa_set_chunk_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets,
-                       (const uint32_t*)sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, end[0], states, home, sl.spec_lookback);
-    HIP_TRY(hipGetLastError());
-    for (uint32_t r = 1; r <= sl.spec_rounds; r++) {
-        hipLaunchKernelGGL((nfa_set_repair_kernel<REV, W>), dim3((unsigned)blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes,
-                           d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, start_used, (const uint4*)end[(r - 1u) & 1u], end[r & 1u]);
-        HIP_TRY(hipGetLastError());
-    }
-    const uint4* end_fin = end[sl.spec_rounds & 1u];
-    if (d_states != nullptr) {
-        if ((rc = set_allow_lds<nfa_set_resolve_kernel<REV, W, true>>(ds.device)) != MFA_OK) return rc;
-        hipLaunchKernelGGL((nfa_set_resolve_kernel<REV, W, true>), dim3((unsigned)q_blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes,
-                           d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint4*)start_used, end_fin, reinterpret_cast<uint4*>(d_states), d_results);
-    } else {
-        if ((rc = set_allow_lds<nfa_set_resolve_kernel<REV, W, false>>(ds.device)) != MFA_OK) return rc;
-        hipLaunchKernelGGL((nfa_set_resolve_kernel<REV, W, false>), dim3((unsigned)q_blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes,
-                           d_offsets, sl.args.hdr, (const SplitEntry*)sl.args.queue, (const uint4*)start_used, end_fin, (uint4*)nullptr, d_results);
-    }
-    HIP_TRY(hipGetLastError());
-    return MFA_OK;
+    const uint64_t per_cu = lds_blocks_per_cu(l.bytes);
+    const unsigned blocks = persistent_grid(sl.map_cap, 256, (uint64_t)ds.n_cus, per_cu), q_blocks = persistent_grid(sl.args.qcap, 256, (uint64_t)ds.n_cus, per_cu);
+    return guess_tail<uint4>(sl, kSetRecQuarters, d_offsets, s,
+        [&](uint4* start_used, uint4* end0) {
+            int rc = set_allow_lds<nfa_set_chunk_kernel<REV, W>>(ds.device);
+            if (rc == MFA_OK) rc = set_allow_lds<nfa_set_repair_kernel<REV, W>>(ds.device);
+            if (rc != MFA_OK) return rc;
+            hipLaunchKernelGGL((nfa_set_chunk_kernel<REV, W>), dim3(blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets,
+                               (const uint32_t*)sl.args.hdr, queue, start_used, end0, reinterpret_cast<const uint4*>(d_states), home, sl.spec_lookback);
+            return MFA_OK;
+        },
+        [&](uint4* start_used, const uint4* end_prev, uint4* end_next) {
+            hipLaunchKernelGGL((nfa_set_repair_kernel<REV, W>), dim3(blocks), dim3(256), l.bytes, s, tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets,
+                               sl.args.hdr, queue, start_used, end_prev, end_next);
+            return MFA_OK;
+        },
+        [&](const uint4* start_used, const uint4* end_fin) {
+            const int rc = d_states != nullptr ? set_allow_lds<nfa_set_resolve_kernel<REV, W, true>>(ds.device) : set_allow_lds<nfa_set_resolve_kernel<REV, W, false>>(ds.device);
+            if (rc != MFA_OK) return rc;
+            hipLaunchKernelGGL((d_states != nullptr ? nfa_set_resolve_kernel<REV, W, true> : nfa_set_resolve_kernel<REV, W, false>), dim3(q_blocks), dim3(256), l.bytes, s,
+                               tables, l.words, l.stack_words, l.in_lds, d_bytes, d_offsets, sl.args.hdr, queue, start_used, end_fin, reinterpret_cast<uint4*>(d_states), d_results);
+            return MFA_OK;
+        });
 }
 
 int set_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                    uint8_t* d_results, void* stream, uint32_t* d_states) {
     if (sl.args.hdr == nullptr) return MFA_OK;
-    hipStream_t s = (hipStream_t)stream;
-#define MFA_SET_TAIL(W) (img.h.is_reversed ? set_split_tail_go<true, W>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states) \
-                                           : set_split_tail_go<false, W>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states))
-    switch (img.set_tables[SET_H_WORDS]) {
-        case 1: return MFA_SET_TAIL(1);
-        case 2: return MFA_SET_TAIL(2);
-        case 4: return MFA_SET_TAIL(4);
-        case 8: return MFA_SET_TAIL(8);
-    }
-#undef MFA_SET_TAIL
-    return MFA_ERR_UNSUPPORTED;
+    MFA_SET_DISPATCH(set_split_tail_go, img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream, d_states);
 }
 
 }  // namespace mfa

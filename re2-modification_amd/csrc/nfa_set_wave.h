@@ -9,16 +9,7 @@
 
 namespace mfa {
 
-// what a block takes of LDS: the four stacks and, when both fit kSetLdsMax, the tables behind them
-struct WaveLds { uint32_t words, depth, in_lds; size_t bytes; };
-
-inline WaveLds wave_lds_of(const HostImage& img) {
-    WaveLds l;
-    l.words = (uint32_t)img.set_tables.size(); l.depth = img.set_tables[SET_H_DEPTH];
-    l.in_lds = ((size_t)4u * l.depth + l.words) * 4u <= kSetLdsMax ? 1u : 0u;
-    l.bytes = ((size_t)4u * l.depth + (l.in_lds ? l.words : 0u)) * 4u;
-    return l;
-}
+// what a block takes of LDS: the four stacks and, when both fit kSetLdsMax, the tables behind them (set_lds_of; `stack_words` is 4 * depth)
 static_assert((size_t)4u * kWaveMaxNodes * 4u <= kSetLdsMax, "the stacks alone fit (a chain is never longer than the image has nodes)");
 
 // wave tables on the device, of a width and depth the kernels hold
@@ -27,6 +18,11 @@ inline bool wave_tables_ok(const HostImage& img, const DeviceState& ds) {
     const uint32_t W = img.set_tables[SET_H_WORDS];
     return W >= 1u && W <= kWaveLanes && W == wave_words_of(img.set_tables[SET_H_NODES]) && img.set_tables[SET_H_DEPTH] <= kWaveMaxNodes;
 }
+
+// direction and the tables' place as template arguments of FN
+#define MFA_WAVE_DISPATCH(FN, in_lds, ...)                                                                                                  \
+    (img.h.is_reversed ? ((in_lds) ? FN<true, true>(__VA_ARGS__) : FN<true, false>(__VA_ARGS__))                                            \
+                       : ((in_lds) ? FN<false, true>(__VA_ARGS__) : FN<false, false>(__VA_ARGS__)))
 
 #ifdef __HIPCC__
 // all 256 lanes of a block: where the tables' sections are read from -- their copy behind the four stacks, made here, or global memory.

@@ -36,14 +36,7 @@ nfa_set_wave_kernel(const uint32_t* __restrict__ tables, uint32_t table_words, u
     extern __shared__ uint32_t lds[];
     const uint32_t wave = WaveDev::uni(threadIdx.x >> 6);
     uint32_t* stack = lds + wave * depth;                              // slot s of this wave: stack[s]
-    const uint32_t* base = tables;
-    if (IN_LDS) {
-        uint32_t* copy = lds + 4u * depth;
-        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
-        __syncthreads();
-        base = copy;
-    }
-    const NfaSetView t = nfa_set_view(tables, base);
+    const NfaSetView t = nfa_set_view(tables, wave_tables_base<IN_LDS>(lds, tables, table_words, depth));
     const uint32_t W = tables[SET_H_WORDS];
     const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
     for (uint64_t sid = (uint64_t)blockIdx.x * 4u + wave; sid < n; sid += n_waves) {
@@ -65,14 +58,7 @@ nfa_set_wave_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_w
     extern __shared__ uint32_t lds[];
     const uint32_t wave = WaveDev::uni(threadIdx.x >> 6);
     uint32_t* stack = lds + wave * depth;
-    const uint32_t* base = tables;
-    if (IN_LDS) {
-        uint32_t* copy = lds + 4u * depth;
-        for (uint32_t k = threadIdx.x; k < table_words; k += 256u) copy[k] = tables[k];
-        __syncthreads();
-        base = copy;
-    }
-    const NfaSetView t = nfa_set_view(tables, base);
+    const NfaSetView t = nfa_set_view(tables, wave_tables_base<IN_LDS>(lds, tables, table_words, depth));
     const uint32_t W = tables[SET_H_WORDS], n_nodes = tables[SET_H_NODES];
     const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
     for (uint64_t sid = (uint64_t)blockIdx.x * 4u + wave; sid < n; sid += n_waves) {
@@ -86,64 +72,39 @@ nfa_set_wave_resume_kernel(const uint32_t* __restrict__ tables, uint32_t table_w
     }
 }
 
-// Behind either main kernel, the kernels of nfa_set_wave_split.hip for the strings it queued (set_wave_split_begin, set_wave_split_tail);
-// ev_start and ev_stop enclose all of it.
+// d_states != nullptr: nfa_set_wave_resume_kernel on these records; else nfa_set_wave_kernel.  Behind either, the kernels of
+// nfa_set_wave_split.hip for the strings it queued; ev_start and ev_stop enclose all of it.
 template <bool REV, bool IN_LDS>
-static int launch_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+static int launch_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
                        uint8_t* d_results, hipStream_t s) {
-    uint64_t blocks = (n + 3) / 4, cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    int rc = set_allow_lds<nfa_set_wave_kernel<REV, IN_LDS>>(ds.device);
+    const bool resume = d_states != nullptr;
+    const MemlessKnobs kn = memless_knobs();
+    const EnginePlan p = plan_memless_engine(set_image(img), resume, kn, n, (uint64_t)ds.n_cus);
+    const uint32_t* tables = (const uint32_t*)ds.d_set_tables;
+    const uint32_t words = (uint32_t)img.set_tables.size(), depth = img.set_tables[SET_H_DEPTH];
+    const int rc = resume ? set_allow_lds<nfa_set_wave_resume_kernel<REV, IN_LDS>>(ds.device) : set_allow_lds<nfa_set_wave_kernel<REV, IN_LDS>>(ds.device);
     if (rc != MFA_OK) return rc;
-    SplitLaunch sl;
-    if ((rc = set_wave_split_begin(img, cx, n, s, &sl)) != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    hipLaunchKernelGGL((nfa_set_wave_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.depth, d_bytes,
-                       d_offsets, n, d_results, sl.args);
-    HIP_TRY(hipGetLastError());
-    if ((rc = set_wave_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, nullptr)) != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-    return MFA_OK;
+    return memless_bracket(kSplitSchemeWave, kn, cx, n, s,
+        [&](const SplitLaunch& sl) {
+            if (resume)
+                hipLaunchKernelGGL((nfa_set_wave_resume_kernel<REV, IN_LDS>), dim3(p.grid), dim3(256), p.lds, s, tables, words, depth, d_bytes, d_offsets, n, d_states, d_results, sl.args);
+            else
+                hipLaunchKernelGGL((nfa_set_wave_kernel<REV, IN_LDS>), dim3(p.grid), dim3(256), p.lds, s, tables, words, depth, d_bytes, d_offsets, n, d_results, sl.args);
+            return MFA_OK;
+        },
+        [&](const SplitLaunch& sl) { return set_wave_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states); });
 }
 
 int launch_nfa_set_wave(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_results, void* stream) {
     if (!wave_tables_ok(img, ds)) return MFA_ERR_UNSUPPORTED;
-    const WaveLds l = wave_lds_of(img);
-    hipStream_t s = (hipStream_t)stream;
-    if (img.h.is_reversed)
-        return l.in_lds ? launch_wave<true, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s) : launch_wave<true, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s);
-    return l.in_lds ? launch_wave<false, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s) : launch_wave<false, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_results, s);
-}
-
-template <bool REV, bool IN_LDS>
-static int launch_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const WaveLds& l, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t* d_states,
-                              uint8_t* d_results, hipStream_t s) {
-    uint64_t blocks = (n + 3) / 4, cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    int rc = set_allow_lds<nfa_set_wave_resume_kernel<REV, IN_LDS>>(ds.device);
-    if (rc != MFA_OK) return rc;
-    SplitLaunch sl;
-    if ((rc = set_wave_split_begin(img, cx, n, s, &sl)) != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_start, s));
-    hipLaunchKernelGGL((nfa_set_wave_resume_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, (const uint32_t*)ds.d_set_tables, l.words, l.depth,
-                       d_bytes, d_offsets, n, d_states, d_results, sl.args);
-    HIP_TRY(hipGetLastError());
-    if ((rc = set_wave_split_tail(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states)) != MFA_OK) return rc;
-    HIP_TRY(hipEventRecord((hipEvent_t)cx.ev_stop, s));
-    return MFA_OK;
+    return MFA_WAVE_DISPATCH(launch_wave, set_lds_of(img).in_lds != 0u, img, ds, cx, d_bytes, d_offsets, n, nullptr, d_results, (hipStream_t)stream);
 }
 
 int launch_nfa_set_wave_resume(const HostImage& img, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                                uint32_t* d_states, uint8_t* d_results, void* stream) {
     if (!wave_tables_ok(img, ds)) return MFA_ERR_UNSUPPORTED;
-    const WaveLds l = wave_lds_of(img);
-    hipStream_t s = (hipStream_t)stream;
-    if (img.h.is_reversed)
-        return l.in_lds ? launch_wave_resume<true, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<true, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
-    return l.in_lds ? launch_wave_resume<false, true>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s) : launch_wave_resume<false, false>(img, ds, cx, l, d_bytes, d_offsets, n, d_states, d_results, s);
+    return MFA_WAVE_DISPATCH(launch_wave, set_lds_of(img).in_lds != 0u, img, ds, cx, d_bytes, d_offsets, n, d_states, d_results, (hipStream_t)stream);
 }
 
 }  // namespace mfa

@@ -18,8 +18,6 @@
 // capped by lds_blocks_per_cu.  A block that finds no chunk leaves before it touches LDS.  The workspace is never quiet.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "nfa_set_split_core.h"      // kSetSplitLookback, kSetSplitRounds: shared with the lane images
 #include "nfa_set_wave.h"
 #include "nfa_set_wave_split_core.h"
@@ -103,80 +101,50 @@ nfa_set_wave_resolve_kernel(const uint32_t* __restrict__ tables, uint32_t table_
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// arena: start_used[map_cap], end[2][map_cap], records of 68 words
-static constexpr size_t kWaveSplitBytesPerChunk = 3u * kWaveStateWords * sizeof(uint32_t);
-static_assert(kWaveSplitBytesPerChunk == 816u, "three wide records per chunk");
-
-// set_split_begin (nfa_set_split.hip) for a wave image: the same knobs, the wave path's chunk minimum, record size and arena cap
-int set_wave_split_begin(const HostImage& img, LaunchCtx& cx, uint64_t n, void* stream, SplitLaunch* out) {
-    *out = SplitLaunch{};
-    cx.split_ran = false;
-    cx.spec_ran = false;
-    cx.set_split_ran = false;
-    const char* on = getenv("MFA_SET_SPLIT");
-    if ((on && on[0] == '0') || !img.set_wave) return MFA_OK;
-    const uint64_t rounds = env_u64("MFA_SET_SPLIT_ROUNDS", kSetSplitRounds), lookback = env_u64("MFA_SET_SPLIT_LOOKBACK", kSetSplitLookback);
-    out->spec_rounds = (uint32_t)(rounds > kSpecRoundsMax ? kSpecRoundsMax : rounds);
-    out->spec_lookback = (uint32_t)(lookback > MFA_MAX_STRING_BYTES ? MFA_MAX_STRING_BYTES : lookback);
-    // never quiet: cx.split_keep makes split_begin_arena launch the tail whatever the pinned word says
-    cx.split_keep = true;
-    const int rc = split_begin_arena(cx, n, stream, out, kWaveSplitBytesPerChunk, false, kWaveSplitChunkMin, kWaveSplitArenaChunks);
-    cx.set_split_ran = cx.split_ran;       // the header's words are mfa_last_set_split's; mfa_last_dfa_split and mfa_last_dfa_spec answer zeros
-    cx.split_ran = false;
-    return rc;
-}
+static_assert(kSplitSchemeWave.per_chunk == 3u * kWaveStateWords * sizeof(uint32_t) && kSplitSchemeWave.chunk_min == kWaveSplitChunkMin &&
+              kSplitSchemeWave.arena_cap == kWaveSplitArenaChunks && kSplitSchemeWave.rounds == kSetSplitRounds && kSplitSchemeWave.lookback == kSetSplitLookback,
+              "memless_plan.h: the wave scheme, three wide records per chunk");
 
 template <bool REV, bool IN_LDS>
 static int wave_split_tail_go(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results,
                               hipStream_t s, uint32_t* d_states) {
-    int rc = split_plan(sl, d_offsets, s);
-    if (rc != MFA_OK) return rc;
-    const WaveLds l = wave_lds_of(img);
+    const SetLds l = set_lds_of(img);
     const uint32_t* tables = (const uint32_t*)ds.d_set_tables;
-    const SplitEntry* queue = (const SplitEntry*)sl.args.queue;
-    uint32_t* start_used = reinterpret_cast<uint32_t*>(sl.maps);
-    uint32_t* end[2] = {start_used + (size_t)sl.map_cap * kWaveStateWords, start_used + 2u * (size_t)sl.map_cap * kWaveStateWords};
+    const uint32_t depth = img.set_tables[SET_H_DEPTH];
+    const SplitEntry* queue = sl.args.queue;
     // one wave per chunk, the chunk count is the plan's: a grid for every chunk the arena holds, capped by what the CUs keep resident;
     // blocks beyond the count leave at once
-    const uint64_t cap = (uint64_t)(ds.n_cus > 0 ? ds.n_cus : 256) * lds_blocks_per_cu(l.bytes);
-    uint64_t blocks = ((uint64_t)sl.map_cap + 3u) / 4u, q_blocks = ((uint64_t)sl.args.qcap + 3u) / 4u;
-    if (blocks > cap) blocks = cap;
-    if (q_blocks > cap) q_blocks = cap;
-    if ((rc = set_allow_lds<nfa_set_wave_chunk_kernel<REV, IN_LDS>>(ds.device)) != MFA_OK) return rc;
-    if ((rc = set_allow_lds<nfa_set_wave_repair_kernel<REV, IN_LDS>>(ds.device)) != MFA_OK) return rc;
-    hipLaunchKernelGGL((nfa_set_wave_chunk_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, tables, l.words, l.depth, d_bytes, d_offsets,
-                       (const uint32_t*)sl.args.hdr, queue, start_used, end[0], (const uint32_t*)d_states, (const uint32_t*)ds.d_set_home, sl.spec_lookback);
-    HIP_TRY(hipGetLastError());
-    for (uint32_t r = 1; r <= sl.spec_rounds; r++) {
-        hipLaunchKernelGGL((nfa_set_wave_repair_kernel<REV, IN_LDS>), dim3((unsigned)blocks), dim3(256), l.bytes, s, tables, l.words, l.depth, d_bytes, d_offsets,
-                           sl.args.hdr, queue, start_used, (const uint32_t*)end[(r - 1u) & 1u], end[r & 1u]);
-        HIP_TRY(hipGetLastError());
-    }
-    const uint32_t* end_fin = end[sl.spec_rounds & 1u];
-    if (d_states != nullptr) {
-        if ((rc = set_allow_lds<nfa_set_wave_resolve_kernel<REV, IN_LDS, true>>(ds.device)) != MFA_OK) return rc;
-        hipLaunchKernelGGL((nfa_set_wave_resolve_kernel<REV, IN_LDS, true>), dim3((unsigned)q_blocks), dim3(256), l.bytes, s, tables, l.words, l.depth, d_bytes, d_offsets,
-                           sl.args.hdr, queue, (const uint32_t*)start_used, end_fin, d_states, d_results);
-    } else {
-        if ((rc = set_allow_lds<nfa_set_wave_resolve_kernel<REV, IN_LDS, false>>(ds.device)) != MFA_OK) return rc;
-        hipLaunchKernelGGL((nfa_set_wave_resolve_kernel<REV, IN_LDS, false>), dim3((unsigned)q_blocks), dim3(256), l.bytes, s, tables, l.words, l.depth, d_bytes, d_offsets,
-                           sl.args.hdr, queue, (const uint32_t*)start_used, end_fin, (uint32_t*)nullptr, d_results);
-    }
-    HIP_TRY(hipGetLastError());
-    return MFA_OK;
+    const uint64_t per_cu = lds_blocks_per_cu(l.bytes);
+    const unsigned blocks = persistent_grid(sl.map_cap, 4, (uint64_t)ds.n_cus, per_cu), q_blocks = persistent_grid(sl.args.qcap, 4, (uint64_t)ds.n_cus, per_cu);
+    return guess_tail<uint32_t>(sl, kWaveStateWords, d_offsets, s,
+        [&](uint32_t* start_used, uint32_t* end0) {
+            int rc = set_allow_lds<nfa_set_wave_chunk_kernel<REV, IN_LDS>>(ds.device);
+            if (rc == MFA_OK) rc = set_allow_lds<nfa_set_wave_repair_kernel<REV, IN_LDS>>(ds.device);
+            if (rc != MFA_OK) return rc;
+            hipLaunchKernelGGL((nfa_set_wave_chunk_kernel<REV, IN_LDS>), dim3(blocks), dim3(256), l.bytes, s, tables, l.words, depth, d_bytes, d_offsets,
+                               (const uint32_t*)sl.args.hdr, queue, start_used, end0, (const uint32_t*)d_states, (const uint32_t*)ds.d_set_home, sl.spec_lookback);
+            return MFA_OK;
+        },
+        [&](uint32_t* start_used, const uint32_t* end_prev, uint32_t* end_next) {
+            hipLaunchKernelGGL((nfa_set_wave_repair_kernel<REV, IN_LDS>), dim3(blocks), dim3(256), l.bytes, s, tables, l.words, depth, d_bytes, d_offsets,
+                               sl.args.hdr, queue, start_used, end_prev, end_next);
+            return MFA_OK;
+        },
+        [&](const uint32_t* start_used, const uint32_t* end_fin) {
+            const int rc = d_states != nullptr ? set_allow_lds<nfa_set_wave_resolve_kernel<REV, IN_LDS, true>>(ds.device)
+                                               : set_allow_lds<nfa_set_wave_resolve_kernel<REV, IN_LDS, false>>(ds.device);
+            if (rc != MFA_OK) return rc;
+            hipLaunchKernelGGL((d_states != nullptr ? nfa_set_wave_resolve_kernel<REV, IN_LDS, true> : nfa_set_wave_resolve_kernel<REV, IN_LDS, false>), dim3(q_blocks),
+                               dim3(256), l.bytes, s, tables, l.words, depth, d_bytes, d_offsets, sl.args.hdr, queue, start_used, end_fin, d_states, d_results);
+            return MFA_OK;
+        });
 }
 
 int set_wave_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets, uint8_t* d_results,
                         void* stream, uint32_t* d_states) {
     if (sl.args.hdr == nullptr) return MFA_OK;
     if (!wave_tables_ok(img, ds) || ds.d_set_home == nullptr) return MFA_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const bool in_lds = wave_lds_of(img).in_lds != 0u;
-    if (img.h.is_reversed)
-        return in_lds ? wave_split_tail_go<true, true>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states)
-                      : wave_split_tail_go<true, false>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
-    return in_lds ? wave_split_tail_go<false, true>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states)
-                  : wave_split_tail_go<false, false>(img, ds, sl, d_bytes, d_offsets, d_results, s, d_states);
+    return MFA_WAVE_DISPATCH(wave_split_tail_go, set_lds_of(img).in_lds != 0u, img, ds, sl, d_bytes, d_offsets, d_results, (hipStream_t)stream, d_states);
 }
 
 }  // namespace mfa

@@ -16,7 +16,8 @@ shim="-Ishim -Wno-unknown-pragmas -Wno-unused-function -Wno-unused-variable"
 # NAME          optimisation   more flags                              sources beside NAME_emul.cpp
 case $name in
 walk)           opt=-O1        more="$shim -Wno-maybe-uninitialized"   src="$csrc/walk_tables.cpp $csrc/image_host.cpp" ;;
-plan|dfa_plan)  opt=-O1        more=                                   src= ;;
+plan|dfa_plan|memless_plan)
+                opt=-O1        more=                                   src= ;;
 dfa_split|dfa_resume|dfa_mixed|nfa_set|nfa_set_resume)
                 opt=-O1        more=$shim                              src=$csrc/image_host.cpp ;;
 # (-O2: these walk every string several times, or do 64 lanes' work per step)

@@ -69,6 +69,8 @@ typedef struct mfa_image_info {
 #define MFA_KERNEL_SPECIALISED 2u /* mfa_jit_kernel: the walk generated for one automaton, one slot per node in VGPRs */
 #define MFA_KERNEL_TABLE       3u /* dfa_walk_kernel: tabulated memory-less automaton                    */
 #define MFA_KERNEL_NODESET     4u /* nfa_set_kernel, nfa_set_resume_kernel, nfa_set_wave_kernel: memory-less automaton beyond the tabulation limit, walked as a set of live nodes */
+/* what a call that is no match call leaves in last_kernel; numbered on from the match kernels above */
+#define MFA_KERNEL_SEARCH      (MFA_KERNEL_NODESET + 1u) /* = 5: search_pass1_*_kernel, search_pass2_kernel -- mfa_search_batch, the search inside lines */
 
 /* Build an image from a blob (include/mfa_image_format.h).  Host-only work: parse,
  * check the structural invariants the kernels rely on, and for MFA_KIND_NFA tabulate
@@ -482,6 +484,37 @@ int mfa_select_write(const uint8_t* d_bytes, const uint64_t* d_offsets, const ui
                      const void* d_workspace, mfa_select_info* d_info,
                      uint8_t* d_out_bytes, uint64_t bytes_capacity, uint64_t* d_out_offsets, uint64_t* d_out_indices,
                      uint64_t max_selected, int device, void* stream);
+
+/* ---- search inside lines ---------------------------------------------------------------------------
+ * Where every match call answers "is the whole string in the language", this one finds the leftmost-longest match INSIDE every string
+ * of a batch: what `grep` (results) and `grep -o` (spans) ask.  For a tabulated memory-less image (kind NFA, 2 to 127 state sets).
+ * Definition.  For string k = bytes[b .. e), a match is a pair b <= i <= j <= e such that mfa_match_batch on this image would answer 1
+ * for bytes[i .. j) taken as a string of its own (an is_reversed image scans that substring from its end, as always).  Reported is the
+ * smallest such i and, for it, the largest j.  Empty matches count: an automaton that accepts the empty string finds i = b everywhere.
+ * Outputs.  Found: d_results[k] = 1, d_spans[2k] = i, d_spans[2k+1] = j -- absolute positions in d_bytes, like the offsets.  Not found:
+ * d_results[k] = 0 and d_spans[2k] = d_spans[2k+1] = b.  A string beyond MFA_MAX_STRING_BYTES is not read: d_results[k] = 2 and an empty
+ * span at b.  d_spans[2n] = d_offsets[n].  d_spans[0 .. 2n] never decreases, so it is itself the offsets array of 2n strings over the
+ * same d_bytes: string 2k is line k's match, string 2k+1 the text between it and the next line's match.  d_span_results (2n bytes) gets
+ * [2k] = d_results[k] and [2k+1] = 0: with it mfa_select_count / mfa_select_write on (d_bytes, d_spans, d_span_results, 2n) and
+ * MFA_SELECT_NEWLINE print every line's match on the device; their indices / 2 are the line numbers.
+ * d_spans may be NULL (results only: the second pass is not launched); d_span_results may be NULL, and needs d_spans.
+ * How.  Two walks per line over two tables derived from the image's own table (csrc/search_tables.h), built by the first call or by
+ * mfa_image_search_info under the image's lock: one from the line's end down, which reads every byte of the batch once and finds i,
+ * and one from i up until no match can go on, which finds j.  One lane walks one line in each pass.
+ * The read rule is mfa_match_batch's: whole aligned 16-byte blocks up to d_offsets[n] rounded up to 16.
+ * Asynchronous on `stream`; re-entrant per (image, device, stream); legal inside a stream capture once a first call on the device has
+ * uploaded the tables.  last_kernel becomes MFA_KERNEL_SEARCH and mfa_last_kernel_ms covers both passes.
+ * n == 0: MFA_OK, and d_spans[0] = d_offsets[0] when d_spans is given.
+ * MFA_ERR_INVALID_ARG: img, d_offsets or d_results NULL; d_span_results without d_spans; a d_spans that is not 8-byte aligned.
+ * MFA_ERR_UNSUPPORTED, answered before the device is touched, every output untouched: a memory automaton, a set-walk image, an image
+ * of more than 127 state sets, an image one of whose two tables passes 127 sets (mfa_image_search_info answers the same).
+ * mfa_search_batch_host: host pointers, as mfa_match_batch_host (spans and span_results may be NULL; a string beyond the limit is
+ * MFA_ERR_TOO_LONG).  mfa_image_search_info: the sets of the two tables, the dead set included (0: the image accepts nothing). */
+int mfa_search_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                     uint8_t* d_results, uint64_t* d_spans, uint8_t* d_span_results, int device, void* stream);
+int mfa_search_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                          uint8_t* results, uint64_t* spans, uint8_t* span_results, int device);
+int mfa_image_search_info(mfa_image_t* img, uint32_t* pass1_states, uint32_t* pass2_states);
 
 /* Same with HOST pointers: copies the batch to the device, matches, copies the
  * results back, synchronises.  Convenience for callers that hold std::strings

@@ -96,6 +96,8 @@ void device_release(DeviceState& ds) {
     if (ds.d_set_tables) (void)hipFree(ds.d_set_tables);
     if (ds.d_set_home) (void)hipFree(ds.d_set_home);
     if (ds.d_walk) (void)hipFree(ds.d_walk);
+    for (uint16_t* t : ds.d_search)
+        if (t) (void)hipFree(t);
     for (LaunchCtx* cx : ds.ctxs) { ctx_free(*cx); delete cx; }
     jit_unload(ds);
     ds = DeviceState{};
@@ -467,6 +469,82 @@ int mfa_image_resume_state_bytes(mfa_image_t* img, uint32_t* bytes) {
     const HostImage& h = img->host;
     *bytes = h.h.kind != MFA_KIND_NFA ? 0u : !h.set_walk ? (uint32_t)sizeof(uint32_t) : h.set_wave ? (uint32_t)sizeof(mfa_set_state_wide) : (uint32_t)sizeof(mfa_set_state);
     return MFA_OK;
+}
+
+// ---- search inside lines (search.hip) ----------------------------------------------------------------------------------------------------
+// which images the search takes: MFA_OK, or the refusal.  Builds the two tables on the way (search_tables.h), once per image; the caller
+// holds img->mu
+static int search_takes(mfa_image_t* img) {
+    const HostImage& h = img->host;
+    if (h.h.kind != MFA_KIND_NFA) return MFA_ERR_UNSUPPORTED;              // a memory automaton's step is no table walk
+    if (h.set_walk || h.dfa_states > kSearchMaxSets) return MFA_ERR_UNSUPPORTED;      // no table, or one that no LDS holds
+    if (img->search.rc == 1) (void)search_tables_build(h, img->search);
+    return img->search.rc;                                                 // MFA_ERR_UNSUPPORTED: one of the two tables passed the limit
+}
+
+int mfa_image_search_info(mfa_image_t* img, uint32_t* pass1_states, uint32_t* pass2_states) {
+    if (!img) return MFA_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(img->mu);
+    const int rc = search_takes(img);
+    if (rc != MFA_OK) return rc;
+    if (pass1_states) *pass1_states = img->search.pass1.states;
+    if (pass2_states) *pass2_states = img->search.pass2.states;
+    return MFA_OK;
+}
+
+int mfa_search_batch(mfa_image_t* img, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint8_t* d_results, uint64_t* d_spans,
+                     uint8_t* d_span_results, int device, void* stream) {
+    if (!img || !d_offsets || !d_results) return MFA_ERR_INVALID_ARG;
+    if ((d_span_results && !d_spans) || ((uintptr_t)d_spans & 7u)) return MFA_ERR_INVALID_ARG;
+    Launch L;
+    L.lk = std::unique_lock<std::mutex>(img->mu);
+    int rc = search_takes(img);
+    if (rc != MFA_OK) return rc;
+    if (n == 0) {
+        if (!d_spans) return MFA_OK;
+        if ((rc = check_device(device)) != MFA_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(d_spans, d_offsets, sizeof(uint64_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));      // spans[0] = offsets[0]
+        return MFA_OK;
+    }
+    if ((rc = device_prepare(img, device, &L.ds)) != MFA_OK) return rc;
+    if ((rc = search_upload(img->search, *L.ds)) != MFA_OK) return rc;      // (the first call on this device: an allocation and a blocking copy)
+    if ((rc = launch_open(img, device, stream, MFA_KERNEL_SEARCH, L)) != MFA_OK) return rc;
+    return launch_search(img->host, img->search, *L.ds, *L.cx, d_bytes, d_offsets, n, d_results, d_spans, d_span_results, stream);
+}
+
+// host pointers: the staging of mfa_match_batch_host, with the spans (made absolute in the caller's offsets again) and their result bytes
+int mfa_search_batch_host(mfa_image_t* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results, uint64_t* spans,
+                          uint8_t* span_results, int device) {
+    if (!img || !offsets || !results || (span_results && !spans)) return MFA_ERR_INVALID_ARG;
+    {
+        std::lock_guard<std::mutex> lk(img->mu);
+        const int rc = search_takes(img);
+        if (rc != MFA_OK) return rc;
+    }
+    if (n == 0) {
+        if (spans) std::memcpy(spans, offsets, sizeof(uint64_t));
+        return MFA_OK;
+    }
+    return match_host_staged(bytes, offsets, n, results, device, [&](const uint8_t* d_bytes, const uint64_t* d_off, uint8_t* d_res, uint64_t, void*) {
+        uint64_t* d_spans = nullptr; uint8_t* d_sr = nullptr;
+        int rc = MFA_OK;
+        hipError_t e = spans ? hipMalloc((void**)&d_spans, (2u * n + 1u) * sizeof(uint64_t)) : hipSuccess;
+        if (e == hipSuccess && span_results) e = hipMalloc((void**)&d_sr, 2u * n);
+        if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+        if (rc == MFA_OK) rc = mfa_search_batch(img, d_bytes, d_off, n, d_res, d_spans, d_sr, device, nullptr);
+        if (rc == MFA_OK) {
+            std::vector<uint64_t> sp(spans ? 2u * n + 1u : 0u);
+            e = hipDeviceSynchronize();
+            if (e == hipSuccess && spans) e = hipMemcpy(sp.data(), d_spans, sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost);
+            if (e == hipSuccess && span_results) e = hipMemcpy(span_results, d_sr, 2u * n, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { set_last_hip_error((int)e); rc = MFA_ERR_HIP; }
+            for (uint64_t& x : sp) x += offsets[0];
+            if (rc == MFA_OK && spans) std::memcpy(spans, sp.data(), sp.size() * sizeof(uint64_t));
+        }
+        if (d_spans) (void)hipFree(d_spans);
+        if (d_sr) (void)hipFree(d_sr);
+        return rc;
+    });
 }
 
 int mfa_last_kernel_ms(mfa_image_t* img, int device, float* ms) {

@@ -15,6 +15,7 @@
 #include "walk_tables.h"
 #include "dfa_split.h"      // and memless_plan.h: MemlessKnobs, SplitScheme, plan_split, plan_memless_engine, persistent_grid
 #include "walk_plan.h"      // LeanHint, WalkPlanInput, env_int, regions_enabled
+#include "search_tables.h"  // SearchTables: the two tables of mfa_search_batch
 
 #define HIP_TRY(expr)                                                   \
     do {                                                                \
@@ -100,6 +101,7 @@ struct DeviceState {
     uint8_t*  d_byte_class = nullptr;
     uint32_t* d_set_tables = nullptr;   // a set-walk image: HostImage::set_tables
     uint32_t* d_set_home = nullptr;     // a wave image: HostImage::set_home_wide, 64 words of their own
+    uint16_t* d_search[2] = {nullptr, nullptr};   // mfa_search_batch: the tables of pass 1 and pass 2 (mfa_image::search), uploaded by its first call
     // launch workspaces
     std::vector<LaunchCtx*> ctxs;
     LaunchCtx*              last = nullptr;    // context of the most recent launch (mfa_last_kernel_ms)
@@ -125,6 +127,7 @@ struct mfa_image {
     uint32_t                          last_kernel = 0;   // MFA_KERNEL_*
     mfa::WalkTables                   walk;              // MFA kind: tables of the live-list walk (walk_tables.h)
     bool                              walk_ok = false;   //   ... built (false: the automaton exceeds the table format)
+    mfa::SearchTables                 search;            // tabulated NFA kind: the tables of mfa_search_batch, built under `mu` by its first call (search_tables.h)
 };
 
 namespace mfa {
@@ -177,6 +180,11 @@ int  set_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl
                     uint8_t* d_results, void* stream, uint32_t* d_states);
 int  set_wave_split_tail(const HostImage& img, DeviceState& ds, const SplitLaunch& sl, const uint8_t* d_bytes, const uint64_t* d_offsets,
                          uint8_t* d_results, void* stream, uint32_t* d_states);
+// search.hip: mfa_search_batch.  search_upload puts the image's two tables on the device once (synchronous); launch_search brackets pass 1
+// and, with d_spans, pass 2 in ev_start and ev_stop
+int  search_upload(const SearchTables& tb, DeviceState& ds);
+int  launch_search(const HostImage& img, const SearchTables& tb, DeviceState& ds, LaunchCtx& cx, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                   uint64_t n, uint8_t* d_results, uint64_t* d_spans, uint8_t* d_span_results, void* stream);
 // regions.hip
 int launch_region_scan(int n_cus, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint64_t* d_table, void* stream, unsigned threads = 256, void* done_event = nullptr);
 // launch contexts (capi.hip); the caller holds the image mutex

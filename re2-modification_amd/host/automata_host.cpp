@@ -348,7 +348,18 @@ void Automata::select_text(const uint8_t* text, size_t n, bool tokens, const cha
     if (n_unanswered) *n_unanswered = 0;
 }
 
-void Automata::match_packed_short(mfa_image* img, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
+// text_match.cpp: the lines of the text searched on the device
+int diploma_search_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n, int device, bool invert, bool only_matching, std::string& out,
+                                  uint64_t* n_unanswered);
+
+void Automata::search_text(const uint8_t* text, size_t n, bool invert, bool only_matching, std::string& out, uint64_t* n_unanswered) {
+    uint64_t unanswered = 0;
+    const int rc = diploma_search_text_on_device(image_for_match(), text, n, device, invert, only_matching, out, &unanswered);
+    if (rc != MFA_OK) fail("Automata::search_text", rc);
+    if (n_unanswered) *n_unanswered = unanswered;
+}
+
+void Automata::match_packed_short(mfa_image* img,const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results) {
     // the devices of the node: all of them by default (north_star: "the string batch shards trivially across the 8 GPUs of one node")
     const int count = mfa_device_count();
     int want = devices;
@@ -495,6 +506,10 @@ void MFA::match_text(const uint8_t* text, size_t n, bool tokens, const char* sto
 
 void MFA::select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered) {
     Automata::select_text(text, n, tokens, stop, invert, out, n_unanswered);      // image_blob() is virtual, as for match_packed
+}
+
+void MFA::search_text(const uint8_t* text, size_t n, bool invert, bool only_matching, std::string& out, uint64_t* n_unanswered) {
+    Automata::search_text(text, n, invert, only_matching, out, n_unanswered);      // (the library refuses a memory automaton: the caller hears its message)
 }
 
 vector<vector<bool>> match_mixed(const vector<MFA*>& automata, const vector<vector<string>>& strs) {

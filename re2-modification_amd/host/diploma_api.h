@@ -160,6 +160,12 @@ public:
     // the text holds a string beyond what one device call takes, or under DIPLOMA_DEVICE_SELECT=0, the selection is done on the host from
     // the answers of match_text; the output is the same.
     void select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered);
+    // The lines of a text that CONTAIN a match -- with `invert`: that contain none -- each with a 0x0a behind it: what `grep` (`grep -v`)
+    // prints; with `only_matching` instead the leftmost-longest match of every line that has one, one per output line (an empty match
+    // is an empty line).  Split, searched (include/mfa_hip.h, "search inside lines") and selected on one device: upload, split,
+    // mfa_search_batch, the selection, its info record back, the kept bytes back.  For a tabulated memory-less automaton; anything the
+    // library refuses throws with its message.  *n_unanswered (may be nullptr): lines beyond what the search reads; they are never kept.
+    void search_text(const uint8_t* text, size_t n, bool invert, bool only_matching, std::string& out, uint64_t* n_unanswered);
 
     // the automaton image handed to the device (include/mfa_image_format.h)
     virtual vector<uint8_t> image_blob() const;
@@ -214,6 +220,7 @@ public:
     void match_packed(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint8_t* results);
     void match_text(const uint8_t* text, size_t n, bool tokens, const char* stop, vector<uint8_t>& results);
     void select_text(const uint8_t* text, size_t n, bool tokens, const char* stop, bool invert, std::string& out, uint64_t* n_unanswered);
+    void search_text(const uint8_t* text, size_t n, bool invert, bool only_matching, std::string& out, uint64_t* n_unanswered);
 
     vector<uint8_t> image_blob() const override;
 };
@@ -358,6 +365,10 @@ bool match_lines(string regexp_str, const string& path, bool reverse, bool bnf, 
 // `invert` those that do not -- each followed by a newline, selected on the device (Automata::select_text).  false: FILE cannot be read.
 // *n_unanswered: lines the device answered neither 0 nor 1 (they are not printed)
 bool grep_lines(string regexp_str, const string& path, bool invert, bool reverse, bool bnf, bool ssnf, uint64_t* n_unanswered);
+// `diploma -search-lines FILE [-v | -o]`: compile as match() does (the header lines are printed), then the lines of FILE that contain a
+// match (`invert`: that contain none), or with `only_matching` the leftmost-longest match of every line that has one, each followed by a
+// newline (Automata::search_text).  false: FILE cannot be read.  *n_unanswered: lines the search did not read (they are not printed)
+bool search_lines(string regexp_str, const string& path, bool invert, bool only_matching, bool reverse, bool bnf, bool ssnf, uint64_t* n_unanswered);
 // matchers/match_mfa.cpp:13,58 counterparts: strings from a file (one per line), one batch, results and
 // timing on stdout
 // The cut points of a batch over `parts` devices: cuts[r] .. cuts[r+1]-1 are the strings of part r (parts + 1 values, cuts[0] = 0,

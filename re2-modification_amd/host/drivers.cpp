@@ -5,6 +5,8 @@
 //                                              split into strings on the device
 //   grep_lines()  (no counterpart)             `./diploma -grep-lines FILE [-v]`: the lines of a file that match (that do not),
 //                                              split, matched and selected on the device
+//   search_lines() (no counterpart)            `./diploma -search-lines FILE [-v | -o]`: the lines of a file that contain a match
+//                                              (that contain none; the matches themselves), split, searched and selected on the device
 //   match_gt()   matchers/match_mfa.cpp:13-56  strings from a file against the Glushkov automaton
 //   match_mfa()  matchers/match_mfa.cpp:58-97  strings from a file against toMFA()'s automaton
 //   run_configuration_examples()  matchers/example_runner.cpp:84-151  `./diploma -match N`: growth curve of one example
@@ -94,6 +96,21 @@ bool grep_lines(string regexp_str, const string& path, bool invert, bool reverse
     string out;
     if (is_mfa) static_cast<MFA*>(automata)->select_text(bytes, text.size(), false, nullptr, invert, out, n_unanswered);
     else automata->select_text(bytes, text.size(), false, nullptr, invert, out, n_unanswered);
+    cout << out << std::flush;
+    return true;
+}
+
+bool search_lines(string regexp_str, const string& path, bool invert, bool only_matching, bool reverse, bool bnf, bool ssnf, uint64_t* n_unanswered) {
+    std::ifstream file(path, std::ios::binary);
+    if (!file.is_open()) return false;
+    const string text = read_all(file);
+    Regexp* regexp = Regexp::parse_regexp(regexp_str);
+    bool is_mfa = false;
+    Automata* automata = regexp->compile(is_mfa, reverse, bnf, ssnf, false);
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+    string out;
+    if (is_mfa) static_cast<MFA*>(automata)->search_text(bytes, text.size(), invert, only_matching, out, n_unanswered);
+    else automata->search_text(bytes, text.size(), invert, only_matching, out, n_unanswered);
     cout << out << std::flush;
     return true;
 }

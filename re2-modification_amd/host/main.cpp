@@ -4,6 +4,7 @@
 //   diploma -match-blocks N [-bnf] [-reverse] [-ssnf] [-all]  as -match for a memory-less regex, every token fed to an Automata::Stream N bytes at a time
 //   diploma -match-lines FILE [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then one 0/1 line per line of FILE, split on the device
 //   diploma -grep-lines FILE [-v] [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then the lines of FILE that match (-v: that do not), selected on the device
+//   diploma -search-lines FILE [-v | -o] [-bnf] [-reverse] [-ssnf] [-all]  regex token from stdin, then the lines of FILE that contain a match (-v: that contain none; -o: the first leftmost-longest match of each line, one per output line -- unlike grep -o one match per line, and an empty match prints an empty line), searched on the device
 //   diploma -dump  [-thompson|-glushkov|-mfa]                 regex token -> automaton image as text
 //   diploma -match-file <gt|mfa> <file>                       matchers/match_mfa.cpp counterparts
 //   diploma -match-mixed [-bnf|-reverse|-ssnf|-all] FILE...   one regex and its strings per file, all files in ONE device call
@@ -197,6 +198,32 @@ int main(int argc, char* argv[]) {
             uint64_t unanswered = 0;
             if (!grep_lines(regex, argv[2], invert, reverse, bnf, ssnf, &unanswered)) { cout << "ERROR\n"; return 1; }
             if (unanswered) { std::cerr << "diploma: -grep-lines: " << unanswered << " lines were not answered\n"; return 2; }
+            return 0;
+        }
+        if (argc > 1 && std::strcmp(argv[1], "-search-lines") == 0) {
+            // what `-match-lines` prints before its answers, then the lines of FILE that CONTAIN a match of the regex (-v: that contain none),
+            // each followed by a newline: `grep` where `-grep-lines` is `grep -x`.  -o: instead, the leftmost-longest match of every line that
+            // has one, one match per output line.  Unlike `grep -o` that is ONE match per line, not every non-overlapping one, and a line
+            // whose match is empty prints an empty line.  For a regex that compiles to a tabulated memory-less automaton of at most 127 state
+            // sets; anything else ends with the library's message and exit status 1.
+            if (argc < 3) { std::cerr << "diploma: -search-lines: which file?\n"; return 1; }
+            bool bnf = false, reverse = false, ssnf = false, invert = false, only_matching = false;
+            for (int i = 3; i < argc; i++) {
+                const string flag = argv[i];
+                if (flag == "-all") bnf = reverse = ssnf = true;
+                else if (flag == "-bnf") bnf = true;
+                else if (flag == "-reverse") reverse = bnf = true;
+                else if (flag == "-ssnf") ssnf = true;
+                else if (flag == "-v") invert = true;
+                else if (flag == "-o") only_matching = true;
+                else { std::cerr << "diploma: -search-lines: unknown flag " << flag << "\n"; return 1; }
+            }
+            if (invert && only_matching) { std::cerr << "diploma: -search-lines: -v and -o exclude each other\n"; return 1; }
+            string regex;
+            cin >> regex;
+            uint64_t unanswered = 0;
+            if (!search_lines(regex, argv[2], invert, only_matching, reverse, bnf, ssnf, &unanswered)) { cout << "ERROR\n"; return 1; }
+            if (unanswered) { std::cerr << "diploma: -search-lines: " << unanswered << " lines were not answered\n"; return 2; }
             return 0;
         }
         if (argc > 1 && std::strcmp(argv[1], "-match") == 0) {

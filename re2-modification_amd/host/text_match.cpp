@@ -119,3 +119,61 @@ int diploma_select_text_on_device(mfa_image_t* img, const uint8_t* text, size_t 
     if (infos.select.n_bytes && hipMemcpy(&out[0], d_out.p, infos.select.n_bytes, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;      // exactly n_bytes
     return MFA_OK;
 }
+
+// Search inside the lines of the text (include/mfa_hip.h, "search inside lines"): split, searched and selected on the device.  `out` gets
+// the lines that hold a match (`invert`: that hold none), or with `only_matching` the leftmost-longest match of every line that has one,
+// each with a 0x0a behind it.  only_matching selects from the spans themselves: they are the offsets of 2n strings over the same bytes,
+// string 2k line k's match, and the span results keep exactly those.  What travels back: the splitter's info record, the selection's,
+// and the kept bytes.  *n_unanswered: lines beyond MFA_MAX_STRING_BYTES, which the search does not read; they are not kept.
+int diploma_search_text_on_device(mfa_image_t* img, const uint8_t* text, size_t n, int device, bool invert, bool only_matching, std::string& out,
+                                  uint64_t* n_unanswered) {
+    out.clear();
+    *n_unanswered = 0;
+    if (invert && only_matching) return MFA_ERR_INVALID_ARG;
+    uint32_t sets1 = 0, sets2 = 0;
+    int rc = mfa_image_search_info(img, &sets1, &sets2);           // an image the search refuses: before the device is touched
+    if (rc != MFA_OK) return rc;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return MFA_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return MFA_ERR_HIP;
+    size_t work_bytes = 0;
+    if ((rc = mfa_split_workspace_bytes(n, &work_bytes)) != MFA_OK) return rc;
+    DeviceBuffer d_text, d_work, d_split_info, d_select_info, d_bytes, d_offsets, d_results, d_spans, d_span_results, d_select_work, d_out, d_out_offsets;
+    const size_t room = (n + 15) / 16 * 16;                      // the read rule: whole 16-byte blocks
+    if ((rc = d_text.alloc(room)) != MFA_OK || (rc = d_work.alloc(work_bytes)) != MFA_OK || (rc = d_split_info.alloc(sizeof(mfa_split_info))) != MFA_OK ||
+        (rc = d_select_info.alloc(sizeof(mfa_select_info))) != MFA_OK) return rc;
+    if (n && hipMemcpy(d_text.p, text, n, hipMemcpyHostToDevice) != hipSuccess) return MFA_ERR_HIP;      // the one upload
+    const uint8_t* const src = n ? (const uint8_t*)d_text.p : nullptr;
+    rc = mfa_split_text_count(src, n, MFA_SPLIT_LINES, nullptr, d_work.p, (mfa_split_info*)d_split_info.p, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    mfa_split_info split;
+    if (hipMemcpy(&split, d_split_info.p, sizeof split, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;
+    const uint64_t n_lines = split.n_strings, capacity = (split.n_bytes + 15) / 16 * 16;
+    const uint64_t n_select = only_matching ? 2u * n_lines : n_lines;
+    size_t select_work_bytes = 0;
+    if ((rc = mfa_select_workspace_bytes(n_select, &select_work_bytes)) != MFA_OK) return rc;
+    if ((rc = d_bytes.alloc(capacity)) != MFA_OK || (rc = d_offsets.alloc((n_lines + 1) * 8)) != MFA_OK || (rc = d_results.alloc(n_lines)) != MFA_OK ||
+        (rc = d_select_work.alloc(select_work_bytes)) != MFA_OK) return rc;
+    if (only_matching && ((rc = d_spans.alloc((2u * n_lines + 1u) * 8)) != MFA_OK || (rc = d_span_results.alloc(2u * n_lines)) != MFA_OK)) return rc;
+    rc = mfa_split_text_write(src, n, MFA_SPLIT_LINES, d_work.p, (mfa_split_info*)d_split_info.p, (uint8_t*)d_bytes.p, capacity, (uint64_t*)d_offsets.p,
+                              n_lines, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    rc = mfa_search_batch(img, (const uint8_t*)d_bytes.p, (const uint64_t*)d_offsets.p, n_lines, (uint8_t*)d_results.p,
+                          only_matching ? (uint64_t*)d_spans.p : nullptr, only_matching ? (uint8_t*)d_span_results.p : nullptr, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    const uint32_t flags = MFA_SELECT_NEWLINE | (invert ? MFA_SELECT_INVERT : 0u);
+    const uint64_t* const sel_offsets = only_matching ? (const uint64_t*)d_spans.p : (const uint64_t*)d_offsets.p;
+    const uint8_t* const sel_results = only_matching ? (const uint8_t*)d_span_results.p : (const uint8_t*)d_results.p;
+    rc = mfa_select_count(sel_results, sel_offsets, n_select, flags, d_select_work.p, (mfa_select_info*)d_select_info.p, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    mfa_select_info sel;
+    if (hipMemcpy(&sel, d_select_info.p, sizeof sel, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;      // the one read-back of the selection
+    *n_unanswered = sel.n_unanswered;
+    if ((rc = d_out.alloc(sel.n_bytes)) != MFA_OK || (rc = d_out_offsets.alloc((sel.n_selected + 1) * 8)) != MFA_OK) return rc;
+    rc = mfa_select_write((const uint8_t*)d_bytes.p, sel_offsets, sel_results, n_select, flags, d_select_work.p, (mfa_select_info*)d_select_info.p,
+                          (uint8_t*)d_out.p, sel.n_bytes, (uint64_t*)d_out_offsets.p, nullptr, sel.n_selected, device, nullptr);
+    if (rc != MFA_OK) return rc;
+    out.resize(sel.n_bytes);
+    if (sel.n_bytes && hipMemcpy(&out[0], d_out.p, sel.n_bytes, hipMemcpyDeviceToHost) != hipSuccess) return MFA_ERR_HIP;      // exactly n_bytes
+    return MFA_OK;
+}

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFA_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libmfa_hip.so")      # (the override: development builds)
 
 OK = 0
-KERNEL_NONE, KERNEL_WALK, KERNEL_SPECIALISED, KERNEL_TABLE, KERNEL_NODESET = 0, 1, 2, 3, 4
+KERNEL_NONE, KERNEL_WALK, KERNEL_SPECIALISED, KERNEL_TABLE, KERNEL_NODESET, KERNEL_SEARCH = 0, 1, 2, 3, 4, 5
 ERR_INVALID_ARG, ERR_BAD_BLOB, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_TOO_LONG, ERR_JIT = -1, -2, -3, -4, -5, -6, -7, -8
 
 EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_image_prepare", "mfa_image_specialize", "mfa_match_batch",
@@ -23,7 +23,8 @@ EXPORTS = ["mfa_image_create", "mfa_image_destroy", "mfa_image_get_info", "mfa_i
            "mfa_match_batch_resume_set", "mfa_match_batch_resume_set_host", "mfa_last_set_split",
            "mfa_match_batch_resume_set_wide", "mfa_match_batch_resume_set_wide_host", "mfa_image_resume_state_bytes",
            "mfa_split_tile_bytes", "mfa_split_workspace_bytes", "mfa_split_text_count", "mfa_split_text_write",
-           "mfa_select_workspace_bytes", "mfa_select_count", "mfa_select_write"]
+           "mfa_select_workspace_bytes", "mfa_select_count", "mfa_select_write",
+           "mfa_search_batch", "mfa_search_batch_host", "mfa_image_search_info"]
 
 DFA_STATE_DEAD, DFA_STATE_START, DFA_STATE_INVALID = 0, 1, 0xffffffff      # words of mfa_match_batch_resume (never stored)
 SET_STATE_WORDS = 12                                                        # a record of mfa_match_batch_resume_set: tag, reserved[3], nodes[8]
@@ -127,6 +128,10 @@ def lib():
             L.mfa_select_workspace_bytes.argtypes = [u64, ctypes.POINTER(ctypes.c_size_t)]
             L.mfa_select_count.argtypes = [vp, vp, u64, ctypes.c_uint32, vp, vp, i32, vp]
             L.mfa_select_write.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, u64, vp, vp, u64, i32, vp]
+        if hasattr(L, "mfa_search_batch"):                # (as above: an older build)
+            L.mfa_search_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, i32, vp]
+            L.mfa_search_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, i32]
+            L.mfa_image_search_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.mfa_strerror.argtypes = [i32]
         L.mfa_strerror.restype = ctypes.c_char_p
         L.mfa_version.restype = ctypes.c_char_p
@@ -292,6 +297,44 @@ class Image:
         out = ctypes.c_uint32()
         _check(lib().mfa_image_resume_state_bytes(self._h, ctypes.byref(out)), "mfa_image_resume_state_bytes")
         return out.value
+
+    def search_tensors(self, d_bytes, d_offsets, d_results=None, d_spans=None, d_span_results=None, stream=None):
+        """mfa_search_batch on torch CUDA tensors: the leftmost-longest match inside every string.  d_bytes uint8, d_offsets int64 (n + 1);
+        d_results: uint8 tensor of n bytes (None: allocated); d_spans: int64 tensor of 2n + 1 words, or None for results only;
+        d_span_results: uint8 tensor of 2n bytes or None (needs d_spans).  Returns d_results[:n].  Asynchronous on `stream`."""
+        import torch
+        n = d_offsets.numel() - 1
+        dev = d_offsets.device.index or 0
+        if d_results is None:
+            d_results = torch.empty(max(n, 1), dtype=torch.uint8, device=d_offsets.device)
+        assert d_spans is None or (d_spans.element_size() == 8 and d_spans.numel() >= 2 * n + 1)
+        assert d_span_results is None or (d_span_results.element_size() == 1 and d_span_results.numel() >= 2 * n)
+        s = stream if stream is not None else torch.cuda.current_stream(d_offsets.device)
+        _check(lib().mfa_search_batch(self._h, d_bytes.data_ptr(), d_offsets.data_ptr(), n, d_results.data_ptr(),
+                                      d_spans.data_ptr() if d_spans is not None else None,
+                                      d_span_results.data_ptr() if d_span_results is not None else None, dev, ctypes.c_void_p(s.cuda_stream)),
+               "mfa_search_batch")
+        return d_results[:n]
+
+    def search_host(self, data, offsets, want_spans=True, device=0):
+        """mfa_search_batch_host: numpy uint8 data + uint64 offsets (n + 1) in host memory -> (results[n], spans[2n + 1], span_results[2n]),
+        the last two None with want_spans=False."""
+        import numpy as np
+        n = len(offsets) - 1
+        res = np.zeros(max(n, 1), dtype=np.uint8)
+        spans = np.zeros(2 * n + 1, dtype=np.uint64) if want_spans else None
+        sres = np.zeros(max(2 * n, 1), dtype=np.uint8) if want_spans else None
+        _check(lib().mfa_search_batch_host(self._h, data.ctypes.data, offsets.ctypes.data, n, res.ctypes.data,
+                                           spans.ctypes.data if want_spans else None, sres.ctypes.data if want_spans else None, device),
+               "mfa_search_batch_host")
+        return res[:n], spans, sres[:2 * n] if want_spans else None
+
+    def search_info(self):
+        """mfa_image_search_info: (sets of the pass 1 table, sets of the pass 2 table), the dead set included; raises ERR_UNSUPPORTED for an
+        image the search refuses"""
+        a, b = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().mfa_image_search_info(self._h, ctypes.byref(a), ctypes.byref(b)), "mfa_image_search_info")
+        return a.value, b.value
 
     def last_kernel_ms(self, device=0):
         ms = ctypes.c_float()
